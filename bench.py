@@ -14,7 +14,11 @@ Workloads (BASELINE.json configs):
      16M-entry maxSignal bitmap.  Every timed step triages against its own
      copy of the 16M-entry state, made before the timed region (the state
      reset is not part of the reference's step), so every timed step runs
-     against the stated maxSignal.  Each step triages a fresh batch.
+     against the stated maxSignal.  Each step triages a fresh batch, up to
+     MAX_BATCHES distinct batches; a longer run takes them again in turn
+     (each still against a fresh copy of the starting state, so the same
+     work), and the --full legs that replay the timed steps (accounting,
+     ordered outputs, pipelined) cover those distinct batches.
   from traces (N=1, reported under "from_traces"): C2 end to end -- the timed
      step also runs the executor signal kernels over the batch's raw PC traces
      (resident in HBM), then triages what they produce.
@@ -35,7 +39,17 @@ Workloads (BASELINE.json configs):
 All inputs are generated on the GPU and resident in HBM before the timed
 region.  value = all signal entries triaged by all ranks / max-over-ranks time.
 
-Run:  python bench.py [--gpus N --steps K --warmup W]
+A plain run does what the headline figure needs and no more: it generates the
+inputs, builds the starting maxSignal, warms up, times the K steps and prints
+the result line.  --full adds every other measurement and check (byte
+accounting and roofline, the ordered-output step, the CPU baselines, the host
+entry point, "from_traces", "steady_state"; --pipeline on request), each of
+which can still be switched off by its own --no-... option.  --dump-outputs DIR
+writes what the last timed step handed its caller (dump_outputs) as
+DIR/<name>.npy; the inputs depend on the arguments alone, so two builds can be
+compared output for output.
+
+Run:  python bench.py [--gpus N --steps K --warmup W] [--full] [--dump-outputs DIR]
       N>1 either under a launcher that sets RANK / LOCAL_RANK / WORLD_SIZE /
       MASTER_* (python -m torch.distributed.run --nproc-per-node N ... bench.py
       --gpus N), or plain: without WORLD_SIZE, `--gpus N` starts the N rank
@@ -125,6 +139,10 @@ HBM_PEAK_GBS = 8000.0  # MI355X HBM3E spec peak (MI355X_MICROARCH.md, chip-level
 U32_WORDS = 1 << 27     # 2^32-bit signal bitmap
 UNIVERSE_SEED = 0x5A17C0DE
 POP_SEED = 0x9091A7E5
+MAX_BATCHES = 32        # distinct resident batches of a workload (3.5 GB each at C2's size); further steps reuse them in turn
+MAX_STATES = 32         # state copies (512 MiB each) of one timed region
+DUMP_SEED = 0xD0C5EED
+DUMP_WORDS = 1 << 21    # bitmap words sampled per set by --dump-outputs (16 MB as float64)
 
 # kernels of one partitioned triage step (sg_bucket.hip), for the per-kernel table
 STEP_KERNELS = ["p1_hist", "p1_scatter", "p2_hist", "p2_scatter", "bucket_triage", "bucket_spill", "scan",
@@ -418,34 +436,87 @@ def account(ctx, maxsig, m0set, newsig, batches, calls, rec_new, diff_vals, diff
     return per
 
 
-def timed_steps(ctx, maxsig, m0set, newsig, batches, rec_new, world, tag=1):
+def timed_steps(ctx, maxsig, m0set, newsig, batches, rec_new, world, tag=1, last=None):
     """K steps, each triaging its batch against its own copy of the starting
     maxSignal (made before the timed region: the state reset is not part of
     the reference's step, fuzzer.go:645-693).  maxsig ends as step 0's copy
-    after step 0.  Returns (wall seconds, per-step triage ms)."""
+    after step 0.  More than MAX_STATES steps run as timed regions of
+    MAX_STATES steps, the state copies made again between the regions (outside
+    the clock), so the memory held does not grow with K; the wall time is the
+    regions' sum.  `last` (a set handle, for --dump-outputs) receives the last
+    step's state.  Returns (wall seconds, per-step triage ms)."""
     tm = StepTimer()
-    states = [maxsig] + [SignalSet(ctx) for _ in batches[1:]]
-    for st in states:
-        call("sg_set_copy", st.h, m0set.h)
-    if world > 1:
-        dist.barrier()
-    torch.cuda.synchronize()
+    states = [maxsig] + [SignalSet(ctx) for _ in batches[1:MAX_STATES]]
+    wall, tri = 0.0, []
     ctx.timing(True)
-    call("sg_ctx_marker", ctx.h, 0, tag)  # the timed region, for kernel traces (scripts/trace_summary.py, pmc_summary.py)
-    t0 = time.perf_counter()
-    for st, b in zip(states, batches):
-        tm.mark()
-        triage(ctx, st, newsig, b, rec_new)
-        tm.mark()
-    call("sg_ctx_marker", ctx.h, 1, tag)
-    torch.cuda.synchronize()
-    if world > 1:
-        dist.barrier()
-    wall = time.perf_counter() - t0
-    tri = [tm.ev[i].elapsed_time(tm.ev[i + 1]) for i in range(0, len(tm.ev), 2)]
+    for k in range(0, len(batches), MAX_STATES):
+        region = list(zip(states, batches[k:k + MAX_STATES]))
+        for st, _ in region:
+            call("sg_set_copy", st.h, m0set.h)
+        if world > 1:
+            dist.barrier()
+        torch.cuda.synchronize()
+        call("sg_ctx_marker", ctx.h, 0, tag)  # the timed region, for kernel traces (scripts/trace_summary.py, pmc_summary.py)
+        t0 = time.perf_counter()
+        for st, b in region:
+            tm.mark()
+            triage(ctx, st, newsig, b, rec_new)
+            tm.mark()
+        call("sg_ctx_marker", ctx.h, 1, tag)
+        torch.cuda.synchronize()
+        if world > 1:
+            dist.barrier()
+        wall += time.perf_counter() - t0
+        tri += [tm.ev[i].elapsed_time(tm.ev[i + 1]) for i in range(0, len(tm.ev), 2)]
+        tm.ev.clear()
+        ctx.kernel_time("scan")  # folds the region's kernel events into the context's per-kernel totals
+    if last is not None:
+        call("sg_set_copy", last, region[-1][0].h)
     for st in states[1:]:
         st.close()
     return wall, tri
+
+
+class SetWords:
+    """A signal set over a torch tensor of its 2^27 bitmap words
+    (sg_set_wrap_dev), so the words can be read with torch."""
+
+    def __init__(self, ctx):
+        self.words = torch.empty(U32_WORDS, dtype=torch.int32, device="cuda")
+        self.h = ctypes.c_void_p()
+        call("sg_set_wrap_dev", ctx.h, ctypes.c_void_p(self.words.data_ptr()), ctypes.byref(self.h))
+
+    def close(self):
+        lib.sg_set_destroy(self.h)
+        self.h, self.words = None, None
+
+
+def dump_outputs(ctx, out_dir, flags, maxsig_last, newsig):
+    """--dump-outputs: what the last timed step handed its caller, as
+    DIR/<name>.npy.  rec_new.npy: its per-record flags (float32, all of them).
+    maxsignal_words.npy / newsignal_words.npy: maxSignal and newSignal after
+    it, as DUMP_WORDS words of the 2^27-word bitmaps at fixed, seeded positions
+    (float64, exact for a 32-bit word; word_index.npy holds the positions).
+    counts.npy: len(maxSignal), len(newSignal), records flagged (float64)."""
+    os.makedirs(out_dir, exist_ok=True)
+    idx = np.sort(np.random.default_rng(DUMP_SEED).integers(0, U32_WORDS, DUMP_WORDS))
+    d_idx = torch.from_numpy(idx).cuda()
+    f = flags.cpu().numpy()
+    np.save(os.path.join(out_dir, "rec_new.npy"), f.astype(np.float32))
+    np.save(os.path.join(out_dir, "word_index.npy"), idx.astype(np.float64))
+    counts = []
+    w = SetWords(ctx)
+    for name, h in (("maxsignal", maxsig_last.h), ("newsignal", newsig.h)):
+        call("sg_set_copy", w.h, h)
+        n = ctypes.c_uint64()
+        call("sg_set_count", w.h, ctypes.byref(n))
+        counts.append(n.value)
+        ctx.sync()
+        torch.cuda.synchronize()
+        words = w.words[d_idx].cpu().numpy().view(np.uint32)
+        np.save(os.path.join(out_dir, name + "_words.npy"), words.astype(np.float64))
+    w.close()
+    np.save(os.path.join(out_dir, "counts.npy"), np.array(counts + [int(f.sum())], dtype=np.float64))
 
 
 def timed_steps_pipelined(ctx, m0set, newsig, batches, flags0):
@@ -562,7 +633,8 @@ def run_c2(ctx, args, cfg, rank):
     g = Gen(cfg)
     t_gen = time.perf_counter()
     warm = g.zipf(ctx, cfg, 2_000_000 + rank)
-    batches = [g.zipf(ctx, cfg, 1_000 + 100_000 * rank + k) for k in range(args.warmup + args.steps)]
+    nb = min(args.warmup + args.steps, MAX_BATCHES)
+    batches = [g.zipf(ctx, cfg, 1_000 + 100_000 * rank + k) for k in range(nb)]
     t_gen = time.perf_counter() - t_gen
     maxnrec = max(b.nrec for b in batches)
     maxnvals = max(b.nvals for b in batches)
@@ -571,27 +643,33 @@ def run_c2(ctx, args, cfg, rank):
     build_m0(ctx, m0set, warm, calls, args.m0, rec_new)
     m0_count = len(m0set)
     del warm
-    for b in batches[: args.warmup]:  # untimed warm-up steps, same state
+    for k in range(args.warmup):  # untimed warm-up steps, same state
         call("sg_set_copy", maxsig.h, m0set.h)
-        triage(ctx, maxsig, newsig, b, rec_new)
+        triage(ctx, maxsig, newsig, batches[k % nb], rec_new)
     torch.cuda.synchronize()
     gpu_flags0 = None
-    timed = batches[args.warmup:]
-    wall, tri = timed_steps(ctx, maxsig, m0set, newsig, timed, rec_new, 1)
+    timed = [batches[(args.warmup + k) % nb] for k in range(args.steps)]
+    legs = timed[:MAX_BATCHES]  # the --full legs below: at most the distinct batches
+    last = SetWords(ctx) if args.dump_outputs else None
+    wall, tri = timed_steps(ctx, maxsig, m0set, newsig, timed, rec_new, 1, last=last.h if last else None)
     kernels = kernel_table(ctx, STEP_KERNELS + OTHER_KERNELS, args.steps)
     ctx.timing(False)
-    call("sg_set_copy", maxsig.h, m0set.h)
-    triage(ctx, maxsig, None, timed[0], rec_new)
-    torch.cuda.synchronize()
-    gpu_flags0 = rec_new[: timed[0].nrec].cpu().numpy()
+    if last:
+        dump_outputs(ctx, args.dump_outputs, rec_new[: timed[-1].nrec], last, newsig)
+        last.close()
+    if not args.no_cpu or args.pipeline or args.host_api:  # step 0's flags, for the legs that check against them
+        call("sg_set_copy", maxsig.h, m0set.h)
+        triage(ctx, maxsig, None, timed[0], rec_new)
+        torch.cuda.synchronize()
+        gpu_flags0 = rec_new[: timed[0].nrec].cpu().numpy()
     res = {"wall_s": wall, "triage_ms": float(np.mean(tri)),
            "m0": m0_count, "units": sum(b.nvals for b in timed), "kernels": kernels, "gen_s": round(t_gen, 2)}
     if not args.no_account:
         diff_vals = torch.empty(maxnvals, dtype=torch.int32, device="cuda")
         diff_off = torch.empty(maxnrec + 1, dtype=torch.int64, device="cuda")
-        res["acct"] = account(ctx, maxsig, m0set, newsig, timed, calls, rec_new, diff_vals, diff_off)
+        res["acct"] = account(ctx, maxsig, m0set, newsig, legs, calls, rec_new, diff_vals, diff_off)
         if args.ordered:
-            res["ordered"] = timed_ordered(ctx, maxsig, m0set, newsig, timed, rec_new, diff_vals, diff_off,
+            res["ordered"] = timed_ordered(ctx, maxsig, m0set, newsig, legs, rec_new, diff_vals, diff_off,
                                            float(np.mean(tri)))
         del diff_vals, diff_off
     if not args.no_cpu:
@@ -599,10 +677,10 @@ def run_c2(ctx, args, cfg, rank):
         res["cpu"] = cpu_baseline(m0_values, timed[0], calls, gpu_flags0, args.cpu_budget, args.cpu_threads,
                                   os.cpu_count())
     if args.pipeline:
-        res["pipelined"] = timed_steps_pipelined(ctx, m0set, newsig, timed, gpu_flags0)
+        res["pipelined"] = timed_steps_pipelined(ctx, m0set, newsig, legs, gpu_flags0)
     if args.host_api:
         res["host_api"] = run_host_api(ctx, timed[0], maxsig, newsig, m0set, gpu_flags0)
-    del batches, timed
+    del batches, timed, legs
     torch.cuda.empty_cache()
     if args.from_traces:
         res["from_traces"] = run_from_traces(ctx, args, cfg, g, maxsig, newsig, m0set, rec_new,
@@ -807,14 +885,15 @@ def run_steady(ctx, args, cfg, g, maxsig, newsig, m0set, rec_new):
         torch.cuda.synchronize()
         del b
     m0_count = len(m0set)
-    batches = [g.population(ctx, cfg, 5_000 + k, args.npop, args.noise) for k in range(args.warmup + args.steps)]
+    nb = min(args.warmup + args.steps, MAX_BATCHES)
+    batches = [g.population(ctx, cfg, 5_000 + k, args.npop, args.noise) for k in range(nb)]
     t_gen = time.perf_counter() - t_gen
     maxnrec = max(b.nrec for b in batches)
     maxnvals = max(b.nvals for b in batches)
-    for b in batches[: args.warmup]:
+    for k in range(args.warmup):
         call("sg_set_copy", maxsig.h, m0set.h)
-        triage(ctx, maxsig, newsig, b, rec_new)
-    timed = batches[args.warmup:]
+        triage(ctx, maxsig, newsig, batches[k % nb], rec_new)
+    timed = [batches[(args.warmup + k) % nb] for k in range(args.steps)]
     f0 = {k: ctx.counter("m0_filter_" + k) for k in ("used", "fallback")}
     wall, tri = timed_steps(ctx, maxsig, m0set, newsig, timed, rec_new, 1, tag=2)
     m0f = {k: ctx.counter("m0_filter_" + k) - f0[k] for k in f0}
@@ -832,7 +911,7 @@ def run_steady(ctx, args, cfg, g, maxsig, newsig, m0set, rec_new):
     if not args.no_account:
         diff_vals = torch.empty(maxnvals, dtype=torch.int32, device="cuda")
         diff_off = torch.empty(maxnrec + 1, dtype=torch.int64, device="cuda")
-        acct = account(ctx, maxsig, m0set, newsig, timed, calls, rec_new, diff_vals, diff_off)
+        acct = account(ctx, maxsig, m0set, newsig, timed[:MAX_BATCHES], calls, rec_new, diff_vals, diff_off)
         out["accounting"] = acct
         out["roofline"] = roofline(acct, float(np.mean(tri)), kernels, "steady")
         del diff_vals, diff_off
@@ -914,6 +993,13 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=8)
     ap.add_argument("--warmup", type=int, default=2)
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline figure: byte accounting and roofline, the ordered-output step, the "
+                         "CPU baselines, the host entry point, from_traces and steady_state (minus the --no-... "
+                         "options given); without it only the timed steps run")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs (flags, sampled maxSignal / newSignal bitmap words, "
+                         "counts) as DIR/<name>.npy")
     ap.add_argument("--mode", choices=["auto", "c2", "c3", "fuzzers"], default="auto",
                     help="auto: c2 at N=1, c3 (hash-sharded one-batch triage) at N>1")
     ap.add_argument("--programs", type=int, default=None, help="programs per GPU (C2: 65536, C3: 131072)")
@@ -946,6 +1032,11 @@ def main():
     ap.add_argument("--pipeline", action="store_true",
                     help="C2: also time the two-stage pipelined loop (syzkaller_amd/pipeline.py)")
     args = ap.parse_args()
+    if not args.full:
+        if args.pipeline:
+            ap.error("--pipeline is a --full measurement")
+        args.no_account = args.no_cpu = True
+        args.ordered = args.host_api = args.from_traces = args.steady = False
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -974,6 +1065,8 @@ def main():
     ctx = Context(local)
     ctx.set_stream(torch.cuda.current_stream().cuda_stream)
 
+    if args.dump_outputs and mode != "c2":
+        raise SystemExit("--dump-outputs covers the single-GPU configuration (C2)")
     if mode == "c3":
         from bench_c3 import run_c3
         result = run_c3(ctx, args, cfg, rank, world)
