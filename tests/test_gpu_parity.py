@@ -331,30 +331,69 @@ def test_signal_set_ops(C):
 class TwoPaths:
     """The same sets kept twice: one pair driven through the ordered-output
     path (the diff CSR from the bucket stage's first owners, sg_triage.hip
-    owned_outputs), one through the flags-only partitioned path."""
+    owned_outputs), and one per regime of the flags-only partitioned path:
+    context option m0_filter 0 (both partition passes and the bucket stage,
+    the digit plane written by pass 1: a fresh batch's path) and 1 (the M0
+    filter between the passes: its tail, or pass 2 from a plane-less pass 1
+    when the survivors overflow).  Which regime auto would pick depends on
+    the slices the context ran before; forced, every batch runs both."""
 
-    def __init__(self, C, ctx=None):
+    def __init__(self, C, ctx=None, filtered=True):
         self.C = C
+        self.ctx = ctx if ctx is not None else C.default_context()
         self.d = (C.SignalSet(ctx), C.SignalSet(ctx))
-        self.f = (C.SignalSet(ctx), C.SignalSet(ctx))
+        self.f = (C.SignalSet(ctx), C.SignalSet(ctx))  # m0_filter 0
+        self.g = (C.SignalSet(ctx), C.SignalSet(ctx)) if filtered else None  # m0_filter 1
+
+    def _pairs(self):
+        return [p for p in (self.d, self.f, self.g) if p is not None]
 
     def add(self, vals):
-        self.C.SignalAdd(self.d[0], vals)
-        self.C.SignalAdd(self.f[0], vals)
+        for p in self._pairs():
+            self.C.SignalAdd(p[0], vals)
 
     def clear(self):
-        for s in self.d + self.f:
-            s.clear()
+        for p in self._pairs():
+            for s in p:
+                s.clear()
+
+    def _launches(self, off):
+        """The batch's launches that hold entries: one, or one per
+        max_launch_records records."""
+        off = np.asarray(off, np.uint64)
+        nrec, m = off.size - 1, int(self.ctx.counter("max_launch_records"))
+        cuts = off[np.minimum(np.arange(0, nrec + m, m), nrec)]
+        return int((np.diff(cuts) > 0).sum())
+
+    def _flags_only(self, pair, mode, vals, off):
+        ctx = self.ctx
+        prev = ctx.get_option("m0_filter")
+        ctx.set_option("m0_filter", mode)
+        try:
+            u0, f0 = ctx.counter("m0_filter_used"), ctx.counter("m0_filter_fallback")
+            flags, _, _ = self.C.triage_batch(pair[0], pair[1], vals, off, want_diff=False)
+            du, df = ctx.counter("m0_filter_used") - u0, ctx.counter("m0_filter_fallback") - f0
+        finally:
+            ctx.set_option("m0_filter", prev)
+        if mode == 0:
+            assert (du, df) == (0, 0), "the M0 filter ran with option m0_filter 0"
+        else:
+            assert du + df >= self._launches(off), (du, df, "the M0 filter was not tried on every launch")
+        return flags
 
     def triage(self, vals, off):
         flags, dv, do = self.C.triage_batch(self.d[0], self.d[1], vals, off)
-        fflags, _, _ = self.C.triage_batch(self.f[0], self.f[1], vals, off, want_diff=False)
+        fflags = self._flags_only(self.f, 0, vals, off)
         assert np.array_equal(flags, fflags), "flags-only path disagrees with the ordered-output path"
+        if self.g is not None:
+            gflags = self._flags_only(self.g, 1, vals, off)
+            assert np.array_equal(flags, gflags), "M0-filter path disagrees with the ordered-output path"
         return flags, dv, do
 
     def exports(self):
         m, n = self.d[0].export(), self.d[1].export()
-        assert np.array_equal(m, self.f[0].export()) and np.array_equal(n, self.f[1].export())
+        for p in self._pairs()[1:]:
+            assert np.array_equal(m, p[0].export()) and np.array_equal(n, p[1].export())
         return m, n
 
 
