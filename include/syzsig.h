@@ -78,7 +78,9 @@ int sg_ctx_kernel_time(sg_ctx* ctx, const char* name, double* ms, uint64_t* laun
  * and "m0_filter_fallback" (record slices it finished / that went on to pass
  * 2), "m0_filter_survivors" (the last launch's), "m0_filter_queued_milli" (the
  * queued fraction of the last partitioned slice, x1000, that auto reads),
- * "m0_filter_halves_log" (the index parts per slice, log2, auto uses now). */
+ * "m0_filter_halves_log" (the index parts per slice, log2, auto uses now);
+ * "hints_candidates" (the last sg_hints_replacers* call's (slot, pair)
+ * matches, before deduplication). */
 int sg_ctx_counter(sg_ctx* ctx, const char* name, uint64_t* out);
 /* Context options.  Every path is selected by its regime; an option only
  * forces one, for a test or a measurement, and no call reads the environment
@@ -505,6 +507,51 @@ int sg_ipc_parse_dev(sg_ctx* ctx, const uint32_t* d_out, const uint64_t* d_out_o
 		     const uint32_t* d_call_nums, uint64_t nprog, uint64_t nrec, int64_t* d_errno, uint8_t* d_fault,
 		     int32_t* d_status, uint64_t* d_sig_off, uint32_t* d_sig_vals, uint64_t* d_cov_off,
 		     uint32_t* d_cov_vals);
+
+/* ---- comparison hints (pkg/ipc/ipc_linux.go:257-304, prog/hints.go) ------- */
+/* The comparison half of readOutCoverage over a batch of programs
+ * (ipc_linux.go:257-304); out / out_off / call_off / call_nums as
+ * sg_ipc_parse's.  A pair is two u64 {key, value}, one AddComp(key, value);
+ * record r's pairs, pairs[2 * pair_off[r] .. 2 * pair_off[r+1]), are the
+ * reader's AddComp calls for that call in the reader's order: per comparison
+ * the type word (SG_IPC_COMPS_TYPE above 7), operands of two words when
+ * (typ & 6) == 6 and of four words read as two little-endian u64 otherwise,
+ * nothing when op1 == op2, else (op2, op1) and, when typ & 1 == 0, also
+ * (op1, op2).  A call's CompMap is the set of its pairs; they are not
+ * deduplicated here.  status[p] is what sg_ipc_parse returns for the same
+ * region; a program whose status is not SG_IPC_OK gets empty lists for all
+ * its records (as its signal does), and so do the calls that did not execute.
+ * pair_off (nrec + 1) is always filled; pairs (capacity cap, in pairs) is
+ * written only when pair_off[nrec] <= cap (the convention of
+ * sg_delta_encode_batch); 2 * ceil(out_off[nprog] / 3) pairs always suffice.
+ * A program's region holds at most 2^32 words (the reader's own view of the
+ * output is 2^28). */
+int sg_ipc_comps(sg_ctx* ctx, const uint32_t* out, const uint64_t* out_off, const uint64_t* call_off,
+		 const uint32_t* call_nums, size_t nprog, int32_t* status, uint64_t* pair_off, uint64_t* pairs,
+		 size_t cap);
+/* Device form: every pointer is device memory, stream-ordered, no host sync.
+ * d_pairs may be NULL when cap is 0 (the offsets alone). */
+int sg_ipc_comps_dev(sg_ctx* ctx, const uint32_t* d_out, const uint64_t* d_out_off, const uint64_t* d_call_off,
+		     const uint32_t* d_call_nums, uint64_t nprog, uint64_t nrec, int32_t* d_status,
+		     uint64_t* d_pair_off, uint64_t* d_pairs, uint64_t cap);
+/* shrinkExpand (prog/hints.go:150-177) over a batch: the loop bodies of
+ * checkConstArg (:95-99) and checkDataArg (:101-118).  Record r's CompMap is
+ * its pairs (pair_off / pairs as above); its argument values are
+ * vals[val_off[r] .. val_off[r+1]): one slot per ConstArg.Val, and one per
+ * window sliceToUint64(Data[i:]), i < min(len, 100), of a DataArg.  Slot i gets
+ * the distinct members of shrinkExpand(vals[i], CompMap_r) at
+ * reps[rep_off[i] .. rep_off[i+1]), ascending (the reference iterates a map).
+ * rep_off (val_off[nrec] + 1) is always filled; reps (capacity cap) is
+ * written only when rep_off[nvals] <= cap.  The number of slots, of pairs and
+ * of (slot, pair) matches must each be below 2^32 (SG_EINVAL otherwise). */
+int sg_hints_replacers(sg_ctx* ctx, const uint64_t* pair_off, const uint64_t* pairs, size_t nrec,
+		       const uint64_t* val_off, const uint64_t* vals, uint64_t* rep_off, uint64_t* reps, size_t cap);
+/* Device form (nvals = val_off[nrec]): stream-ordered but for one small
+ * device-to-host read (about 1 KiB, one wait): the match count that sizes its
+ * workspace and the replacers' varying bits. */
+int sg_hints_replacers_dev(sg_ctx* ctx, const uint64_t* d_pair_off, const uint64_t* d_pairs, uint64_t nrec,
+			   const uint64_t* d_val_off, const uint64_t* d_vals, uint64_t nvals, uint64_t* d_rep_off,
+			   uint64_t* d_reps, uint64_t cap);
 
 #ifdef __cplusplus
 }

@@ -117,6 +117,12 @@ SIGNATURES = {
                              P64, P32]),
     "sg_ipc_parse_dev": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_uint64, c_uint64, c_void_p,
                                  c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "sg_ipc_comps": (c_int, [c_void_p, P32, P64, P64, P32, c_size_t, POINTER(c_int32), P64, P64, c_size_t]),
+    "sg_ipc_comps_dev": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_uint64, c_uint64, c_void_p,
+                                 c_void_p, c_void_p, c_uint64]),
+    "sg_hints_replacers": (c_int, [c_void_p, P64, P64, c_size_t, P64, P64, P64, P64, c_size_t]),
+    "sg_hints_replacers_dev": (c_int, [c_void_p, c_void_p, c_void_p, c_uint64, c_void_p, c_void_p, c_uint64, c_void_p,
+                                       c_void_p, c_uint64]),
 }
 
 

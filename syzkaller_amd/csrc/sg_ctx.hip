@@ -729,6 +729,8 @@ int sg_ctx_counter(sg_ctx* ctx, const char* name, uint64_t* out) {
     *out = ctx->m0f_queued < 0 ? ~0ull : (uint64_t)(ctx->m0f_queued * 1000.0 + 0.5);
   else if (!strcmp(name, "m0_filter_halves_log"))  // the index's parts per slice (log2) the auto regime uses now
     *out = (uint64_t)ctx->m0f_logh;
+  else if (!strcmp(name, "hints_candidates"))  // the last sg_hints_replacers* call's matches (sg_hints.hip)
+    *out = ctx->hints_cands;
   else if (!strcmp(name, "cpu_quota_milli"))
     *out = (uint64_t)(ctx->cpu_quota * 1000.0 + 0.5);
   else {

@@ -122,6 +122,8 @@ struct sg_ctx {
   // the wall time of those copies and of its waits for the staging slots'
   // DMA, and the copy threads used
   uint64_t host_copy_bytes = 0, host_copy_ns = 0, host_wait_ns = 0, host_threads = 0;
+  // the last sg_hints_replacers* call's (slot, pair) matches, before deduplication (sg_hints.hip)
+  uint64_t hints_cands = 0;
   hipStream_t own_stream = nullptr;
   hipStream_t stream = nullptr;
   // grow-only device workspace and pinned host staging

@@ -1,0 +1,115 @@
+"""Comparison hints on the GPU: the executor's comparisons into per-call
+CompMaps (pkg/ipc/ipc_linux.go:257-304) and the matching of argument values
+against them (prog/hints.go:95-177), over batches.
+
+A CompMap travels as the reader's AddComp sequence: an array of {key, value}
+pairs with one offset per call.  Cloning the program, replaceArg and validate
+stay with the caller; what comes back is, per argument value, the replacers
+that shrinkExpand yields, ascending.
+"""
+import ctypes
+
+import numpy as np
+
+from ._lib import call
+from .cover import U64, _ctx, _p32, _p64, _u32, _u64
+
+MAX_DATA_LENGTH = 100  # hints.go:36
+
+
+def ipc_comps(out, out_off, call_off, call_nums=None, ctx=None):
+    """The comparison half of readOutCoverage over a batch of program output
+    regions (arguments as cover.ipc_parse).  Returns (status int32[nprog],
+    pairs u64[n, 2], pair_off u64[nrec + 1]): call r's AddComp(key, value)
+    calls, in the reader's order, are pairs[pair_off[r]:pair_off[r + 1]]."""
+    w, oo, co = _u32(out), _u64(out_off), _u64(call_off)
+    nprog = oo.size - 1
+    assert co.size == nprog + 1
+    nrec = int(co[-1])
+    nums = None if call_nums is None else _u32(call_nums)
+    assert nums is None or nums.size == nrec
+    status = np.empty(max(nprog, 1), dtype=np.int32)
+    po = np.empty(nrec + 1, dtype=U64)
+    cap = 2 * ((w.size + 2) // 3)  # a comparison is >= 3 words and yields <= 2 pairs
+    pairs = np.empty((max(cap, 1), 2), dtype=U64)
+    call("sg_ipc_comps", _ctx(ctx).h, _p32(w), _p64(oo), _p64(co), _p32(nums) if nums is not None else None, nprog,
+         status.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), _p64(po), _p64(pairs), cap)
+    return status[:nprog], pairs[: int(po[-1])], po
+
+
+def comp_maps(pairs, pair_off):
+    """ipc.GetCompMaps: one CompMap (dict key -> set of values) per call."""
+    pairs = _u64(pairs)
+    pairs = pairs.reshape(pairs.size // 2, 2)
+    maps = []
+    for r in range(len(pair_off) - 1):
+        m = {}
+        for k, v in pairs[int(pair_off[r]):int(pair_off[r + 1])].tolist():
+            m.setdefault(k, set()).add(v)
+        maps.append(m)
+    return maps
+
+
+def shrink_expand_batch(pairs, pair_off, vals, val_off, ctx=None, cap=None):
+    """shrinkExpand over a batch: record r's CompMap is its pairs, its argument
+    values vals[val_off[r]:val_off[r + 1]].  Returns (reps, rep_off): value
+    slot i's distinct replacers, ascending, are reps[rep_off[i]:rep_off[i + 1]]."""
+    p, po, v, vo = _u64(pairs), _u64(pair_off), _u64(vals), _u64(val_off)
+    nrec = po.size - 1
+    assert vo.size == nrec + 1 and p.size == 2 * int(po[-1]) and v.size == int(vo[-1])
+    ro = np.empty(v.size + 1, dtype=U64)
+    cap = max(1024, 4 * v.size) if cap is None else int(cap)
+    for _ in range(2):  # a second call when the first capacity was short
+        reps = np.empty(max(cap, 1), dtype=U64)
+        call("sg_hints_replacers", _ctx(ctx).h, _p64(po), _p64(p), nrec, _p64(vo), _p64(v), _p64(ro), _p64(reps), cap)
+        if int(ro[-1]) <= cap:
+            break
+        cap = int(ro[-1])
+    return reps[: int(ro[-1])], ro
+
+
+def _pairs_of(compmap):
+    """A CompMap given as a dict, laid out as its sorted (key, value) items."""
+    items = sorted((int(k), int(v)) for k, vs in compmap.items() for v in vs)
+    return np.array(items, dtype=U64).reshape(len(items), 2)
+
+
+def _one(vals, compmap, ctx):
+    pairs = _pairs_of(compmap)
+    vals = _u64(vals)
+    reps, ro = shrink_expand_batch(pairs, [0, pairs.shape[0]], vals, [0, vals.size], ctx=ctx)
+    return reps, ro
+
+
+def ShrinkExpand(v, compmap, ctx=None):
+    """prog/hints.go:150-177 shrinkExpand: the set of replacers of v."""
+    reps, _ = _one([v], compmap, ctx)
+    return set(reps.tolist())
+
+
+def CheckConstArg(v, compmap, ctx=None):
+    """prog/hints.go:95-99 checkConstArg: the values of the new ConstArgs."""
+    return ShrinkExpand(v, compmap, ctx)
+
+
+def slice_to_uint64(s):
+    """prog/hints.go:188-205 sliceToUint64: little endian, zero padded."""
+    return int.from_bytes(bytes(s[:8]).ljust(8, b"\x00"), "little")
+
+
+def CheckDataArg(data, compmap, ctx=None):
+    """prog/hints.go:101-118 checkDataArg for a userspace -> kernel argument:
+    the set of data strings its callback sees.  One value slot per window
+    Data[i:], i < min(len, 100); each replacer goes back little endian,
+    truncated to the remaining length."""
+    data = bytes(data)
+    n = min(len(data), MAX_DATA_LENGTH)
+    if n == 0:
+        return set()
+    reps, ro = _one([slice_to_uint64(data[i:]) for i in range(n)], compmap, ctx)
+    res = set()
+    for i in range(n):
+        k = min(8, len(data) - i)
+        for rep in reps[int(ro[i]):int(ro[i + 1])].tolist():
+            res.add(data[:i] + rep.to_bytes(8, "little")[:k] + data[i + k:])
+    return res
