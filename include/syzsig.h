@@ -80,7 +80,9 @@ int sg_ctx_kernel_time(sg_ctx* ctx, const char* name, double* ms, uint64_t* laun
  * queued fraction of the last partitioned slice, x1000, that auto reads),
  * "m0_filter_halves_log" (the index parts per slice, log2, auto uses now);
  * "hints_candidates" (the last sg_hints_replacers* call's (slot, pair)
- * matches, before deduplication). */
+ * matches, before deduplication); "exec_comps_general" (the calls the last
+ * sg_exec_comps* call sent down its general path), "exec_comps_fast_cap"
+ * (SG_EXEC_COMPS_FAST_CAP). */
 int sg_ctx_counter(sg_ctx* ctx, const char* name, uint64_t* out);
 /* Context options.  Every path is selected by its regime; an option only
  * forces one, for a test or a measurement, and no call reads the environment
@@ -106,6 +108,8 @@ int sg_ctx_counter(sg_ctx* ctx, const char* name, uint64_t* out);
  *                          records, backing off after fallbacks; 1 always; 0 never)
  *   "m0_filter_halves"     its index in 2^k parts per slice (-1 auto: 2 parts once a
  *                          part overflows; 0..2 forced)
+ *   "exec_comps_path"      sg_exec_comps' path (-1 by each call's distinct records,
+ *                          0 the general path for every call)
  * Unknown keys and out-of-range values return SG_EINVAL. */
 int sg_ctx_set_option(sg_ctx* ctx, const char* key, int64_t value);
 int sg_ctx_get_option(sg_ctx* ctx, const char* key, int64_t* out);
@@ -448,6 +452,53 @@ int sg_exec_signal_queued_dev(sg_ctx* ctx, const uint32_t* d_pcs, const uint64_t
 int sg_triage_traces_queued(sg_ctx* ctx, sg_set* maxsig, sg_set* newsig, const uint32_t* pcs,
 			    const uint64_t* call_off, const uint64_t* prog_off, size_t nprog, uint8_t* rec_new,
 			    uint32_t* sig_vals, uint64_t* sig_off);
+
+/* ---- executor comparisons (executor/executor.h:379-387, :621-673) ---------- */
+/* The flag_collect_comps branch of handle_completion over a batch of raw
+ * KCOV_TRACE_CMP buffers.  recs is the KCOV layout unchanged, four u64 per
+ * record {type, arg1, arg2, pc} (kcov_comparison_t, executor.h:118-123); call c
+ * owns records call_off[c] .. call_off[c+1], call_off[0] == 0.  Any u64 is
+ * legal in every field.  Per call, calls independent:
+ *  - std::sort under operator< (:384, :665-673): by (type, arg1, arg2) as full
+ *    unsigned 64-bit values;
+ *  - std::unique under operator== (:385, :659-663): one record of every run
+ *    equal in those three fields (pc takes no part and is never written, so
+ *    which one stays cannot be observed);
+ *  - kcov_comparison_t::write per survivor (:386-387, :621-657).
+ * comp_off (ncalls + 1) is the prefix sum of each call's comps_size.  comps
+ * holds three u64 per kept comparison in sorted order, {type, arg1', arg2'},
+ * arg' being what write() leaves in the struct (:632-645): sign-extended from
+ * 8, 16 or 32 bits when type & 6 is 0, 2 or 4, unchanged when it is 6.  The
+ * extension comes after sort and unique, as in the reference: two records
+ * that differ only above the operand width stay two entries, in raw order.
+ * word_off (ncalls + 1) / words are the u32 words write() emits, in order:
+ * (uint32_t)type, then (uint32_t)arg1', (uint32_t)arg2' when (type & 6) != 6,
+ * else the low and high halves of arg1' and of arg2' (:646-656).  Pass
+ * word_off == NULL to skip the words.
+ * This is the WRITER's layout: two operand words unless the size is 8.  The
+ * reader of this reference snapshot takes two operand words when the size IS 8
+ * (pkg/ipc/ipc_linux.go:272-289), and sg_ipc_comps keeps reading it that way;
+ * the two are not reconciled here.  A consumer on the device takes the
+ * full-width comps triples and needs no wire detour.
+ * Offsets are always filled; comps (capacity comps_cap, in triples) is written
+ * only when comp_off[ncalls] <= comps_cap, words (capacity words_cap) only when
+ * word_off[ncalls] <= words_cap (the convention of sg_ipc_comps); nrecs triples
+ * and 5 * nrecs words always suffice.  Limits (SG_EINVAL): nrecs < 2^32,
+ * ncalls < 2^31.  A call's word count is kept in 32 bits: a single call of more
+ * than (2^32 - 1) / 5 records is not supported (a KCOV buffer holds 16,383).
+ * A call whose distinct records exceed SG_EXEC_COMPS_FAST_CAP leaves the
+ * one-workgroup shape for the general (radix sort) path; it is never truncated. */
+#define SG_EXEC_COMPS_FAST_CAP 4096
+int sg_exec_comps(sg_ctx* ctx, const uint64_t* recs, const uint64_t* call_off, size_t ncalls, uint64_t* comp_off,
+		  uint64_t* comps, size_t comps_cap, uint64_t* word_off, uint32_t* words, size_t words_cap);
+/* Device form (nrecs = call_off[ncalls]): every pointer is device memory,
+ * stream-ordered.  A batch of more than SG_EXEC_COMPS_FAST_CAP records costs
+ * one small device-to-host read (16 B, one wait): the records of the calls
+ * that left the fast shape size the general path's workspace.  Smaller batches,
+ * and option "exec_comps_path" = 0, read nothing. */
+int sg_exec_comps_dev(sg_ctx* ctx, const uint64_t* d_recs, const uint64_t* d_call_off, uint64_t ncalls, uint64_t nrecs,
+		      uint64_t* d_comp_off, uint64_t* d_comps, uint64_t comps_cap, uint64_t* d_word_off,
+		      uint32_t* d_words, uint64_t words_cap);
 
 /* ---- synthetic Zipf traces (bench / test input generator) ----------------- */
 /* Zipf(s) over `nranks` PC ranks mapped through a permutation seeded by

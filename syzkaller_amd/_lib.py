@@ -108,6 +108,9 @@ SIGNATURES = {
     "sg_exec_signal_queued_dev": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_uint64, c_uint64, c_uint64, c_void_p,
                                           c_void_p, c_void_p]),
     "sg_triage_traces_queued": (c_int, [c_void_p, c_void_p, c_void_p, P32, P64, P64, c_size_t, P8, P32, P64]),
+    "sg_exec_comps": (c_int, [c_void_p, P64, P64, c_size_t, P64, P64, c_size_t, P64, P32, c_size_t]),
+    "sg_exec_comps_dev": (c_int, [c_void_p, c_void_p, c_void_p, c_uint64, c_uint64, c_void_p, c_void_p, c_uint64, c_void_p,
+                                  c_void_p, c_uint64]),
     "sg_gen_zipf_traces_dev": (c_int, [c_void_p, c_uint64, c_uint64, c_double, c_uint32, c_uint64, c_uint64, c_uint32,
                                        c_uint32, c_void_p]),
     "sg_gen_population_traces_dev": (c_int, [c_void_p, c_uint64, c_uint64, c_uint64, c_uint64, c_double, c_double,

@@ -94,12 +94,13 @@ enum SgOpt : int {
   kOptHostCopyThreads,      // host ingest: pageable -> pinned copy threads (0: from the CPU quota)
   kOptM0Filter,             // flags path: the M0 filter (sg_bucket.hip): -1 by the last batches, 0 never, 1 always tried
   kOptM0Halves,             // the filter's index per slice in 2^k parts (-1 by its fill, 0..2 forced)
+  kOptExecCompsPath,        // sg_exec_comps: -1 by each call's distinct records, 0 the general path for every call
   kOptCount
 };
 
 struct sg_ctx {
   int device = 0;
-  int64_t opt[kOptCount] = {0, 0, -1, 1, 0, 0, -1, -1, 0, 0, -1, -1};
+  int64_t opt[kOptCount] = {0, 0, -1, 1, 0, 0, -1, -1, 0, 0, -1, -1, -1};
   // the M0 filter's buffers (lazy, sg_bucket.hip) and its regime state: the
   // last record slice's outcome (1 filtered, 0 partitioned), the queued
   // records of the last partitioned slice (counted on the device, read back
@@ -124,6 +125,8 @@ struct sg_ctx {
   uint64_t host_copy_bytes = 0, host_copy_ns = 0, host_wait_ns = 0, host_threads = 0;
   // the last sg_hints_replacers* call's (slot, pair) matches, before deduplication (sg_hints.hip)
   uint64_t hints_cands = 0;
+  // the calls the last sg_exec_comps* call sent down the general path (sg_exec_comps.hip)
+  uint64_t exec_comps_general = 0;
   hipStream_t own_stream = nullptr;
   hipStream_t stream = nullptr;
   // grow-only device workspace and pinned host staging

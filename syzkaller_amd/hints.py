@@ -1,6 +1,7 @@
-"""Comparison hints on the GPU: the executor's comparisons into per-call
-CompMaps (pkg/ipc/ipc_linux.go:257-304) and the matching of argument values
-against them (prog/hints.go:95-177), over batches.
+"""Comparison hints on the GPU: the executor's own comparison branch over raw
+KCOV_TRACE_CMP buffers (executor/executor.h:379-387), the executor's
+comparisons into per-call CompMaps (pkg/ipc/ipc_linux.go:257-304) and the
+matching of argument values against them (prog/hints.go:95-177), over batches.
 
 A CompMap travels as the reader's AddComp sequence: an array of {key, value}
 pairs with one offset per call.  Cloning the program, replaceArg and validate
@@ -15,6 +16,31 @@ from ._lib import call
 from .cover import U64, _ctx, _p32, _p64, _u32, _u64
 
 MAX_DATA_LENGTH = 100  # hints.go:36
+EXEC_COMPS_FAST_CAP = 4096  # include/syzsig.h SG_EXEC_COMPS_FAST_CAP: a call's distinct records on the fast shape
+
+
+def exec_comps(recs, call_off, ctx=None, words=True):
+    """handle_completion's flag_collect_comps branch (executor.h:379-387) over a
+    batch of raw KCOV_TRACE_CMP buffers: recs u64[n, 4] {type, arg1, arg2, pc},
+    call c's records recs[call_off[c]:call_off[c + 1]].  Returns (comp_off,
+    comps u64[m, 3], word_off, words): call c's sorted, deduplicated
+    comparisons {type, arg1', arg2'} (operands as write() extends them) are
+    comps[comp_off[c]:comp_off[c + 1]], the u32 words write() emits for them
+    words[word_off[c]:word_off[c + 1]] (the writer's widths); word_off and
+    words are None with words=False."""
+    r, co = _u64(recs), _u64(call_off)
+    ncalls = co.size - 1
+    nrecs = int(co[-1])
+    assert r.size == 4 * nrecs
+    cpo = np.empty(ncalls + 1, dtype=U64)
+    comps = np.empty((max(nrecs, 1), 3), dtype=U64)
+    wo = np.empty(ncalls + 1, dtype=U64) if words else None
+    w = np.empty(max(5 * nrecs, 1), dtype=np.uint32) if words else None
+    call("sg_exec_comps", _ctx(ctx).h, _p64(r), _p64(co), ncalls, _p64(cpo), _p64(comps), nrecs,
+         _p64(wo) if words else None, _p32(w) if words else None, 5 * nrecs if words else 0)
+    if not words:
+        return cpo, comps[: int(cpo[-1])], None, None
+    return cpo, comps[: int(cpo[-1])], wo, w[: int(wo[-1])]
 
 
 def ipc_comps(out, out_off, call_off, call_nums=None, ctx=None):
