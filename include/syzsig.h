@@ -79,6 +79,8 @@ int sg_ctx_kernel_time(sg_ctx* ctx, const char* name, double* ms, uint64_t* laun
  * 2), "m0_filter_survivors" (the last launch's), "m0_filter_queued_milli" (the
  * queued fraction of the last partitioned slice, x1000, that auto reads),
  * "m0_filter_halves_log" (the index parts per slice, log2, auto uses now);
+ * "flag_skip_used" (bucket launches run in two phases), "flag_skip_full_blocks"
+ * (fully queued 4096-record blocks the last of them found after its first phase);
  * "hints_candidates" (the last sg_hints_replacers* call's (slot, pair)
  * matches, before deduplication); "exec_comps_general" (the calls the last
  * sg_exec_comps* call sent down its general path), "exec_comps_fast_cap"
@@ -86,8 +88,9 @@ int sg_ctx_kernel_time(sg_ctx* ctx, const char* name, double* ms, uint64_t* laun
 int sg_ctx_counter(sg_ctx* ctx, const char* name, uint64_t* out);
 /* Context options.  Every path is selected by its regime; an option only
  * forces one, for a test or a measurement, and no call reads the environment
- * (sg_ctx_create seeds "debug_part", "bucket_blocks" and "prefix_pairs" from
- * SG_DEBUG_PART / SG_BUCKET_BLOCKS / SG_PREFIX_PAIRS, for the GPU scripts).
+ * (sg_ctx_create seeds "debug_part", "bucket_blocks", "prefix_pairs" and
+ * "flag_skip" from SG_DEBUG_PART / SG_BUCKET_BLOCKS / SG_PREFIX_PAIRS /
+ * SG_FLAG_SKIP, for the GPU scripts).
  * Keys (-1 = the regime's choice where it applies):
  *   "max_launch_records"   records per partitioned launch (0: 2^24)
  *   "owner_key_space"      Minimize's first-owner key space (0: 2^32 - 1; set
@@ -110,6 +113,11 @@ int sg_ctx_counter(sg_ctx* ctx, const char* name, uint64_t* out);
  *                          part overflows; 0..2 forced)
  *   "exec_comps_path"      sg_exec_comps' path (-1 by each call's distinct records,
  *                          0 the general path for every call)
+ *   "flag_skip"            the flags path's bucket stage in two launches, the second
+ *                          skipping the flag stores of record blocks the first left
+ *                          fully queued (-1 auto: after a partitioned slice that
+ *                          queued most of its records; 1 always; 0 never)
+ *   "flag_skip_split"      k, 1..8: the first launch takes 1 / 2^k of the bucket list
  * Unknown keys and out-of-range values return SG_EINVAL. */
 int sg_ctx_set_option(sg_ctx* ctx, const char* key, int64_t value);
 int sg_ctx_get_option(sg_ctx* ctx, const char* key, int64_t* out);

@@ -922,7 +922,11 @@ struct BucketArgs {
   const uint32_t* blist_b; // non-empty buckets, in bucket order ...
   const uint4* blist_q;    // ... and their descriptors
   const uint32_t* nlist;   // device: their number
-  uint64_t* dbg;           // diagnostics (k_bucket<true>): per block {start, end, buckets, rounds, 4 phase cycle sums}
+  // the list window of a split launch (flag_skip): with A = *nlist >> win_shift,
+  // win 1 takes entries [0, A), win 2 [A, *nlist), 0 all of them
+  uint32_t win, win_shift;
+  const uint32_t* fsum;    // nullable: bit per kFsRecs records of the launch, set: every flag of the block is set already
+  uint64_t* dbg;          // diagnostics (k_bucket<true>): per block {start, end, buckets, rounds, 4 phase cycle sums}
   // candidate emission (sharded triage, sg_shard.hip; the prefix protocol's
   // begin): instead of flagging records and updating maxSignal, every
   // distinct candidate s of the batch is written once, with its first
@@ -1144,11 +1148,48 @@ __device__ __forceinline__ void bucket_pre_load(const BucketArgs& a, uint32_t b,
   }
 }
 
-// thread 0: bucket and descriptor of list entry t (kNumBuckets: past the end)
-__device__ __forceinline__ uint32_t list_bucket(const BucketArgs& a, uint32_t t, uint32_t nl, uint4* q) {
+// thread 0: bucket and descriptor of entry t of the list window [l0, l0 + nl)
+// (kNumBuckets: past the end)
+__device__ __forceinline__ uint32_t list_bucket(const BucketArgs& a, uint32_t t, uint32_t l0, uint32_t nl, uint4* q) {
   if (t >= nl) return kNumBuckets;
-  *q = a.blist_q[t];
-  return a.blist_b[t];
+  *q = a.blist_q[l0 + t];
+  return a.blist_b[l0 + t];
+}
+
+// Record-flag summary of a split launch: one bit per block of kFsRecs
+// consecutive records of the launch, set iff every existing record of the block
+// was flagged when k_flag_summary ran between the two bucket launches.
+// Nothing clears a flag within a call, so a store to such a record would
+// rewrite a 1: the second launch (kSkip) and the direct-table kernel leave it
+// out.  At the launch maximum of 2^24 records the summary is 512 B.
+constexpr uint32_t kFsBits = 12, kFsRecs = 1u << kFsBits;
+constexpr uint32_t kFsWords = (uint32_t)(kMaxLaunchRecords >> kFsBits) / 32;
+static_assert(kFsWords * 32ull * kFsRecs == kMaxLaunchRecords, "summary covers a launch's records");
+__device__ __forceinline__ bool fs_full(const uint32_t* fs, uint32_t rec) {
+  return (fs[rec >> (kFsBits + 5)] >> ((rec >> kFsBits) & 31u)) & 1u;
+}
+
+// A wave per block: lane l tests the 16 flags from 1024 j + 16 l, j < 4.
+// sum is zero on entry; *nfull counts the bits set.
+__global__ __launch_bounds__(256) void k_flag_summary(const uint8_t* __restrict__ rec_new, uint32_t nrec,
+                                                      uint32_t* __restrict__ sum, uint32_t* __restrict__ nfull) {
+  const uint32_t blk = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+  if (blk >= (nrec + kFsRecs - 1) >> kFsBits) return;  // (per wave)
+  bool full = true;
+#pragma unroll
+  for (int j = 0; j < 4; j++) {
+    const uint32_t i = blk * kFsRecs + j * 1024 + lane * 16;
+    if (i + 16 <= nrec && ((uintptr_t)(rec_new + i) & 15) == 0) {
+      const uint4 v = *reinterpret_cast<const uint4*>(rec_new + i);
+      for (uint32_t w : {v.x, v.y, v.z, v.w}) full &= ((w - 0x01010101u) & ~w & 0x80808080u) == 0;  // no zero byte
+    } else {
+      for (uint32_t k = i; k < i + 16 && k < nrec; k++) full &= rec_new[k] != 0;
+    }
+  }
+  if (__all(full) && lane == 0) {
+    atomicOr(&sum[blk >> 5], 1u << (blk & 31));
+    atomicAdd(nfull, 1u);
+  }
 }
 
 #ifndef SG_LDS_BARRIER
@@ -1221,9 +1262,12 @@ __device__ __forceinline__ void take_wait(uint32_t&) {}
 
 // kEmit: 0 flags and set updates, 1 candidate pairs (counted per owning
 // shard), 2 the ordered outputs' new-signal pairs, group-major, with the set
-// updates
-template <bool kDbg, int kEmit>
+// updates.  kSkip (kEmit 0, the second launch of a split one): the flush
+// leaves out the flag stores of record blocks whose summary bit is set.
+template <bool kDbg, int kEmit, bool kSkip = false>
 __global__ __launch_bounds__(kBThreads) __attribute__((amdgpu_waves_per_eu(kBWaves))) void k_bucket(BucketArgs a) {
+  static_assert(!kSkip || kEmit == 0, "the summary guards flag stores");
+  __shared__ uint32_t fsum[kSkip ? kFsWords : 1];
   __shared__ uint32_t mslice[kBucketWords];
   __shared__ uint32_t nbits[kBucketWords];
   __shared__ uint32_t ht[kHash];
@@ -1249,18 +1293,25 @@ __global__ __launch_bounds__(kBThreads) __attribute__((amdgpu_waves_per_eu(kBWav
   for (uint32_t i = tid; i < kHash; i += kBThreads) ht[i] = kEmpty;
   for (uint32_t i = tid; i < kBucketWords; i += kBThreads) nbits[i] = 0;
   if (tid == 0) sh_fail = 0;
+  if (kSkip)
+    for (uint32_t i = tid; i < kFsWords; i += kBThreads) fsum[i] = a.fsum[i];
   // list entries: blockIdx and gridDim + blockIdx first, then tickets from
   // 2 x gridDim.  Thread 0 takes each ticket a bucket before it resolves it and
   // resolves it a bucket before it is needed, so neither wait is exposed.
-  const uint32_t nl = *a.nlist;
+  uint32_t nl = *a.nlist, l0 = 0;
+  if (a.win) {  // a split launch's window of the list
+    const uint32_t na = nl >> a.win_shift;
+    l0 = a.win == 2 ? na : 0;
+    nl = a.win == 2 ? nl - na : na;
+  }
   // (tickets are taken at every install, also past the list's end: waiting
   // for the list entry before taking the next would be another round trip)
   uint32_t pend_t = 0;  // thread 0: ticket taken, not yet resolved
   if (tid == 0) {
     uint4 q0 = make_uint4(0, 0, 0, 0), q1 = make_uint4(0, 0, 0, 0);
-    sh_b[0] = list_bucket(a, blockIdx.x, nl, &q0);
+    sh_b[0] = list_bucket(a, blockIdx.x, l0, nl, &q0);
     sh_q[0] = q0;
-    sh_b[1] = list_bucket(a, gridDim.x + blockIdx.x, nl, &q1);
+    sh_b[1] = list_bucket(a, gridDim.x + blockIdx.x, l0, nl, &q1);
     sh_q[1] = q1;
     pend_t = take_ticket(a.ticket);
   }
@@ -1302,7 +1353,7 @@ __global__ __launch_bounds__(kBThreads) __attribute__((amdgpu_waves_per_eu(kBWav
     uint4 pend_q = make_uint4(0, 0, 0, 0);
     if (tid == 0) {
       take_wait(pend_t);  // (taken a bucket ago; the install waited for older loads already)
-      pend_b = list_bucket(a, 2 * gridDim.x + pend_t, nl, &pend_q);
+      pend_b = list_bucket(a, 2 * gridDim.x + pend_t, l0, nl, &pend_q);
       pend_t = take_ticket(a.ticket);
       if (kEmit) take_wait(pend_t);
       sh_fail = 0;  // (every wave read the previous bucket's before the barrier above)
@@ -1585,7 +1636,7 @@ __global__ __launch_bounds__(kBThreads) __attribute__((amdgpu_waves_per_eu(kBWav
           if (v != kEmpty) {
             const uint32_t sl = map_signal(i, v);
             atomicOr(&nbits[sl >> 5], 1u << (sl & 31));
-            a.rec_new[v & kRecMask] = 1;
+            if (!kSkip || !fs_full(fsum, v & kRecMask)) a.rec_new[v & kRecMask] = 1;
           }
         }
         lds_barrier();
@@ -1660,8 +1711,11 @@ __global__ __launch_bounds__(kDThreads) void k_bucket_direct(BucketArgs a) {
   __shared__ uint32_t shcnt[kEmit ? kMaxShards : 1];
   __shared__ uint32_t lcnt[kEmit ? kMaxGroups : 1];
   __shared__ unsigned long long lbase[kEmit ? kMaxGroups : 1];
+  __shared__ uint32_t fsum[kEmit ? 1 : kFsWords];  // after a split launch: its summary (else zero)
   const int tid = threadIdx.x;
   const uint32_t nsp = *a.nspill, NG = a.NG;
+  if (!kEmit)  // (the job loop's first barrier orders it)
+    for (uint32_t i = tid; i < kFsWords; i += kDThreads) fsum[i] = a.fsum ? a.fsum[i] : 0u;
   if (kEmit) {
     for (uint32_t i = tid; i < kMaxShards; i += kDThreads) shcnt[i] = 0;
     for (uint32_t i = tid; i < kMaxGroups; i += kDThreads) lcnt[i] = 0;
@@ -1708,7 +1762,7 @@ __global__ __launch_bounds__(kDThreads) void k_bucket_direct(BucketArgs a) {
       }
     } else {
       for (uint32_t i = tid; i < kQ; i += kDThreads)
-        if (owner[i] != kEmpty) a.rec_new[owner[i]] = 1;
+        if (owner[i] != kEmpty && !fs_full(fsum, owner[i])) a.rec_new[owner[i]] = 1;
       for (uint32_t i = tid; i < kQW; i += kDThreads) {
         const uint32_t nb = nbits[i];
         if (nb) {
@@ -2395,7 +2449,7 @@ struct BucketPlan {
     oO2 = p.add((256 * gmax + 1) * 4);
     oV2 = p.add(n * 4 + 64);  // the bucket kernel's 16-B loads may read past the end
     oSP = p.add(((uint64_t)kNumBuckets + 1) * 4);
-    oTK = p.add(4);
+    oTK = p.add(16 + kFsWords * 4);  // two tickets (a split launch's phases), the record-flag summary
     oBN = p.add((uint64_t)kNumBuckets * 4);
     oBP = p.add(((uint64_t)kNumBuckets + 1) * 4);
     oLB = p.add((uint64_t)kNumBuckets * 4);
@@ -2575,6 +2629,46 @@ static int partition_one(sg_ctx* ctx, const uint32_t* d_vals, const uint64_t* d_
 
 // Stage B: the bucket kernels over stage A's buckets (bp rebased by stage A):
 // flags and set updates, or (emit) the candidate pairs.
+// pinned words the regimes read without a host wait: [0] the queued records of
+// the last counted partitioned slice (behind m0f_ev), [4] a split launch's
+// full record blocks (behind fs_ev)
+static int m0f_host_alloc(sg_ctx* ctx) {
+  if (ctx->m0f_host) return SG_OK;
+  SG_HIP(hipHostMalloc((void**)&ctx->m0f_host, 64, hipHostMallocDefault));
+  SG_HIP(hipEventCreateWithFlags(&ctx->m0f_ev, hipEventDisableTiming));
+  return SG_OK;
+}
+
+// the queued fraction of the last counted partitioned slice, once its copy has landed
+static void m0f_poll(sg_ctx* ctx) {
+  if (ctx->m0f_pending && hipEventQuery(ctx->m0f_ev) == hipSuccess) {
+    ctx->m0f_pending = false;
+    ctx->m0f_queued = (double)*ctx->m0f_host / (double)(ctx->m0f_nrec ? ctx->m0f_nrec : 1);
+  }
+}
+
+// The split bucket stage's regime: option flag_skip 1 always, 0 never.  The
+// split pays when the first launch leaves nearly every record flagged, that
+// is in a batch that queues nearly all of its records (a fresh corpus: every
+// record owns ~200 new signals spread over all buckets); in a low-novelty
+// batch it only adds a launch (measured +0.05 ms on the steady batch).  A
+// block's stores are skipped only when all of its kFsRecs records are queued:
+// with a queued fraction q that is q^4096 of the blocks (0.29 at 0.9997, 0.66
+// at 0.9999), and the measured gain of 0.17 ms with every block full covers
+// the added launch from about 0.3 of them.  auto therefore splits when the
+// last counted partitioned slice of the context queued at least kFsQueued of
+// its records (the count that the M0 filter's regime reads): a fresh corpus.
+// Before the first count is read -- a context's first slice, or its count
+// still in flight -- it does not; while a later count is in flight the last
+// one read stands.
+constexpr double kFsQueued = 0.9997;
+static bool fs_split(sg_ctx* ctx) {
+  const int64_t o = ctx->opt[kOptFlagSkip];
+  if (o >= 0) return o != 0;
+  m0f_poll(ctx);
+  return ctx->m0f_queued >= kFsQueued;
+}
+
 static int buckets_one(sg_ctx* ctx, const BucketPlan& bp, uint32_t* mwords, uint32_t* nwords, uint8_t* d_rec_new,
                        const EmitArgs* emit, uint64_t n, uint64_t nrec, const uint32_t* owords = nullptr) {
   const uint32_t NG = (uint32_t)bp.NG;
@@ -2618,7 +2712,19 @@ static int buckets_one(sg_ctx* ctx, const BucketPlan& bp, uint32_t* mwords, uint
     SG_HIP(hipMalloc(&ddbg, (size_t)bgrid * 88));
     ba.dbg = ddbg;
   }
-  SG_HIP(hipMemsetAsync(ba.ticket, 0, 4, ctx->stream));
+  // The flags path in two launches (option flag_skip): the first 1 / 2^k of
+  // the bucket list with every flag stored, the record-flag summary, then the
+  // rest of the list without the stores that the summary shows to rewrite a 1.
+  const bool split = !emit && !dbg && d_rec_new && nrec <= kMaxLaunchRecords && fs_split(ctx);
+  uint32_t* fsum = ba.ticket + 4;
+  uint32_t* fcnt = (uint32_t*)ctx->dscal + 33;  // (a device scalar of the context)
+  if (split) {
+    if (!ctx->fs_ev) SG_HIP(hipEventCreateWithFlags(&ctx->fs_ev, hipEventDisableTiming));
+    int rc = m0f_host_alloc(ctx);
+    if (rc) return rc;
+    SG_HIP(hipMemsetAsync(fcnt, 0, 4, ctx->stream));
+  }
+  SG_HIP(hipMemsetAsync(ba.ticket, 0, split ? 16 + kFsWords * 4 : 4, ctx->stream));
   SG_HIP(hipMemsetAsync(nspill, 0, 4, ctx->stream));
   ba.blist_b = (const uint32_t*)ws_at(ctx, bp.oLB);
   ba.blist_q = (const uint4*)ws_at(ctx, bp.oLQ);
@@ -2631,8 +2737,25 @@ static int buckets_one(sg_ctx* ctx, const BucketPlan& bp, uint32_t* mwords, uint
       hipLaunchKernelGGL((k_bucket<false, 1>), dim3(bgrid), dim3(kBThreads), 0, ctx->stream, ba);
     else if (dbg)
       hipLaunchKernelGGL((k_bucket<true, 0>), dim3(bgrid), dim3(kBThreads), 0, ctx->stream, ba);
-    else
+    else if (!split)
       hipLaunchKernelGGL((k_bucket<false, 0>), dim3(bgrid), dim3(kBThreads), 0, ctx->stream, ba);
+    else {
+      ba.win = 1;
+      ba.win_shift = (uint32_t)ctx->opt[kOptFlagSkipSplit];
+      hipLaunchKernelGGL((k_bucket<false, 0>), dim3(bgrid), dim3(kBThreads), 0, ctx->stream, ba);
+      hipLaunchKernelGGL(k_flag_summary, dim3(div_up(div_up(nrec, kFsRecs), 4)), dim3(256), 0, ctx->stream,
+                         (const uint8_t*)d_rec_new, (uint32_t)nrec, fsum, fcnt);
+      ba.win = 2;
+      ba.ticket++;
+      ba.fsum = fsum;  // (the direct-table kernel below honours it too)
+      hipLaunchKernelGGL((k_bucket<false, 0, true>), dim3(bgrid), dim3(kBThreads), 0, ctx->stream, ba);
+    }
+  }
+  if (split) {
+    SG_HIP(hipMemcpyAsync(ctx->m0f_host + 4, fcnt, 4, hipMemcpyDeviceToHost, ctx->stream));
+    SG_HIP(hipEventRecord(ctx->fs_ev, ctx->stream));
+    ctx->fs_pending = true;
+    ctx->fs_used++;
   }
   {
     ScopedTimer tm(ctx, "bucket_spill");
@@ -2808,11 +2931,10 @@ __global__ void k_count_flags(const uint8_t* __restrict__ f, uint64_t n, uint32_
 // device and copied to pinned memory behind an event, read by a later m0f_try.
 static int m0f_note_partitioned(sg_ctx* ctx, const uint8_t* d_rec_new, uint64_t nrec) {
   ctx->m0f_last = 0;
-  if (ctx->opt[kOptM0Filter] >= 0 || ctx->m0f_pending) return SG_OK;
-  if (!ctx->m0f_host) {
-    SG_HIP(hipHostMalloc((void**)&ctx->m0f_host, 64, hipHostMallocDefault));
-    SG_HIP(hipEventCreateWithFlags(&ctx->m0f_ev, hipEventDisableTiming));
-  }
+  // (read by the auto regimes of the M0 filter and of the split bucket stage)
+  if ((ctx->opt[kOptM0Filter] >= 0 && ctx->opt[kOptFlagSkip] >= 0) || ctx->m0f_pending) return SG_OK;
+  int rc = m0f_host_alloc(ctx);
+  if (rc) return rc;
   uint32_t* dcnt = (uint32_t*)ctx->dscal + 32;  // (a device scalar of the context)
   SG_HIP(hipMemsetAsync(dcnt, 0, 4, ctx->stream));
   hipLaunchKernelGGL(k_count_flags, dim3(std::min<uint64_t>(256, div_up(nrec, 1024))), dim3(256), 0, ctx->stream,
@@ -2836,10 +2958,7 @@ constexpr double kFTryQueued = 0.25;
 static bool m0f_try(sg_ctx* ctx) {
   const int64_t o = ctx->opt[kOptM0Filter];
   if (o >= 0) return o != 0;
-  if (ctx->m0f_pending && hipEventQuery(ctx->m0f_ev) == hipSuccess) {
-    ctx->m0f_pending = false;
-    ctx->m0f_queued = (double)*ctx->m0f_host / (double)(ctx->m0f_nrec ? ctx->m0f_nrec : 1);
-  }
+  m0f_poll(ctx);
   if (ctx->m0f_skip) {  // (backing off after fallbacks)
     ctx->m0f_skip--;
     return false;

@@ -499,7 +499,12 @@ int sg_ctx_create(int device, sg_ctx** out) {
   // the diagnostics switches of the GPU scripts, read once here (every other
   // option is set by sg_ctx_set_option; nothing reads the environment later)
   c->debug_part = getenv("SG_DEBUG_PART") != nullptr;
-  if (const char* e = getenv("SG_BUCKET_BLOCKS")) c->opt[kOptBucketBlocks] = strtoll(e, nullptr, 10);
+  {
+    static const struct { const char* name; int opt; int64_t lo, hi; } kSeed[] = {
+        {"SG_BUCKET_BLOCKS", kOptBucketBlocks, INT64_MIN, INT64_MAX}, {"SG_FLAG_SKIP", kOptFlagSkip, -1, 1}};
+    for (const auto& s : kSeed)
+      if (const char* e = getenv(s.name)) c->opt[s.opt] = std::min(std::max<int64_t>(strtoll(e, nullptr, 10), s.lo), s.hi);
+  }
   if (const char* e = getenv("SG_PREFIX_PAIRS")) c->opt[kOptPrefixPairs] = strtoll(e, nullptr, 10) != 0;
   c->cpu_quota = host_cpu_quota();
   int rc = ensure_device(c);
@@ -542,6 +547,7 @@ void sg_ctx_destroy(sg_ctx* ctx) {
   if (ctx->m0f) hipFree(ctx->m0f);
   if (ctx->m0f_host) hipHostFree(ctx->m0f_host);
   if (ctx->m0f_ev) hipEventDestroy(ctx->m0f_ev);
+  if (ctx->fs_ev) hipEventDestroy(ctx->fs_ev);
   if (ctx->slice_off) hipFree(ctx->slice_off);
   if (ctx->slice_cuts) hipFree(ctx->slice_cuts);
   if (ctx->dscal) hipFree(ctx->dscal);
@@ -630,7 +636,7 @@ int sg_ctx_marker(sg_ctx* ctx, int end, uint32_t tag) {
 static const char* const kOptNames[kOptCount] = {
     "bucket_blocks",      "prefix_pairs",       "fold_map",         "minimize_filter",   "minimize_filter_ranks",
     "report_direct",      "rpc_encode_elems",   "rpc_decode_blocks", "host_slice",       "host_copy_threads",
-    "m0_filter",          "m0_filter_halves",   "exec_comps_path"};
+    "m0_filter",          "m0_filter_halves",   "exec_comps_path",  "flag_skip",         "flag_skip_split"};
 
 int sg_ctx_set_option(sg_ctx* ctx, const char* key, int64_t value) {
   if (!ctx || !key) return SG_EINVAL;
@@ -661,8 +667,8 @@ int sg_ctx_set_option(sg_ctx* ctx, const char* key, int64_t value) {
     return SG_OK;
   }
   // value ranges, in kOptNames' order (tri-state options: -1 the regime's choice)
-  static const int64_t kLo[kOptCount] = {0, 0, -1, 0, 0, 0, -1, -1, 0, 0, -1, -1, -1};
-  static const int64_t kHi[kOptCount] = {1 << 20, 1, 1, 1, 1 << 20, 1, 1, 1, 1ll << 40, 64, 1, 2, 0};
+  static const int64_t kLo[kOptCount] = {0, 0, -1, 0, 0, 0, -1, -1, 0, 0, -1, -1, -1, -1, 1};
+  static const int64_t kHi[kOptCount] = {1 << 20, 1, 1, 1, 1 << 20, 1, 1, 1, 1ll << 40, 64, 1, 2, 0, 1, 8};
   for (int i = 0; i < kOptCount; i++)
     if (!strcmp(key, kOptNames[i])) {
       if (value < kLo[i] || value > kHi[i]) {
@@ -729,7 +735,16 @@ int sg_ctx_counter(sg_ctx* ctx, const char* name, uint64_t* out) {
     *out = ctx->m0f_queued < 0 ? ~0ull : (uint64_t)(ctx->m0f_queued * 1000.0 + 0.5);
   else if (!strcmp(name, "m0_filter_halves_log"))  // the index's parts per slice (log2) the auto regime uses now
     *out = (uint64_t)ctx->m0f_logh;
-  else if (!strcmp(name, "hints_candidates"))  // the last sg_hints_replacers* call's matches (sg_hints.hip)
+  else if (!strcmp(name, "flag_skip_used"))  // bucket launches run in two phases (sg_bucket.hip)
+    *out = ctx->fs_used;
+  else if (!strcmp(name, "flag_skip_full_blocks")) {  // fully queued record blocks the last of them found after phase A
+    if (ctx->fs_pending) {
+      SG_HIP(hipEventSynchronize(ctx->fs_ev));
+      ctx->fs_pending = false;
+      ctx->fs_full_blocks = ctx->m0f_host[4];
+    }
+    *out = ctx->fs_full_blocks;
+  } else if (!strcmp(name, "hints_candidates"))  // the last sg_hints_replacers* call's matches (sg_hints.hip)
     *out = ctx->hints_cands;
   else if (!strcmp(name, "exec_comps_general"))  // the last sg_exec_comps* call's calls on the general path
     *out = ctx->exec_comps_general;

@@ -79,8 +79,9 @@ constexpr uint32_t kPrefixSlots = 2;
 // Context options (sg_ctx_set_option): each regime selects its own path, and
 // an option only forces one, for a test or a measurement.  -1 = the regime's
 // choice.  No option is read from the environment on a call; sg_ctx_create
-// seeds the diagnostics ones (debug_part, bucket_blocks, prefix_pairs) from
-// SG_DEBUG_PART / SG_BUCKET_BLOCKS / SG_PREFIX_PAIRS for the GPU scripts.
+// seeds the diagnostics ones (debug_part, bucket_blocks, prefix_pairs,
+// flag_skip) from SG_DEBUG_PART / SG_BUCKET_BLOCKS / SG_PREFIX_PAIRS /
+// SG_FLAG_SKIP for the GPU scripts.
 enum SgOpt : int {
   kOptBucketBlocks = 0,     // cap of the persistent bucket grid (0: none)
   kOptPrefixPairs,          // prefix_begin's form when the caller passes -1 (0 kept partitions, 1 pairs)
@@ -95,12 +96,15 @@ enum SgOpt : int {
   kOptM0Filter,             // flags path: the M0 filter (sg_bucket.hip): -1 by the last batches, 0 never, 1 always tried
   kOptM0Halves,             // the filter's index per slice in 2^k parts (-1 by its fill, 0..2 forced)
   kOptExecCompsPath,        // sg_exec_comps: -1 by each call's distinct records, 0 the general path for every call
+  kOptFlagSkip,             // bucket stage in two launches, the second skipping the flag stores of fully queued
+                            // record blocks (sg_bucket.hip): -1 by the last partitioned slice, 0 never, 1 always
+  kOptFlagSkipSplit,        // ... the first launch takes the first 1 / 2^k of the bucket list
   kOptCount
 };
 
 struct sg_ctx {
   int device = 0;
-  int64_t opt[kOptCount] = {0, 0, -1, 1, 0, 0, -1, -1, 0, 0, -1, -1, -1};
+  int64_t opt[kOptCount] = {0, 0, -1, 1, 0, 0, -1, -1, 0, 0, -1, -1, -1, -1, 3};
   // the M0 filter's buffers (lazy, sg_bucket.hip) and its regime state: the
   // last record slice's outcome (1 filtered, 0 partitioned), the queued
   // records of the last partitioned slice (counted on the device, read back
@@ -115,6 +119,12 @@ struct sg_ctx {
   double m0f_queued = -1;        // queued fraction of the last partitioned slice (-1 unknown)
   uint64_t m0f_used = 0, m0f_fallback = 0, m0f_survivors = 0;
   uint32_t m0f_backoff = 0, m0f_skip = 0;
+  // the split bucket stage (flag_skip): launches split, and the summary bits
+  // of the last one (counted on the device, read through m0f_host[4] once
+  // fs_ev has passed)
+  uint64_t fs_used = 0, fs_full_blocks = 0;
+  hipEvent_t fs_ev = nullptr;
+  bool fs_pending = false;
   int m0f_logh = 0;  // auto: the index in 2^m0f_logh parts per slice (raised when a slice's index overflows)  // auto: slices not to try after fallbacks (doubling, <= 64)
   // host CPUs this process may use (cgroup cpu.max quota, else the affinity
   // mask), read at creation: sizes the host ingest's copy threads
