@@ -84,7 +84,11 @@ int sg_ctx_kernel_time(sg_ctx* ctx, const char* name, double* ms, uint64_t* laun
  * "hints_candidates" (the last sg_hints_replacers* call's (slot, pair)
  * matches, before deduplication); "exec_comps_general" (the calls the last
  * sg_exec_comps* call sent down its general path), "exec_comps_fast_cap"
- * (SG_EXEC_COMPS_FAST_CAP). */
+ * (SG_EXEC_COMPS_FAST_CAP); "owned_big_records" (the records the last
+ * ordered-output call -- sg_triage_batch[_dev] with diff lists, sg_merge_poll
+ * -- swept a workgroup each instead of a wave each, summed over its record
+ * slices; counted on the device and read here after a stream sync, so the
+ * call itself gains no wait). */
 int sg_ctx_counter(sg_ctx* ctx, const char* name, uint64_t* out);
 /* Context options.  Every path is selected by its regime; an option only
  * forces one, for a test or a measurement, and no call reads the environment

@@ -78,7 +78,8 @@ class Context:
     def counter(self, name):
         """sg_ctx_counter: "owner_resets", "owner_floor", "owner_key_space", "max_launch_records",
         the host ingest's "host_copy_bytes" / "host_copy_ns" / "host_wait_ns" / "host_copy_threads",
-        "cpu_quota_milli", "hints_candidates"."""
+        "cpu_quota_milli", "hints_candidates", the last ordered-output call's "owned_big_records"
+        (include/syzsig.h lists them all)."""
         v = c_uint64()
         call("sg_ctx_counter", self.h, name.encode(), byref(v))
         return v.value

@@ -524,6 +524,15 @@ int sg_ctx_create(int device, sg_ctx** out) {
     delete c;
     return hip_fail(e, "hipMalloc(dscal)");
   }
+  e = hipMalloc(&c->own_big, 256);
+  if (e == hipSuccess) e = hipMemset(c->own_big, 0, 256);
+  if (e != hipSuccess) {
+    if (c->own_big) hipFree(c->own_big);
+    hipFree(c->dscal);
+    hipStreamDestroy(c->own_stream);
+    delete c;
+    return hip_fail(e, "hipMalloc(own_big)");
+  }
   *out = c;
   return SG_OK;
 }
@@ -551,6 +560,7 @@ void sg_ctx_destroy(sg_ctx* ctx) {
   if (ctx->slice_off) hipFree(ctx->slice_off);
   if (ctx->slice_cuts) hipFree(ctx->slice_cuts);
   if (ctx->dscal) hipFree(ctx->dscal);
+  if (ctx->own_big) hipFree(ctx->own_big);
   if (ctx->gen_prob) hipFree(ctx->gen_prob);
   if (ctx->gen_alias) hipFree(ctx->gen_alias);
   if (ctx->gen_perm) hipFree(ctx->gen_perm);
@@ -748,7 +758,12 @@ int sg_ctx_counter(sg_ctx* ctx, const char* name, uint64_t* out) {
     *out = ctx->hints_cands;
   else if (!strcmp(name, "exec_comps_general"))  // the last sg_exec_comps* call's calls on the general path
     *out = ctx->exec_comps_general;
-  else if (!strcmp(name, "exec_comps_fast_cap"))  // distinct records a call may hold on the fast shape
+  else if (!strcmp(name, "owned_big_records")) {  // the last ordered-output call's records left to k_own_big (sg_triage.hip)
+    uint32_t v = 0;
+    SG_HIP(hipStreamSynchronize(ctx->stream));
+    SG_HIP(hipMemcpy(&v, ctx->own_big, 4, hipMemcpyDeviceToHost));
+    *out = v;
+  } else if (!strcmp(name, "exec_comps_fast_cap"))  // distinct records a call may hold on the fast shape
     *out = SG_EXEC_COMPS_FAST_CAP;
   else if (!strcmp(name, "cpu_quota_milli"))
     *out = (uint64_t)(ctx->cpu_quota * 1000.0 + 0.5);

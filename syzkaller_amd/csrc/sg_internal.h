@@ -170,6 +170,10 @@ struct sg_ctx {
   uint64_t* slice_cuts = nullptr;
   // small device scalars (counters / flags)
   uint64_t* dscal = nullptr;
+  // records the last ordered-output call listed for k_own_big (sg_triage.hip):
+  // zeroed by the call, added to by each slice's launch, read by
+  // sg_ctx_counter("owned_big_records") after a stream sync
+  uint32_t* own_big = nullptr;
   // cached Zipf generator tables (alias method + rank->pc permutation)
   uint32_t* gen_prob = nullptr;
   uint32_t* gen_alias = nullptr;

@@ -89,6 +89,7 @@ struct OwnArgs {
   uint32_t* big;         // [0]: count, then the records left for k_own_big
   uint64_t n;            // elements in the batch (vals[0 .. n) readable)
   uint32_t* ticket;      // k_own_pipe's next block of 64 records (zeroed)
+  uint32_t* nbig;        // the call's records listed for k_own_big, over its slices (counter "owned_big_records")
 };
 
 // The set: 1 << bb buckets of four slots, a key in the first bucket from its
@@ -502,6 +503,7 @@ __global__ __launch_bounds__(kOwnBigT) void k_own_big(OwnArgs a) {
   constexpr int kW = kOwnBigT / 64;
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
   const uint32_t nbig = a.big[0];
+  if (blockIdx.x == 0 && tid == 0 && nbig) atomicAdd(a.nbig, nbig);  // (once per launch: a slice's share)
   for (uint32_t j = blockIdx.x; j < nbig; j += gridDim.x) {
     const uint32_t r = uni32(a.big[1 + j]);
     const uint2 q = make_uint2(uni32(a.po[r].x), uni32(a.po[r].y));
@@ -1000,6 +1002,7 @@ static int owned_outputs(sg_ctx* ctx, uint32_t* mwords, uint32_t* nwords, const 
     set_error("ordered triage: a batch holds < 2^32 signal entries and < 2^32 - 1 records");
     return SG_EINVAL;
   }
+  SG_HIP(hipMemsetAsync(ctx->own_big, 0, 4, ctx->stream));  // (read by sg_ctx_counter only: no wait here)
   if (nrec && d_rec_new) SG_HIP(hipMemsetAsync(d_rec_new, 0, nrec, ctx->stream));
   if (nvals == 0) {
     if (d_out_off) SG_HIP(hipMemsetAsync(d_out_off, 0, (nrec + 1) * 8, ctx->stream));
@@ -1086,7 +1089,7 @@ static int owned_outputs(sg_ctx* ctx, uint32_t* mwords, uint32_t* nwords, const 
     hipLaunchKernelGGL(k_own_bounds_search, dim3(div_up(nr, 256)), dim3(256), 0, ctx->stream, (const uint64_t*)sorted,
                        np, (uint32_t)nr, po);
     OwnArgs oa{d_vals, roff, e0, (uint32_t)nr, sorted, po, d_rec_new ? d_rec_new + r0 : nullptr, s.dmask, big, nvals,
-               big + nr + 1};
+               big + nr + 1, ctx->own_big};
     SG_HIP(hipMemsetAsync(big + nr + 1, 0, 4, ctx->stream));
     if (aligned)
       rc = launch_own<true>(ctx, oa, nr, dedup);
@@ -1350,13 +1353,14 @@ int sg_merge_poll(sg_ctx* ctx, sg_set* mgr_max, const uint32_t* a_vals, const ui
   if (!ctx || !mgr_max || !a_off || !new_off) return SG_EINVAL;
   uint64_t nv = a_off[npoll] - a_off[0];
   if (a_off[0] != 0 || (nv && (!a_vals || !new_vals))) return SG_EINVAL;
-  if (nv == 0) {
-    for (size_t k = 0; k <= npoll; k++) new_off[k] = 0;
-    return SG_OK;
-  }
   std::lock_guard<std::mutex> g(ctx->mu);
   int rc = check_alloc(ctx);
   if (rc) return rc;
+  if (nv == 0) {
+    SG_HIP(hipMemsetAsync(ctx->own_big, 0, 4, ctx->stream));  // (no record listed)
+    for (size_t k = 0; k <= npoll; k++) new_off[k] = 0;
+    return SG_OK;
+  }
   // the Poll loop (manager.go:949-956) is a first-owner loop over the polls
   // with mgr.maxSignal as the running set, each poll's new signals in its
   // order, once each (its first occurrence): the ordered-output path with

@@ -69,6 +69,20 @@ def triage(maxset, newset, records):
     return flags, diffs
 
 
+def merge_poll(maxset, polls):
+    """syz-manager/manager.go:949-956 with a Python set: each poll's signals
+    not yet in maxSignal, in its order, once each."""
+    news = []
+    for sig in polls:
+        new = []
+        for s in sig:
+            if s not in maxset:
+                maxset.add(s)
+                new.append(s)
+        news.append(new)
+    return news
+
+
 def minimize(corpus, order):
     """pkg/cover/cover.go:129-145 over a given order."""
     covered, out = set(), []
