@@ -489,9 +489,9 @@ int sg_triage_traces_queued(sg_ctx* ctx, sg_set* maxsig, sg_set* newsig, const u
  * word_off == NULL to skip the words.
  * This is the WRITER's layout: two operand words unless the size is 8.  The
  * reader of this reference snapshot takes two operand words when the size IS 8
- * (pkg/ipc/ipc_linux.go:272-289), and sg_ipc_comps keeps reading it that way;
- * the two are not reconciled here.  A consumer on the device takes the
- * full-width comps triples and needs no wire detour.
+ * (pkg/ipc/ipc_linux.go:272-289), and sg_ipc_comps keeps reading it that way.
+ * The device consumers of the full-width comps triples are sg_comps_pairs and
+ * sg_hints_from_kcov ("hint seeds" below).
  * Offsets are always filled; comps (capacity comps_cap, in triples) is written
  * only when comp_off[ncalls] <= comps_cap, words (capacity words_cap) only when
  * word_off[ncalls] <= words_cap (the convention of sg_ipc_comps); nrecs triples
@@ -615,6 +615,64 @@ int sg_hints_replacers(sg_ctx* ctx, const uint64_t* pair_off, const uint64_t* pa
 int sg_hints_replacers_dev(sg_ctx* ctx, const uint64_t* d_pair_off, const uint64_t* d_pairs, uint64_t nrec,
 			   const uint64_t* d_val_off, const uint64_t* d_vals, uint64_t nvals, uint64_t* d_rep_off,
 			   uint64_t* d_reps, uint64_t cap);
+
+/* ---- hint seeds: raw comparisons to replacers (syz-fuzzer/fuzzer.go:627-643) */
+/* The reader's loop body (pkg/ipc/ipc_linux.go:290-302) at full operand width
+ * over a triples CSR, the layout sg_exec_comps returns: call c's comparisons
+ * are the triples {type, arg1, arg2} comps[3 * comp_off[c] .. 3 * comp_off[c+1]),
+ * comp_off[0] == 0.  Calls are independent.  Per triple, in order: op1, op2 are
+ * arg1, arg2 sign-extended from 8, 16 or 32 bits when type & 6 is 0, 2 or 4,
+ * unchanged when it is 6 (kcov_comparison_t::write, executor/executor.h:632-645;
+ * idempotent, so a no-op on sg_exec_comps' output, and any triples are legal
+ * input); nothing when op1 == op2 (:290-293), else the pair (op2, op1) (:294)
+ * and, when type & 1 == 0, also (op1, op2) (:295-302).  A call that holds a
+ * triple with type > 7 is the reader's :266-270 error: status[c] =
+ * SG_IPC_COMPS_TYPE and an empty pair list (the reader assigns Comps after the
+ * loop, :304); every other call has SG_IPC_OK and is unaffected.
+ * status (ncalls) and pair_off (ncalls + 1) are always filled; pairs (two u64
+ * {key, value} per pair, capacity cap in pairs, as sg_ipc_comps') is written
+ * only when pair_off[ncalls] <= cap; 2 * comp_off[ncalls] pairs always suffice.
+ * SG_EINVAL: a NULL ctx, comp_off, status or pair_off; comps NULL with
+ * comparisons present; pairs NULL with cap > 0; comp_off[0] != 0 or decreasing
+ * offsets; 2^31 comparisons or more (the pairs stay below 2^32), 2^31 calls or
+ * more.  The host form stages its inputs once. */
+int sg_comps_pairs(sg_ctx* ctx, const uint64_t* comp_off, const uint64_t* comps, size_t ncalls, int32_t* status,
+		   uint64_t* pair_off, uint64_t* pairs, size_t cap);
+/* Device form (ncomps = comp_off[ncalls]): every pointer is device memory,
+ * stream-ordered, no host wait; the capacity is checked on the device.  The
+ * offsets cannot be checked: they are clamped to ncomps. */
+int sg_comps_pairs_dev(sg_ctx* ctx, const uint64_t* d_comp_off, const uint64_t* d_comps, uint64_t ncalls,
+		       uint64_t ncomps, int32_t* d_status, uint64_t* d_pair_off, uint64_t* d_pairs, uint64_t cap);
+/* A hint seed's raw KCOV_TRACE_CMP buffers and argument values to shrinkExpand's
+ * replacers in one call.  recs / call_off are sg_exec_comps', val_off / vals /
+ * rep_off / reps / cap are sg_hints_replacers' with record r being call r.  The
+ * result is, by definition, that of sg_exec_comps on the buffers, sg_comps_pairs
+ * on its triples and sg_hints_replacers on those pairs and the values; status
+ * (ncalls) is sg_comps_pairs': a call with SG_IPC_COMPS_TYPE has an empty
+ * CompMap, so all its slots get empty lists.  The triples and the pairs stay in
+ * device memory; no triples and no words are written at all.  Option
+ * "exec_comps_path" applies as in sg_exec_comps; the counters
+ * "exec_comps_general" and "hints_candidates" report this call's stages.
+ * SG_EINVAL: what the three stages reject (a NULL ctx, call_off, val_off, status
+ * or rep_off; recs / vals NULL with records / values present; reps NULL with
+ * cap > 0; offsets that do not start at 0 or decrease; 2^31 calls or 2^32 value
+ * slots or (slot, pair) matches or more), and 2^31 records or more: a call keeps
+ * at most its records, and the pairs of 2^31 comparisons could reach 2^32.
+ * The host form copies the buffers, offsets and values in once, reads the
+ * status and the offsets back, then the replacers when they fit. */
+int sg_hints_from_kcov(sg_ctx* ctx, const uint64_t* recs, const uint64_t* call_off, size_t ncalls,
+		       const uint64_t* val_off, const uint64_t* vals, int32_t* status, uint64_t* rep_off, uint64_t* reps,
+		       size_t cap);
+/* Device form (nrecs = call_off[ncalls], nvals = val_off[ncalls]): every pointer
+ * is device memory, stream-ordered but for the two small device-to-host reads
+ * its stages already have: sg_exec_comps_dev's 16 bytes when the batch holds
+ * more than SG_EXEC_COMPS_FAST_CAP records (none with "exec_comps_path" = 0),
+ * and sg_hints_replacers_dev's match count (about 1 KiB).  Its intermediates
+ * (2 * nrecs pairs, two offsets per call) live in the context's grow-only
+ * device staging buffer, which waits for the stream only when it has to grow. */
+int sg_hints_from_kcov_dev(sg_ctx* ctx, const uint64_t* d_recs, const uint64_t* d_call_off, uint64_t ncalls,
+			   uint64_t nrecs, const uint64_t* d_val_off, const uint64_t* d_vals, uint64_t nvals,
+			   int32_t* d_status, uint64_t* d_rep_off, uint64_t* d_reps, uint64_t cap);
 
 #ifdef __cplusplus
 }

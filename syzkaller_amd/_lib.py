@@ -126,6 +126,12 @@ SIGNATURES = {
     "sg_hints_replacers": (c_int, [c_void_p, P64, P64, c_size_t, P64, P64, P64, P64, c_size_t]),
     "sg_hints_replacers_dev": (c_int, [c_void_p, c_void_p, c_void_p, c_uint64, c_void_p, c_void_p, c_uint64, c_void_p,
                                        c_void_p, c_uint64]),
+    "sg_comps_pairs": (c_int, [c_void_p, P64, P64, c_size_t, POINTER(c_int32), P64, P64, c_size_t]),
+    "sg_comps_pairs_dev": (c_int, [c_void_p, c_void_p, c_void_p, c_uint64, c_uint64, c_void_p, c_void_p, c_void_p,
+                                   c_uint64]),
+    "sg_hints_from_kcov": (c_int, [c_void_p, P64, P64, c_size_t, P64, P64, POINTER(c_int32), P64, P64, c_size_t]),
+    "sg_hints_from_kcov_dev": (c_int, [c_void_p, c_void_p, c_void_p, c_uint64, c_uint64, c_void_p, c_void_p, c_uint64,
+                                       c_void_p, c_void_p, c_void_p, c_uint64]),
 }
 
 

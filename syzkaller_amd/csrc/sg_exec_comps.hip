@@ -37,7 +37,9 @@
 // reference) and writes triples and words at those offsets.  The words are the
 // WRITER's layout (two operand words unless the size is 8, :646-656); the
 // reader of this snapshot takes the opposite widths (ipc_linux.go:272-289) and
-// sg_ipc_comps keeps reading those: the two are not reconciled.
+// sg_ipc_comps keeps reading those: the two are not reconciled.  The device
+// consumer of the triples is sg_hint_seed.hip; its fused call takes the raw
+// workspace keys (exec_comps with `raw`) and skips k_ec_emit.
 // Every loop is bounded by a count known on entry (records of the call, table
 // entries, sort size, 64 search steps).
 #include "sg_internal.h"
@@ -499,11 +501,12 @@ static int ec_general(sg_ctx* ctx, const EcArgs& a, uint64_t ng, size_t base) {
   return SG_OK;
 }
 
-// sg_exec_comps_dev's body; ctx lock held, the device ensured
-static int exec_comps(sg_ctx* ctx, const uint64_t* d_recs, const uint64_t* d_call_off, uint64_t ncalls, uint64_t nrecs,
-                      uint64_t* d_comp_off, uint64_t* d_comps, uint64_t comps_cap, uint64_t* d_word_off,
-                      uint32_t* d_words, uint64_t words_cap) {
+// sg_exec_comps_dev's body; ctx lock held, the device ensured (sg_internal.h)
+int exec_comps(sg_ctx* ctx, const uint64_t* d_recs, const uint64_t* d_call_off, uint64_t ncalls, uint64_t nrecs,
+               uint64_t* d_comp_off, uint64_t* d_comps, uint64_t comps_cap, uint64_t* d_word_off, uint32_t* d_words,
+               uint64_t words_cap, EcRaw* raw) {
   ctx->exec_comps_general = 0;
+  if (raw) *raw = EcRaw{};
   if (ncalls == 0 || nrecs == 0) {
     SG_HIP(hipMemsetAsync(d_comp_off, 0, (ncalls + 1) * 8, ctx->stream));
     if (d_word_off) SG_HIP(hipMemsetAsync(d_word_off, 0, (ncalls + 1) * 8, ctx->stream));
@@ -589,6 +592,12 @@ static int exec_comps(sg_ctx* ctx, const uint64_t* d_recs, const uint64_t* d_cal
     rc = scan_counts(ctx, a.wcnt, d_word_off, ncalls, scan_a);
     if (rc) return rc;
   }
+  if (raw) {  // the caller reads the workspace keys itself; the word counts and the scan's workspace are done with
+    raw->tmp = a.tmp;
+    raw->cnt = a.wcnt;
+    raw->scan_off = scan_a;
+    return SG_OK;
+  }
   if (d_comps || (d_word_off && d_words)) {
     ScopedTimer tm(ctx, "exec_comps_emit");
     hipLaunchKernelGGL(k_ec_emit, dim3(div_up(ncalls, 4)), dim3(256), 0, ctx->stream, d_call_off, ncalls, nrecs,
@@ -599,7 +608,7 @@ static int exec_comps(sg_ctx* ctx, const uint64_t* d_recs, const uint64_t* d_cal
   return SG_OK;
 }
 
-static int ec_limits(uint64_t ncalls, uint64_t nrecs) {
+int ec_limits(uint64_t ncalls, uint64_t nrecs) {
   if (nrecs >= (1ull << 32) || ncalls >= (1ull << 31)) {
     set_error("sg_exec_comps: %llu records, %llu calls (the limits are 2^32 - 1 and 2^31 - 1)",
               (unsigned long long)nrecs, (unsigned long long)ncalls);

@@ -558,12 +558,13 @@ static uint64_t bits_below(uint64_t n) {  // a mask covering 0 .. n - 1
   return n > 1 ? m : 0;
 }
 
-// The join and the sorts behind sg_hints_replacers*; ctx lock held.  With
-// reps_in_ws the replacers go to a workspace buffer of min(cap, candidates)
-// slots (*ws_reps), for the host form to copy out.
-static int hints_replacers(sg_ctx* ctx, const uint64_t* d_pair_off, const uint64_t* d_pairs, uint64_t nrec,
-                           const uint64_t* d_val_off, const uint64_t* d_vals, uint64_t nvals, uint64_t* d_rep_off,
-                           uint64_t* d_reps, uint64_t cap, bool reps_in_ws, uint64_t** ws_reps) {
+// The join and the sorts behind sg_hints_replacers* and sg_hints_from_kcov*
+// (sg_internal.h); ctx lock held.  With reps_in_ws the replacers go to a
+// workspace buffer of min(cap, candidates) slots (*ws_reps), for the host form
+// to copy out.
+int hints_replacers(sg_ctx* ctx, const uint64_t* d_pair_off, const uint64_t* d_pairs, uint64_t nrec,
+                    const uint64_t* d_val_off, const uint64_t* d_vals, uint64_t nvals, uint64_t* d_rep_off,
+                    uint64_t* d_reps, uint64_t cap, bool reps_in_ws, uint64_t** ws_reps) {
   if (ws_reps) *ws_reps = nullptr;
   ctx->hints_cands = 0;
   if (nvals >= (1ull << 32)) {

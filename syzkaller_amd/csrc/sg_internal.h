@@ -312,6 +312,29 @@ int radix_pass_runs(sg_ctx* ctx, const uint64_t* src, const std::vector<uint64_t
                     const std::vector<uint64_t>& run_cnt, uint32_t shift, uint64_t* dst, size_t ws_used);
 size_t radix_pass_runs_ws(uint64_t n, uint64_t nruns);
 
+// sg_exec_comps_dev's body (sg_exec_comps.hip; ctx lock held, the device
+// ensured).  With `raw` it stops before k_ec_emit: d_comp_off is filled, no
+// triples and no words are written, and raw tells where the workspace holds
+// the calls' sorted distinct keys, raw (call c's at tmp + 3 * call_off[c],
+// comp_off[c + 1] - comp_off[c] of them), until the next ws_reserve.  tmp is
+// null when the batch has no calls or no records (nothing was reserved).
+struct EcRaw {
+  const uint64_t* tmp = nullptr;
+  uint32_t* cnt = nullptr;  // [ncalls] scratch of the same reservation, free for the caller
+  size_t scan_off = 0;      // scan_counts' workspace for ncalls counts, likewise
+};
+int exec_comps(sg_ctx* ctx, const uint64_t* d_recs, const uint64_t* d_call_off, uint64_t ncalls, uint64_t nrecs,
+               uint64_t* d_comp_off, uint64_t* d_comps, uint64_t comps_cap, uint64_t* d_word_off, uint32_t* d_words,
+               uint64_t words_cap, EcRaw* raw = nullptr);
+int ec_limits(uint64_t ncalls, uint64_t nrecs);
+// The join and the sorts behind sg_hints_replacers* (sg_hints.hip; ctx lock
+// held).  Plans the context workspace from offset 0 and may move it.  With
+// reps_in_ws the replacers go to a workspace buffer of min(cap, candidates)
+// slots (*ws_reps), for a host form to copy out.
+int hints_replacers(sg_ctx* ctx, const uint64_t* d_pair_off, const uint64_t* d_pairs, uint64_t nrec,
+                    const uint64_t* d_val_off, const uint64_t* d_vals, uint64_t nvals, uint64_t* d_rep_off,
+                    uint64_t* d_reps, uint64_t cap, bool reps_in_ws, uint64_t** ws_reps);
+
 }  // namespace sg
 
 // ---- device helpers -------------------------------------------------------

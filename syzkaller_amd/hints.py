@@ -3,6 +3,9 @@ KCOV_TRACE_CMP buffers (executor/executor.h:379-387), the executor's
 comparisons into per-call CompMaps (pkg/ipc/ipc_linux.go:257-304) and the
 matching of argument values against them (prog/hints.go:95-177), over batches.
 
+comps_pairs joins the two ends at full operand width, and hints_from_kcov /
+HintSeed run all three stages in one call for a hint seed's raw buffers.
+
 A CompMap travels as the reader's AddComp sequence: an array of {key, value}
 pairs with one offset per call.  Cloning the program, replaceArg and validate
 stay with the caller; what comes back is, per argument value, the replacers
@@ -92,6 +95,93 @@ def shrink_expand_batch(pairs, pair_off, vals, val_off, ctx=None, cap=None):
             break
         cap = int(ro[-1])
     return reps[: int(ro[-1])], ro
+
+
+def _pi32(a):
+    return a.ctypes.data_as(ctypes.POINTER(ctypes.c_int32))
+
+
+def comps_pairs(comp_off, comps, ctx=None):
+    """The reader's loop body (ipc_linux.go:290-302) at full operand width over
+    the triples exec_comps returns.  Returns (status int32[ncalls], pairs
+    u64[n, 2], pair_off u64[ncalls + 1]): call c's AddComp(key, value) calls, in
+    the reader's order, are pairs[pair_off[c]:pair_off[c + 1]]; a call holding
+    a type above 7 has status SG_IPC_COMPS_TYPE and no pairs."""
+    co, c = _u64(comp_off), _u64(comps)
+    ncalls = co.size - 1
+    ncomps = int(co[-1])
+    assert c.size == 3 * ncomps
+    status = np.empty(max(ncalls, 1), dtype=np.int32)
+    po = np.empty(ncalls + 1, dtype=U64)
+    cap = 2 * ncomps  # a comparison yields at most 2 pairs
+    pairs = np.empty((max(cap, 1), 2), dtype=U64)
+    call("sg_comps_pairs", _ctx(ctx).h, _p64(co), _p64(c), ncalls, _pi32(status), _p64(po), _p64(pairs), cap)
+    return status[:ncalls], pairs[: int(po[-1])], po
+
+
+def hints_from_kcov(recs, call_off, vals, val_off, ctx=None, cap=None):
+    """Raw KCOV_TRACE_CMP buffers and argument values to replacers in one call:
+    exec_comps, comps_pairs and shrink_expand_batch with call c as record c,
+    the triples and pairs staying on the device.  Returns (status int32[ncalls],
+    reps, rep_off): value slot i's distinct replacers, ascending, are
+    reps[rep_off[i]:rep_off[i + 1]]; a call whose status is SG_IPC_COMPS_TYPE
+    has an empty CompMap."""
+    r, co, v, vo = _u64(recs), _u64(call_off), _u64(vals), _u64(val_off)
+    ncalls = co.size - 1
+    assert vo.size == ncalls + 1 and r.size == 4 * int(co[-1]) and v.size == int(vo[-1])
+    status = np.empty(max(ncalls, 1), dtype=np.int32)
+    ro = np.empty(v.size + 1, dtype=U64)
+    cap = max(1024, 4 * v.size) if cap is None else int(cap)
+    for _ in range(2):  # a second call when the first capacity was short
+        reps = np.empty(max(cap, 1), dtype=U64)
+        call("sg_hints_from_kcov", _ctx(ctx).h, _p64(r), _p64(co), ncalls, _p64(vo), _p64(v), _pi32(status), _p64(ro),
+             _p64(reps), cap)
+        if int(ro[-1]) <= cap:
+            break
+        cap = int(ro[-1])
+    return status[:ncalls], reps[: int(ro[-1])], ro
+
+
+def HintSeed(calls, ctx=None):
+    """The data half of MutateWithHints (prog/hints.go:50-59) for one hint seed
+    (syz-fuzzer/fuzzer.go:627-643).  calls: one (recs u64[n, 4], args) per call,
+    the call's raw KCOV_TRACE_CMP records and its arguments, each an int (a
+    ConstArg.Val) or bytes (the Data of a DirIn / DirInOut DataArg).  One
+    hints_from_kcov call.  Returns per call a list with, per argument, the set
+    of replacer ints (checkConstArg) or of mutated data strings (checkDataArg)."""
+    recs, call_off, vals, val_off = [], [0], [], [0]
+    for r, args in calls:
+        r = _u64(r)
+        assert r.size % 4 == 0
+        recs.append(r)
+        call_off.append(call_off[-1] + r.size // 4)
+        for a in args:
+            if isinstance(a, (bytes, bytearray, memoryview)):
+                data = bytes(a)
+                vals += [slice_to_uint64(data[i:]) for i in range(min(len(data), MAX_DATA_LENGTH))]
+            else:
+                vals.append(int(a))
+        val_off.append(len(vals))
+    recs = np.concatenate(recs) if recs else np.zeros(0, dtype=U64)
+    _, reps, ro = hints_from_kcov(recs, call_off, np.array(vals, dtype=U64), val_off, ctx=ctx)
+    res, slot = [], 0
+    for _, args in calls:
+        out = []
+        for a in args:
+            if isinstance(a, (bytes, bytearray, memoryview)):
+                data = bytes(a)
+                got = set()
+                for i in range(min(len(data), MAX_DATA_LENGTH)):
+                    k = min(8, len(data) - i)
+                    for rep in reps[int(ro[slot]):int(ro[slot + 1])].tolist():
+                        got.add(data[:i] + rep.to_bytes(8, "little")[:k] + data[i + k:])
+                    slot += 1
+            else:
+                got = set(reps[int(ro[slot]):int(ro[slot + 1])].tolist())
+                slot += 1
+            out.append(got)
+        res.append(out)
+    return res
 
 
 def _pairs_of(compmap):
