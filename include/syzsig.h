@@ -88,7 +88,23 @@ int sg_ctx_kernel_time(sg_ctx* ctx, const char* name, double* ms, uint64_t* laun
  * ordered-output call -- sg_triage_batch[_dev] with diff lists, sg_merge_poll
  * -- swept a workgroup each instead of a wave each, summed over its record
  * slices; counted on the device and read here after a stream sync, so the
- * call itself gains no wait). */
+ * call itself gains no wait); the paths of the last merge (sg_merge,
+ * sg_merge_batch, and the merges inside sg_union_fold), in pairs, summing to
+ * the batch: "merge_pairs_generic" (keep masks, scan and scatter: the whole
+ * batch as soon as one pair has no side of <= 4096 values -- for Difference /
+ * Intersection, a first list above 4096 -- or holds 2^32 values or more),
+ * "merge_pairs_diff_small" (Difference / Intersection, a workgroup per pair),
+ * "merge_pairs_gap" and "merge_pairs_tile" (Union / SymmetricDifference, a
+ * workgroup per pair: the large side at least 32x the small one, and the
+ * rest); the paths of the last Canonicalize (sg_canonicalize[_batch], and the
+ * one inside sg_triage_newsig): "canon_wave_lists" and "canon_block_lists"
+ * (non-empty lists of <= 1024 and of 1025..4096 values when no list is
+ * longer: sort and unique in one pass), "canon_big_segments" (lists above
+ * 4096; non-zero: the whole batch took the tile sort, the rank-merge passes
+ * and the separate unique pass, and the two list counts are 0),
+ * "canon_merge_passes" (its rank-merge launches).  These eight are host
+ * arithmetic over the call's lengths; a call that ends before any device work
+ * (no pairs, two empty lists, no values) leaves them unchanged. */
 int sg_ctx_counter(sg_ctx* ctx, const char* name, uint64_t* out);
 /* Context options.  Every path is selected by its regime; an option only
  * forces one, for a test or a measurement, and no call reads the environment

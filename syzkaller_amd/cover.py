@@ -78,7 +78,10 @@ class Context:
     def counter(self, name):
         """sg_ctx_counter: "owner_resets", "owner_floor", "owner_key_space", "max_launch_records",
         the host ingest's "host_copy_bytes" / "host_copy_ns" / "host_wait_ns" / "host_copy_threads",
-        "cpu_quota_milli", "hints_candidates", the last ordered-output call's "owned_big_records"
+        "cpu_quota_milli", "hints_candidates", the last ordered-output call's "owned_big_records",
+        the last merge's pairs per path "merge_pairs_generic" / "merge_pairs_diff_small" /
+        "merge_pairs_gap" / "merge_pairs_tile", the last Canonicalize's "canon_wave_lists" /
+        "canon_block_lists" / "canon_big_segments" / "canon_merge_passes"
         (include/syzsig.h lists them all)."""
         v = c_uint64()
         call("sg_ctx_counter", self.h, name.encode(), byref(v))

@@ -758,6 +758,22 @@ int sg_ctx_counter(sg_ctx* ctx, const char* name, uint64_t* out) {
     *out = ctx->hints_cands;
   else if (!strcmp(name, "exec_comps_general"))  // the last sg_exec_comps* call's calls on the general path
     *out = ctx->exec_comps_general;
+  else if (!strcmp(name, "merge_pairs_generic"))  // the last merge_dev call's pairs per path (sg_merge.hip)
+    *out = ctx->merge_pairs[0];
+  else if (!strcmp(name, "merge_pairs_diff_small"))
+    *out = ctx->merge_pairs[1];
+  else if (!strcmp(name, "merge_pairs_gap"))
+    *out = ctx->merge_pairs[2];
+  else if (!strcmp(name, "merge_pairs_tile"))
+    *out = ctx->merge_pairs[3];
+  else if (!strcmp(name, "canon_wave_lists"))  // the last canonicalize_dev call's segments per path
+    *out = ctx->canon_stats[0];
+  else if (!strcmp(name, "canon_block_lists"))
+    *out = ctx->canon_stats[1];
+  else if (!strcmp(name, "canon_big_segments"))
+    *out = ctx->canon_stats[2];
+  else if (!strcmp(name, "canon_merge_passes"))  // ... and its rank-merge launches
+    *out = ctx->canon_stats[3];
   else if (!strcmp(name, "owned_big_records")) {  // the last ordered-output call's records left to k_own_big (sg_triage.hip)
     uint32_t v = 0;
     SG_HIP(hipStreamSynchronize(ctx->stream));

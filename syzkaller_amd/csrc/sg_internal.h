@@ -137,6 +137,12 @@ struct sg_ctx {
   uint64_t hints_cands = 0;
   // the calls the last sg_exec_comps* call sent down the general path (sg_exec_comps.hip)
   uint64_t exec_comps_general = 0;
+  // the last merge_dev call's pairs per path (generic, k_diff_small, and
+  // k_merge_small's gap / tile forms) and the last canonicalize_dev call's
+  // segments per path (a wave each, a workgroup each, the big path) with its
+  // rank-merge passes (sg_merge.hip): host arithmetic over the lengths
+  uint64_t merge_pairs[4] = {0, 0, 0, 0};
+  uint64_t canon_stats[4] = {0, 0, 0, 0};
   hipStream_t own_stream = nullptr;
   hipStream_t stream = nullptr;
   // grow-only device workspace and pinned host staging

@@ -173,6 +173,9 @@ constexpr int kMS = 4096;               // max small side
 // least this many times the small one (long gaps); dense interleavings (the
 // corpus folds of similar-sized lists) merge tile by tile.
 constexpr uint64_t kGapRatio = 32;
+// the one statement of that test: k_merge_small's two instantiations split a
+// batch's pairs by it, and merge_dev counts them by it (ns <= kMS)
+__host__ __device__ __forceinline__ bool merge_gap_pair(uint64_t ns, uint64_t nl) { return nl >= kGapRatio * ns; }
 constexpr int kMT = 1024;               // threads
 constexpr int kMU = kMS / kMT;          // small elements per thread (consecutive)
 #ifndef SG_KML
@@ -375,7 +378,7 @@ __global__ __launch_bounds__(kMT) __attribute__((amdgpu_waves_per_eu(8, 8))) voi
   __syncthreads();
   // S: keep flags (copy t against the count in L) and insertion points in L
   uint32_t flags = 0;
-  if ((nl >= kGapRatio * ns) != kGap) return;  // the other instantiation's pair
+  if (merge_gap_pair(ns, nl) != kGap) return;  // the other instantiation's pair
   constexpr bool gap = kGap;
   // gap path: L copies of a value S also holds are dropped up to S's count (the keep
   // rule for L's side: Union when L is cov1, SymmetricDifference)
@@ -1139,8 +1142,14 @@ int canonicalize_dev(sg_ctx* ctx, uint32_t* d_vals, const uint64_t* off, uint64_
       parity[k] = passes & 1;
     }
   }
-  if (big.empty() && nseg <= 0xFFFFFFFFull)  // every segment fits one tile: sort and unique in one pass
+  // the paths taken (sg_ctx_counter "canon_*"): lists a wave each, a workgroup
+  // each, big segments, rank-merge passes
+  ctx->canon_stats[0] = ctx->canon_stats[1] = ctx->canon_stats[2] = ctx->canon_stats[3] = 0;
+  if (big.empty() && nseg <= 0xFFFFFFFFull) {  // every segment fits one tile: sort and unique in one pass
+    for (const SortChunk& c : chunks) ctx->canon_stats[c.len <= kWaveList ? 0 : 1]++;
     return canonicalize_small(ctx, d_vals, off, nseg, chunks, out_len);
+  }
+  ctx->canon_stats[2] = big.size();
   std::sort(big.begin(), big.end(), [](const BigSeg& x, const BigSeg& y) { return x.len > y.len; });
   std::vector<uint64_t> vs(big.size() + 1, 0);
   for (size_t i = 0; i < big.size(); i++) vs[i + 1] = vs[i] + big[i].len;
@@ -1185,6 +1194,7 @@ int canonicalize_dev(sg_ctx* ctx, uint32_t* d_vals, const uint64_t* off, uint64_
       hipLaunchKernelGGL(k_merge_pass, dim3((uint32_t)std::min<uint64_t>(div_up(nel, 256), 16384)), dim3(256), 0,
                          ctx->stream, bufs[pass & 1], bufs[(pass + 1) & 1], dbig, dvs, nact, w);
     }
+    ctx->canon_stats[3] = (uint64_t)pass;
   }
   CanonArgs a{};
   a.buf[0] = b0;
@@ -1238,6 +1248,18 @@ int merge_dev(sg_ctx* ctx, int op, const uint32_t* da, const uint32_t* db, uint3
   for (size_t k = 0; k < npair && small; k++) small = std::min(a_len[k], b_len[k]) <= (uint64_t)kMS;
   bool asmall = !bside;  // Difference / Intersection, every first list fits in LDS
   for (size_t k = 0; k < npair && asmall; k++) asmall = a_len[k] <= (uint64_t)kMS;
+  // the small kernels keep insertion points, ranks and output indices in 32
+  // bits: a pair of 2^32 or more values sends the batch down the generic path
+  for (size_t k = 0; k < npair && (small || asmall); k++)
+    if (a_len[k] + b_len[k] > 0xFFFFFFFFull) small = asmall = false;
+  // the paths taken (sg_ctx_counter "merge_pairs_*"): generic, k_diff_small, gap, tile
+  uint64_t ngap = 0;
+  for (size_t k = 0; k < npair && small; k++)
+    ngap += merge_gap_pair(std::min(a_len[k], b_len[k]), std::max(a_len[k], b_len[k])) ? 1 : 0;
+  ctx->merge_pairs[0] = asmall || small ? 0 : npair;
+  ctx->merge_pairs[1] = asmall ? npair : 0;
+  ctx->merge_pairs[2] = small ? ngap : 0;
+  ctx->merge_pairs[3] = small ? npair - ngap : 0;
   uint64_t na = aoff[npair], nb = bside ? boff[npair] : 0;
   uint64_t nca = ((na + kTile - 1) / kTile) * kChunksPerTile, ncb = ((nb + kTile - 1) / kTile) * kChunksPerTile;
   WsPlan p;

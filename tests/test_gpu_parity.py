@@ -128,8 +128,11 @@ def test_merge_batch_small_side_multisets(C):
     """The one-small-side merge (sg_merge.hip k_merge_small): pairs whose
     small list fits in LDS against large lists with long runs of one value
     (across its 4096-element tiles), sentinels on both sides, either side
-    small, and a mix with a pair too large for it (generic path); then
-    Difference / Intersection with every first list small (k_diff_small)."""
+    small; then Difference / Intersection with every first list small
+    (k_diff_small).  Every small side has at most 4096 values, so no batch
+    here takes the generic path, except Difference / Intersection over the
+    pairs whose first list is the large one (tests/test_merge_edges.py pins
+    the routing and the generic path with many pairs)."""
     rng = np.random.default_rng(115)
     lists = []
     for it in range(24):
