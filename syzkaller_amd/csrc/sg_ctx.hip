@@ -735,7 +735,7 @@ int sg_ctx_counter(sg_ctx* ctx, const char* name, uint64_t* out) {
     *out = ctx->host_wait_ns;
   else if (!strcmp(name, "host_copy_threads"))
     *out = ctx->host_threads;
-  else if (!strcmp(name, "m0_filter_used"))  // record slices the M0 filter finished (sg_bucket.hip)
+  else if (!strcmp(name, "m0_filter_used"))  // record slices the M0 filter finished (sg_m0filter.hip)
     *out = ctx->m0f_used;
   else if (!strcmp(name, "m0_filter_fallback"))  // ... and those whose survivors overflowed (the partition went on)
     *out = ctx->m0f_fallback;

@@ -22,7 +22,7 @@ constexpr uint64_t kSetBytes = kSetWords * 4;
 constexpr uint64_t kOwnerEntries = 1ull << 32;
 constexpr uint32_t kOwnerInf = 0xFFFFFFFFu;
 // Records per launch of the partitioned triage (256 groups of 2^16 records);
-// larger batches run as consecutive record slices (sg_bucket.hip).
+// larger batches run as consecutive record slices (sg_part_triage.hip).
 constexpr uint64_t kMaxLaunchRecords = 1ull << 24;
 
 // Element tiles of the streaming kernels: 256 threads, one uint4 (4 values)
@@ -93,7 +93,7 @@ enum SgOpt : int {
   kOptRpcDecodeBlocks,      // delta decode: -1 by shape, 0 per-list, 1 per-block
   kOptHostSlice,            // host ingest: entries per record slice (0: the default)
   kOptHostCopyThreads,      // host ingest: pageable -> pinned copy threads (0: from the CPU quota)
-  kOptM0Filter,             // flags path: the M0 filter (sg_bucket.hip): -1 by the last batches, 0 never, 1 always tried
+  kOptM0Filter,             // flags path: the M0 filter (sg_m0filter.hip): -1 by the last batches, 0 never, 1 always tried
   kOptM0Halves,             // the filter's index per slice in 2^k parts (-1 by its fill, 0..2 forced)
   kOptExecCompsPath,        // sg_exec_comps: -1 by each call's distinct records, 0 the general path for every call
   kOptFlagSkip,             // bucket stage in two launches, the second skipping the flag stores of fully queued
@@ -105,7 +105,7 @@ enum SgOpt : int {
 struct sg_ctx {
   int device = 0;
   int64_t opt[kOptCount] = {0, 0, -1, 1, 0, 0, -1, -1, 0, 0, -1, -1, -1, -1, 3};
-  // the M0 filter's buffers (lazy, sg_bucket.hip) and its regime state: the
+  // the M0 filter's buffers (lazy, sg_m0filter.hip) and its regime state: the
   // last record slice's outcome (1 filtered, 0 partitioned), the queued
   // records of the last partitioned slice (counted on the device, read back
   // through m0f_host once m0f_ev has passed: no host wait) and its record
@@ -118,14 +118,14 @@ struct sg_ctx {
   uint64_t m0f_nrec = 0;
   double m0f_queued = -1;        // queued fraction of the last partitioned slice (-1 unknown)
   uint64_t m0f_used = 0, m0f_fallback = 0, m0f_survivors = 0;
-  uint32_t m0f_backoff = 0, m0f_skip = 0;
+  uint32_t m0f_backoff = 0, m0f_skip = 0;  // auto: slices not to try after fallbacks (doubling, <= 64)
   // the split bucket stage (flag_skip): launches split, and the summary bits
   // of the last one (counted on the device, read through m0f_host[4] once
   // fs_ev has passed)
   uint64_t fs_used = 0, fs_full_blocks = 0;
   hipEvent_t fs_ev = nullptr;
   bool fs_pending = false;
-  int m0f_logh = 0;  // auto: the index in 2^m0f_logh parts per slice (raised when a slice's index overflows)  // auto: slices not to try after fallbacks (doubling, <= 64)
+  int m0f_logh = 0;  // auto: the index in 2^m0f_logh parts per slice (raised when a slice's index overflows)
   // host CPUs this process may use (cgroup cpu.max quota, else the affinity
   // mask), read at creation: sizes the host ingest's copy threads
   double cpu_quota = 0;
@@ -166,13 +166,13 @@ struct sg_ctx {
   // partitioned triage: records per launch (option max_launch_records lowers
   // it, for tests of the record slicing) and diagnostics (option debug_part)
   uint64_t max_launch_recs = 0;
-  // two-phase triage state (prefix_begin / prefix_end, sg_bucket.hip)
+  // two-phase triage state (prefix_begin / prefix_end, sg_prefix.hip)
   PrefixSlot prefix[kPrefixSlots];
   bool debug_part = false;
   // rebased record offsets of record slices (grow-only, owned)
   uint64_t* slice_off = nullptr;
   size_t slice_off_cap = 0;
-  // a batch's record-slice cuts, found on the device (sg_bucket.hip k_slice_cuts)
+  // a batch's record-slice cuts, found on the device (sg_part_triage.hip k_slice_cuts)
   uint64_t* slice_cuts = nullptr;
   // small device scalars (counters / flags)
   uint64_t* dscal = nullptr;
@@ -241,7 +241,7 @@ struct ScopedTimer {
 inline uint32_t div_up(uint64_t a, uint64_t b) { return (uint32_t)((a + b - 1) / b); }
 
 // Device exclusive scan of u32 counts into u64 offsets, out[n] = total
-// (sg_scan.hip).  Uses the workspace tail beyond `ws_used`.
+// (sg_ctx.hip).  Uses the workspace tail beyond `ws_used`.
 int scan_counts(sg_ctx* ctx, const uint32_t* d_in, uint64_t* d_out, uint64_t n, size_t ws_used);
 size_t scan_ws_bytes(uint64_t n);
 
@@ -257,7 +257,7 @@ double host_cpu_quota();
 int host_copy_threads(const sg_ctx* ctx);
 int host_pipeline(sg_ctx* ctx, uint32_t* mwords, uint32_t* nwords, const uint32_t* vals, const uint64_t* rec_off,
                   uint64_t nrec, uint8_t* rec_new, bool trace);
-// Partitioned flags-only triage (sg_bucket.hip); ctx lock held.  trace:
+// Partitioned flags-only triage (sg_part_triage.hip); ctx lock held.  trace:
 // d_vals are raw per-call PC traces, triaged by their edge signal.
 int bucket_triage(sg_ctx* ctx, uint32_t* mwords, uint32_t* nwords, const uint32_t* d_vals, const uint64_t* d_off,
                   uint64_t n, uint64_t nrec, uint8_t* d_rec_new, bool trace = false);
@@ -283,9 +283,9 @@ int rebase_offsets(sg_ctx* ctx, const uint64_t* d_off, uint64_t n, uint64_t base
 size_t bucket_plan_bytes(uint64_t n, uint64_t nrec);
 // A batch's record slices (<= max_launch_recs records, <= lim entries unless
 // one record alone holds more), as {r0, r1, e0, e1} quadruples: cuts found on
-// the device, one wait (sg_bucket.hip k_slice_cuts).
+// the device, one wait (sg_part_triage.hip k_slice_cuts).
 int record_slice_cuts(sg_ctx* ctx, const uint64_t* d_off, uint64_t nrec, uint64_t lim, std::vector<uint64_t>& cuts);
-// Two-phase triage (sg_bucket.hip): begin ORs into marks_words the batch's
+// Two-phase triage (sg_prefix.hip): begin ORs into marks_words the batch's
 // signal not in base_words and keeps the batch's partitions (or each such
 // signal's first record) in the slot; end flags the records against
 // mwords | owords and, with `update`, updates mwords / nwords.

@@ -8,7 +8,7 @@
 // records holding s, so the signal space shards cleanly:
 //
 //   candidates  (every rank, its contiguous slice of the batch's records)
-//               the partitioned path (sg_bucket.hip) in emission mode: each
+//               the partitioned path (sg_part.h) in emission mode: each
 //               distinct s not in the replicated maxSignal snapshot, once,
 //               with its first record of the slice (global index), grouped
 //               by owning shard shard_of(s) -- only candidates travel;

@@ -428,7 +428,7 @@ class PrefixTriage:
     of C_k with its first record and step 3 tests those pairs against the
     current maxSignal | P_k (its cost grows with |C_k|: slower on fresh
     batches, cheaper in the fuzzer's low-novelty steady state; include/syzsig.h,
-    sg_bucket.hip).  The rank takes "pairs" while the last batch it has a count
+    sg_prefix.hip).  The rank takes "pairs" while the last batch it has a count
     for had |C_k| below pairs_below of its signal entries; the counts come back
     without a host wait (a pinned copy, read once its event has passed).  The
     forms are interchangeable stage by stage, so ranks may differ.  Stage

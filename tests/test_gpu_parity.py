@@ -496,7 +496,7 @@ def test_triage_edge_cases(C):
 
 
 def test_triage_partition_geometry(C):
-    """Inputs aimed at the partitioned path's tables (sg_bucket.hip): tiles cut
+    """Inputs aimed at the partitioned path's tables (sg_partition.hip): tiles cut
     by the 64-record cap (kRecCap), runs of >= 64 empty records (coinciding
     cuts), record counts around multiples of 64, several pass-2 groups of 1020
     tiles (kGroupTiles), one slice holding the whole batch, and a 2^16-signal
@@ -766,7 +766,7 @@ def test_triage_dev_unaligned_input(C):
 
 def test_triage_record_slices(C):
     """Batches above the per-launch record limit run as consecutive record
-    slices (sg_bucket.hip bucket_triage); the limit is lowered here so that
+    slices (sg_part_triage.hip bucket_triage); the limit is lowered here so that
     slices start mid-batch, at empty records and at group boundaries.  The
     cuts come from the device (k_slice_cuts): up to 64 slices read with their
     count, more in a second read (3, 300), and past 4096 the host's own walk

@@ -1,4 +1,4 @@
-"""The M0 filter (sg_bucket.hip k_m0_index / k_m0_filter and the tail): the
+"""The M0 filter (sg_m0filter.hip k_m0_index / k_m0_filter and the tail): the
 flags path's regime for low-novelty batches, between the two partition
 passes.  Forced on (context option m0_filter 1) every batch must give the
 sequential loop's flags, maxSignal and newSignal (syz-fuzzer/fuzzer.go:645-693,

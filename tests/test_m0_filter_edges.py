@@ -1,4 +1,4 @@
-"""The M0 filter (sg_bucket.hip k_m0_index / k_m0_filter / k_m0_tail_*,
+"""The M0 filter (sg_m0filter.hip k_m0_index / k_m0_filter / k_m0_tail_*,
 m0_filter(), m0f_try()) at its capacity edges, across the partition's
 geometries and through every caller that reaches it.
 
@@ -21,18 +21,18 @@ pytestmark = pytest.mark.gpu
 
 SENT = 0xFFFFFFFF
 
-# The kernel's constants (syzkaller_amd/csrc/sg_bucket.hip, by line).
-K_REM_BITS = 11          # kFRemBits :1914   positions per filter bucket: 2^11 (2^(11-k) with 2^k index parts)
-K_BUCKETS = 8192         # kFBuckets :1915   buckets per index part
-K_OV_USABLE = 1984 - 1   # kFOvBlocks - 1 :1916   overflow blocks per index part (block 0 is the dummy)
-K_SPILL = 512            # kFSpill :1919     spill list per index part
-K_PARTS = 8              # kFParts :1939 (SG_FPARTS :1926)   filter workgroups per slice, 8 >> k per index part
-K_WG_CAP = 2048          # kFWgCap :1940     survivors per filter workgroup
-K_SURV_CAP = 1 << 20     # kFSurvCap :1922   survivors per launch
-K_HDR = 8                # fields of a bucket header (:2020: 7 values and the block link past 8 values)
+# The kernel's constants (syzkaller_amd/csrc/sg_m0filter.hip; the last two sg_part.h).
+K_REM_BITS = 11          # kFRemBits    positions per filter bucket: 2^11 (2^(11-k) with 2^k index parts)
+K_BUCKETS = 8192         # kFBuckets    buckets per index part
+K_OV_USABLE = 1984 - 1   # kFOvBlocks - 1   overflow blocks per index part (block 0 is the dummy)
+K_SPILL = 512            # kFSpill      spill list per index part
+K_PARTS = 8              # kFParts (SG_FPARTS)   filter workgroups per slice, 8 >> k per index part
+K_WG_CAP = 2048          # kFWgCap      survivors per filter workgroup
+K_SURV_CAP = 1 << 20     # kFSurvCap    survivors per launch
+K_HDR = 8                # fields of a bucket header (k_m0_index: 7 values and the block link past 8 values)
 K_BLK = 8                # values of an overflow block
-K_TILE = 16384           # kPT (SG_PT :58)   entries per pass-1 tile
-K_GROUP = 1 << 16        # kGroupRecs :77    records per group
+K_TILE = 16384           # kPT (SG_PT)  entries per pass-1 tile
+K_GROUP = 1 << 16        # kGroupRecs   records per group
 
 
 @pytest.fixture(scope="module")

@@ -1,5 +1,5 @@
 """Set-exact trace triage (sg_triage_traces[_dev]): raw per-call PC traces in,
-edge signal computed in the partition's loads (sg_bucket.hip k_hist_trace /
+edge signal computed in the partition's loads (sg_partition.hip k_hist_trace /
 k_p1_scatter<trace>), zero edges dropped.  The claim under test
 (include/syzsig.h): the per-call flags and the maxSignal / newSignal updates
 equal those of the executor-exact signal (executor/executor.h:389-401,
