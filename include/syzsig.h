@@ -84,7 +84,11 @@ int sg_ctx_kernel_time(sg_ctx* ctx, const char* name, double* ms, uint64_t* laun
  * "hints_candidates" (the last sg_hints_replacers* call's (slot, pair)
  * matches, before deduplication); "exec_comps_general" (the calls the last
  * sg_exec_comps* call sent down its general path), "exec_comps_fast_cap"
- * (SG_EXEC_COMPS_FAST_CAP); "owned_big_records" (the records the last
+ * (SG_EXEC_COMPS_FAST_CAP), and the same two of sg_exec_cover*,
+ * "exec_cover_general" and "exec_cover_fast_cap"; "triage_runs_wide" (the
+ * candidates of the last sg_triage_runs_from_kcov* call that held a cover list
+ * not non-decreasing as u32; counted on the device, read here after a stream
+ * sync); "owned_big_records" (the records the last
  * ordered-output call -- sg_triage_batch[_dev] with diff lists, sg_merge_poll
  * -- swept a workgroup each instead of a wave each, summed over its record
  * slices; counted on the device and read here after a stream sync, so the
@@ -132,6 +136,8 @@ int sg_ctx_counter(sg_ctx* ctx, const char* name, uint64_t* out);
  *   "m0_filter_halves"     its index in 2^k parts per slice (-1 auto: 2 parts once a
  *                          part overflows; 0..2 forced)
  *   "exec_comps_path"      sg_exec_comps' path (-1 by each call's distinct records,
+ *                          0 the general path for every call)
+ *   "exec_cover_path"      sg_exec_cover's path (-1 by each call's distinct PCs,
  *                          0 the general path for every call)
  *   "flag_skip"            the flags path's bucket stage in two launches, the second
  *                          skipping the flag stores of record blocks the first left
@@ -527,6 +533,110 @@ int sg_exec_comps(sg_ctx* ctx, const uint64_t* recs, const uint64_t* call_off, s
 int sg_exec_comps_dev(sg_ctx* ctx, const uint64_t* d_recs, const uint64_t* d_call_off, uint64_t ncalls, uint64_t nrecs,
 		      uint64_t* d_comp_off, uint64_t* d_comps, uint64_t comps_cap, uint64_t* d_word_off,
 		      uint32_t* d_words, uint64_t words_cap);
+
+/* ---- executor cover (executor/executor.h:402-415) --------------------------- */
+/* The flag_collect_cover branch of handle_completion over a batch of raw KCOV
+ * buffers: what a triage execution returns as Cover (syz-fuzzer/fuzzer.go:540-542
+ * sets FlagCollectCover, :708 always adds FlagDedupCover).  pcs is the KCOV
+ * layout unchanged, one u64 per PC (th->cover_data[i]); call c owns
+ * pcs[call_off[c] .. call_off[c+1]), call_off[0] == 0.  Any u64 is a legal PC.
+ * Calls are independent.  cov_off (ncalls + 1) / cov (u32, capacity cov_cap):
+ *  - dedup == 0 (:413-414): cov is (uint32_t)pcs[i] in trace order and cov_off
+ *    equals call_off;
+ *  - dedup == 1 (flag_dedup_cover, :405-410): std::sort ascending as unsigned
+ *    64-bit values (:408), std::unique (:409), then the truncation (:411-414).
+ * The truncation comes after the unique, as in the reference ("assuming that
+ * they fit into 32-bits", :411-412): 0x1_0000_0010 and 0x2_0000_0010 stay two
+ * entries, in u64 order, so a call's u32 list may hold repeats and need not be
+ * ascending when its PCs differ above bit 31.
+ * Offsets are always filled; cov is written only when cov_off[ncalls] <=
+ * cov_cap; call_off[ncalls] values always suffice.  SG_EINVAL: a NULL ctx,
+ * call_off or cov_off; pcs NULL with PCs present; cov NULL with cov_cap > 0;
+ * call_off[0] != 0 or decreasing offsets; 2^32 PCs or more, 2^31 calls or
+ * more; dedup > 1.  A KCOV buffer holds at most 65,535 PCs (kCoverSize,
+ * executor_linux.cc:39, :310); longer calls are exact all the same.
+ * A call whose distinct PCs exceed SG_EXEC_COVER_FAST_CAP leaves the
+ * one-workgroup shape for the general (radix sort) path; it is never truncated
+ * (option "exec_cover_path", counters "exec_cover_general" and
+ * "exec_cover_fast_cap"). */
+#define SG_EXEC_COVER_FAST_CAP 8192
+int sg_exec_cover(sg_ctx* ctx, const uint64_t* pcs, const uint64_t* call_off, size_t ncalls, int dedup,
+		  uint64_t* cov_off, uint32_t* cov, size_t cov_cap);
+/* Device form (npcs = call_off[ncalls]): every pointer is device memory,
+ * stream-ordered.  The offsets cannot be checked: each call's range is clamped
+ * to npcs.  With dedup == 1 a batch of more than SG_EXEC_COVER_FAST_CAP PCs
+ * costs one small device-to-host read (16 B, one wait): the PCs of the calls
+ * that left the fast shape size the general path's workspace.  Smaller batches
+ * (no call of theirs can be flagged), dedup == 0 and option "exec_cover_path"
+ * = 0 read nothing.  The capacity is checked on the device. */
+int sg_exec_cover_dev(sg_ctx* ctx, const uint64_t* d_pcs, const uint64_t* d_call_off, uint64_t ncalls, uint64_t npcs,
+		      int dedup, uint64_t* d_cov_off, uint32_t* d_cov, uint64_t cov_cap);
+
+/* ---- triage re-runs from raw buffers (syz-fuzzer/fuzzer.go:521-576) --------- */
+/* triageInput's loop for n candidates from the raw KCOV buffers of their nruns
+ * re-executions each (1..8; the reference runs 3).  corpus is corpusSignal (only
+ * read); sig_vals / sig_off (n + 1) hold each candidate's inp.signal, raw;
+ * call[k] is inp.call, minimized[k] inp.minimized.  Execution e = k * nruns + i
+ * is run i of candidate k: its calls are prog_off[e] .. prog_off[e+1] (n * nruns
+ * + 1 offsets), call c owns pcs[call_off[c] .. call_off[c+1]), u64 PCs as
+ * sg_exec_cover's.  An execution with no calls, or with fewer than call[k] + 1
+ * calls, is len(info) == 0.  Per run, by definition: Signal_i is call call[k]'s
+ * list from sg_exec_signal on the execution's PCs truncated as (uint32_t)pc
+ * (executor/executor.h:394), the dedup table fresh per execution and shared by
+ * its calls in order; Cover_i is that call's list from sg_exec_cover with dedup
+ * = 1.  Per candidate, exactly fuzzer.go:526-576:
+ *  1. new = Canonicalize(SignalDiff(corpus, inp.signal)) (:527-532); empty:
+ *     SG_TIN_NO_NEW.
+ *  2. minimized (:543-552): cover is a copy of the first non-empty Cover_i,
+ *     whatever Signal_i is (none: empty); SG_TIN_OK, new as in step 1.
+ *  3. otherwise (:553-576), for i ascending: an empty execution or an empty
+ *     Signal_i is skipped once and ends the candidate with SG_TIN_NOT_EXECUTED
+ *     the second time (:558-565); else new = Intersection(new,
+ *     Canonicalize(Signal_i)) (:567), an empty new ends it with SG_TIN_FLAKY
+ *     (:568-570), and cover becomes a copy of Cover_i when it is empty, else
+ *     Union(cover, Cover_i) (:571-575; pkg/cover/cover.go:63-102: a copy keeps a
+ *     0xFFFFFFFF and Union drops it, and Union keeps each value at its largest
+ *     count).  A candidate that survives every run is SG_TIN_OK.
+ * status (n); new_off (n + 1) / new_vals and cov_off (n + 1) / cov_vals: both
+ * lists are empty for every status but SG_TIN_OK.  Offsets are always filled;
+ * each payload is written only when it fits its own capacity (sig_off[n] and
+ * call_off[ncalls] values always suffice).  The caller then runs prog.Minimize
+ * with sg_triage_subset and sends RpcInput{Signal: Canonicalize(inp.signal),
+ * Cover: cover} (:596-603).
+ * A Cover_i that is not non-decreasing as u32 (PCs that differ above bit 31)
+ * makes foreach order-dependent; such candidates are folded by the literal
+ * two-pointer loop and stay exact (counter "triage_runs_wide": the candidates of
+ * the last call that held such a list).  Option "exec_cover_path" applies.
+ * SG_EINVAL: a NULL ctx, corpus (or one of another context), offsets or, with
+ * candidates, call / minimized / status; values NULL where present; a payload
+ * NULL with its capacity > 0; offsets that do not start at 0 or decrease; nruns
+ * outside 1..8; 2^28 candidates, 2^31 calls, 2^32 PCs or signals or more.
+ * The host form stages once and reads back the status and the offsets, then
+ * the payloads. */
+#define SG_TIN_OK 0
+#define SG_TIN_NO_NEW 1       /* fuzzer.go:529-531 */
+#define SG_TIN_NOT_EXECUTED 2 /* :560-562 */
+#define SG_TIN_FLAKY 3        /* :568-570 */
+int sg_triage_runs_from_kcov(sg_ctx* ctx, sg_set* corpus, const uint32_t* sig_vals, const uint64_t* sig_off, size_t n,
+			     const uint32_t* call, const uint8_t* minimized, uint32_t nruns, const uint64_t* pcs,
+			     const uint64_t* call_off, const uint64_t* prog_off, int32_t* status, uint64_t* new_off,
+			     uint32_t* new_vals, size_t new_cap, uint64_t* cov_off, uint32_t* cov_vals, size_t cov_cap);
+/* Device form (nsig = sig_off[n], ncalls = prog_off[n * nruns], npcs =
+ * call_off[ncalls]): every pointer is device memory.  The offsets cannot be
+ * checked and are trusted as sg_exec_signal_dev trusts its own.  Stream-ordered
+ * but for the waits its stages already have, all before the first run: the
+ * 16 bytes of sg_exec_cover_dev when the batch holds more than
+ * SG_EXEC_COVER_FAST_CAP PCs (or with "exec_cover_path" = 0), the SignalDiff
+ * offsets ((n + 1) * 8 bytes, as sg_triage_newsig: Canonicalize is planned on
+ * the host) and Canonicalize's lengths, after which the state words go up.  No
+ * host round trip between the runs or after them.  Its intermediates live in
+ * the context's grow-only device staging buffer. */
+int sg_triage_runs_from_kcov_dev(sg_ctx* ctx, sg_set* corpus, const uint32_t* d_sig_vals, const uint64_t* d_sig_off,
+				 uint64_t n, uint64_t nsig, const uint32_t* d_call, const uint8_t* d_minimized,
+				 uint32_t nruns, const uint64_t* d_pcs, const uint64_t* d_call_off,
+				 const uint64_t* d_prog_off, uint64_t ncalls, uint64_t npcs, int32_t* d_status,
+				 uint64_t* d_new_off, uint32_t* d_new_vals, uint64_t new_cap, uint64_t* d_cov_off,
+				 uint32_t* d_cov_vals, uint64_t cov_cap);
 
 /* ---- synthetic Zipf traces (bench / test input generator) ----------------- */
 /* Zipf(s) over `nranks` PC ranks mapped through a permutation seeded by

@@ -17,6 +17,11 @@ SG_EHIP = -2
 SG_ENOMEM = -3
 SG_ENODEV = -4
 
+TIN_OK = 0  # sg_triage_runs_from_kcov's statuses (include/syzsig.h SG_TIN_*)
+TIN_NO_NEW = 1
+TIN_NOT_EXECUTED = 2
+TIN_FLAKY = 3
+
 OP_DIFFERENCE = 0
 OP_SYMDIFF = 1
 OP_UNION = 2
@@ -111,6 +116,13 @@ SIGNATURES = {
     "sg_exec_comps": (c_int, [c_void_p, P64, P64, c_size_t, P64, P64, c_size_t, P64, P32, c_size_t]),
     "sg_exec_comps_dev": (c_int, [c_void_p, c_void_p, c_void_p, c_uint64, c_uint64, c_void_p, c_void_p, c_uint64, c_void_p,
                                   c_void_p, c_uint64]),
+    "sg_exec_cover": (c_int, [c_void_p, P64, P64, c_size_t, c_int, P64, P32, c_size_t]),
+    "sg_exec_cover_dev": (c_int, [c_void_p, c_void_p, c_void_p, c_uint64, c_uint64, c_int, c_void_p, c_void_p, c_uint64]),
+    "sg_triage_runs_from_kcov": (c_int, [c_void_p, c_void_p, P32, P64, c_size_t, P32, P8, c_uint32, P64, P64, P64,
+                                         POINTER(c_int32), P64, P32, c_size_t, P64, P32, c_size_t]),
+    "sg_triage_runs_from_kcov_dev": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_uint64, c_uint64, c_void_p,
+                                             c_void_p, c_uint32, c_void_p, c_void_p, c_void_p, c_uint64, c_uint64,
+                                             c_void_p, c_void_p, c_void_p, c_uint64, c_void_p, c_void_p, c_uint64]),
     "sg_gen_zipf_traces_dev": (c_int, [c_void_p, c_uint64, c_uint64, c_double, c_uint32, c_uint64, c_uint64, c_uint32,
                                        c_uint32, c_void_p]),
     "sg_gen_population_traces_dev": (c_int, [c_void_p, c_uint64, c_uint64, c_uint64, c_uint64, c_double, c_double,

@@ -78,7 +78,8 @@ class Context:
     def counter(self, name):
         """sg_ctx_counter: "owner_resets", "owner_floor", "owner_key_space", "max_launch_records",
         the host ingest's "host_copy_bytes" / "host_copy_ns" / "host_wait_ns" / "host_copy_threads",
-        "cpu_quota_milli", "hints_candidates", the last ordered-output call's "owned_big_records",
+        "cpu_quota_milli", "hints_candidates", "exec_cover_general" / "exec_cover_fast_cap", "triage_runs_wide",
+        the last ordered-output call's "owned_big_records",
         the last merge's pairs per path "merge_pairs_generic" / "merge_pairs_diff_small" /
         "merge_pairs_gap" / "merge_pairs_tile", the last Canonicalize's "canon_wave_lists" /
         "canon_block_lists" / "canon_big_segments" / "canon_merge_passes"
@@ -480,6 +481,63 @@ def exec_signal(pcs, call_off, prog_off, ctx=None):
     so = np.empty(ncalls + 1, dtype=U64)
     call("sg_exec_signal", _ctx(ctx).h, _p32(p), _p64(co), _p64(po), po.size - 1, _p32(sv), _p64(so))
     return sv[: int(so[-1])], so
+
+
+EXEC_COVER_FAST_CAP = 8192  # include/syzsig.h SG_EXEC_COVER_FAST_CAP: a call's distinct PCs on the fast shape
+
+
+def exec_cover(pcs, call_off, dedup=True, ctx=None):
+    """handle_completion's flag_collect_cover branch (executor/executor.h:402-415)
+    over a batch of raw KCOV buffers: pcs u64, call c's PCs
+    pcs[call_off[c]:call_off[c + 1]].  Returns (cov u32, cov_off): call c's Cover
+    is cov[cov_off[c]:cov_off[c + 1]] -- with dedup (flag_dedup_cover) its
+    distinct PCs in u64 order, truncated after the unique (so PCs that differ
+    only above bit 31 stay separate entries); without it every PC truncated, in
+    trace order."""
+    p, co = _u64(pcs), _u64(call_off)
+    ncalls = co.size - 1
+    npcs = int(co[-1])
+    assert p.size == npcs
+    cvo = np.empty(ncalls + 1, dtype=U64)
+    cov = np.empty(max(npcs, 1), dtype=U32)
+    call("sg_exec_cover", _ctx(ctx).h, _p64(p), _p64(co), ncalls, 1 if dedup else 0, _p64(cvo), _p32(cov), npcs)
+    return cov[: int(cvo[-1])], cvo
+
+
+def triage_runs_from_kcov(corpus, sig_vals, sig_off, call, minimized, nruns, pcs, call_off, prog_off, ctx=None):
+    """triageInput's loop (syz-fuzzer/fuzzer.go:521-576) for n candidates from the
+    raw KCOV buffers of their nruns re-executions each: candidate k's inp.signal
+    is sig_vals[sig_off[k]:sig_off[k + 1]], its call call[k], its runs the
+    executions k * nruns .. (k + 1) * nruns - 1, execution e's calls
+    prog_off[e] .. prog_off[e + 1], call c's u64 PCs pcs[call_off[c]:call_off[c + 1]].
+    Returns (status int32[n], new_vals, new_off, cov_vals, cov_off): newSignal
+    and inputCover per candidate, both empty unless status is TIN_OK."""
+    sv, so, cl, mn = _u32(sig_vals), _u64(sig_off), _u32(call), np.ascontiguousarray(np.asarray(minimized, np.uint8))
+    p, co, po = _u64(pcs), _u64(call_off), _u64(prog_off)
+    n = so.size - 1
+    assert cl.size == n and mn.size == n and po.size == n * nruns + 1 and co.size == int(po[-1]) + 1
+    status = np.empty(max(n, 1), dtype=np.int32)
+    no, vo = np.empty(n + 1, dtype=U64), np.empty(n + 1, dtype=U64)
+    nv, cv = np.empty(max(sv.size, 1), dtype=U32), np.empty(max(p.size, 1), dtype=U32)
+    _lib.call("sg_triage_runs_from_kcov", corpus.ctx.h if ctx is None else ctx.h, corpus.h, _p32(sv), _p64(so), n,
+              _p32(cl), _p8(mn), nruns, _p64(p), _p64(co), _p64(po),
+              status.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), _p64(no), _p32(nv), sv.size, _p64(vo), _p32(cv), p.size)
+    return status[:n], nv[: int(no[-1])], no, cv[: int(vo[-1])], vo
+
+
+def TriageInput(corpus, signal, call, runs, minimized=False):
+    """triageInput (fuzzer.go:521-576) up to prog.Minimize for one candidate:
+    signal is inp.signal, call inp.call, runs the re-executions, each a list of
+    per-call u64 PC arrays (an empty list: the execution returned no info).
+    Returns (status, newSignal, inputCover)."""
+    calls = [np.asarray(c, dtype=U64).reshape(-1) for r in runs for c in r]
+    prog_off = np.concatenate([[0], np.cumsum([len(r) for r in runs])]).astype(U64)
+    call_off = np.concatenate([[0], np.cumsum([c.size for c in calls])]).astype(U64)
+    pcs = np.concatenate(calls) if calls else np.zeros(0, dtype=U64)
+    sig = _u32(signal)
+    status, nv, _, cv, _ = triage_runs_from_kcov(corpus, sig, [0, sig.size], [call], [1 if minimized else 0], len(runs),
+                                                 pcs, call_off, prog_off)
+    return int(status[0]), nv, cv
 
 
 def cover_uncovered(cov, base, sym_start, sym_end, all_pcs, ctx=None):

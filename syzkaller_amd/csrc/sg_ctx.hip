@@ -646,7 +646,8 @@ int sg_ctx_marker(sg_ctx* ctx, int end, uint32_t tag) {
 static const char* const kOptNames[kOptCount] = {
     "bucket_blocks",      "prefix_pairs",       "fold_map",         "minimize_filter",   "minimize_filter_ranks",
     "report_direct",      "rpc_encode_elems",   "rpc_decode_blocks", "host_slice",       "host_copy_threads",
-    "m0_filter",          "m0_filter_halves",   "exec_comps_path",  "flag_skip",         "flag_skip_split"};
+    "m0_filter",          "m0_filter_halves",   "exec_comps_path",  "flag_skip",         "flag_skip_split",
+    "exec_cover_path"};
 
 int sg_ctx_set_option(sg_ctx* ctx, const char* key, int64_t value) {
   if (!ctx || !key) return SG_EINVAL;
@@ -677,8 +678,8 @@ int sg_ctx_set_option(sg_ctx* ctx, const char* key, int64_t value) {
     return SG_OK;
   }
   // value ranges, in kOptNames' order (tri-state options: -1 the regime's choice)
-  static const int64_t kLo[kOptCount] = {0, 0, -1, 0, 0, 0, -1, -1, 0, 0, -1, -1, -1, -1, 1};
-  static const int64_t kHi[kOptCount] = {1 << 20, 1, 1, 1, 1 << 20, 1, 1, 1, 1ll << 40, 64, 1, 2, 0, 1, 8};
+  static const int64_t kLo[kOptCount] = {0, 0, -1, 0, 0, 0, -1, -1, 0, 0, -1, -1, -1, -1, 1, -1};
+  static const int64_t kHi[kOptCount] = {1 << 20, 1, 1, 1, 1 << 20, 1, 1, 1, 1ll << 40, 64, 1, 2, 0, 1, 8, 0};
   for (int i = 0; i < kOptCount; i++)
     if (!strcmp(key, kOptNames[i])) {
       if (value < kLo[i] || value > kHi[i]) {
@@ -758,6 +759,8 @@ int sg_ctx_counter(sg_ctx* ctx, const char* name, uint64_t* out) {
     *out = ctx->hints_cands;
   else if (!strcmp(name, "exec_comps_general"))  // the last sg_exec_comps* call's calls on the general path
     *out = ctx->exec_comps_general;
+  else if (!strcmp(name, "exec_cover_general"))  // the last sg_exec_cover* call's calls on the general path
+    *out = ctx->exec_cover_general;
   else if (!strcmp(name, "merge_pairs_generic"))  // the last merge_dev call's pairs per path (sg_merge.hip)
     *out = ctx->merge_pairs[0];
   else if (!strcmp(name, "merge_pairs_diff_small"))
@@ -779,8 +782,15 @@ int sg_ctx_counter(sg_ctx* ctx, const char* name, uint64_t* out) {
     SG_HIP(hipStreamSynchronize(ctx->stream));
     SG_HIP(hipMemcpy(&v, ctx->own_big, 4, hipMemcpyDeviceToHost));
     *out = v;
+  } else if (!strcmp(name, "triage_runs_wide")) {  // the last sg_triage_runs_from_kcov* call's candidates folded by foreach
+    uint32_t v = 0;                                 // for a cover that is not non-decreasing (sg_triage_runs.hip)
+    SG_HIP(hipStreamSynchronize(ctx->stream));
+    SG_HIP(hipMemcpy(&v, ctx->own_big + kTrWideSlot, 4, hipMemcpyDeviceToHost));
+    *out = v;
   } else if (!strcmp(name, "exec_comps_fast_cap"))  // distinct records a call may hold on the fast shape
     *out = SG_EXEC_COMPS_FAST_CAP;
+  else if (!strcmp(name, "exec_cover_fast_cap"))  // distinct PCs a call may hold on the fast shape
+    *out = SG_EXEC_COVER_FAST_CAP;
   else if (!strcmp(name, "cpu_quota_milli"))
     *out = (uint64_t)(ctx->cpu_quota * 1000.0 + 0.5);
   else {

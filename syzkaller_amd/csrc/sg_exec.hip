@@ -489,16 +489,13 @@ static void build_zipf_tables(uint64_t seed, double s, uint32_t N, std::vector<u
 
 }  // namespace sg
 
-using namespace sg;
+namespace sg {
 
-extern "C" {
-
-static int exec_signal(sg_ctx* ctx, const uint32_t* d_pcs, const uint64_t* d_call_off, const uint64_t* d_prog_off,
-                       uint64_t nprog, uint64_t ncalls, uint64_t npcs, const uint8_t* d_rec_new, uint32_t* d_sig_vals,
-                       uint64_t* d_sig_off) {
-  std::lock_guard<std::mutex> g(ctx->mu);
-  int rc = ensure_device(ctx);
-  if (rc) return rc;
+// sg_exec_signal_dev's / sg_exec_signal_queued_dev's body; ctx lock held, the device ensured (sg_internal.h)
+int exec_signal_body(sg_ctx* ctx, const uint32_t* d_pcs, const uint64_t* d_call_off, const uint64_t* d_prog_off,
+                     uint64_t nprog, uint64_t ncalls, uint64_t npcs, const uint8_t* d_rec_new, uint32_t* d_sig_vals,
+                     uint64_t* d_sig_off) {
+  int rc = SG_OK;
   if (ncalls == 0) {
     SG_HIP(hipMemsetAsync(d_sig_off, 0, 8, ctx->stream));
     return SG_OK;
@@ -559,6 +556,21 @@ static int exec_signal(sg_ctx* ctx, const uint32_t* d_pcs, const uint64_t* d_cal
   }
   SG_HIP(hipGetLastError());
   return SG_OK;
+}
+
+}  // namespace sg
+
+using namespace sg;
+
+extern "C" {
+
+static int exec_signal(sg_ctx* ctx, const uint32_t* d_pcs, const uint64_t* d_call_off, const uint64_t* d_prog_off,
+                       uint64_t nprog, uint64_t ncalls, uint64_t npcs, const uint8_t* d_rec_new, uint32_t* d_sig_vals,
+                       uint64_t* d_sig_off) {
+  std::lock_guard<std::mutex> g(ctx->mu);
+  int rc = ensure_device(ctx);
+  if (rc) return rc;
+  return exec_signal_body(ctx, d_pcs, d_call_off, d_prog_off, nprog, ncalls, npcs, d_rec_new, d_sig_vals, d_sig_off);
 }
 
 int sg_exec_signal_dev(sg_ctx* ctx, const uint32_t* d_pcs, const uint64_t* d_call_off, const uint64_t* d_prog_off,

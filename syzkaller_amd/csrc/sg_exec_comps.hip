@@ -399,21 +399,14 @@ __global__ __launch_bounds__(256) void k_ec_emit(const uint64_t* __restrict__ ca
   }
 }
 
-static uint64_t ec_bits_below(uint64_t n) {  // a mask covering 0 .. n - 1
+uint64_t ec_bits_below(uint64_t n) {  // a mask covering 0 .. n - 1
   uint64_t m = 0;
   while (n > 1 && m < n - 1) m = (m << 1) | 1;
   return m;
 }
 
-struct EcGen {
-  uint64_t ng;
-  uint64_t *v, *ka, *kb, *pos;
-  uint32_t* flags;
-  size_t tail;  // the sort's and the scan's workspace
-};
-
 // v (and its copy in ka) -> the distinct values u, ascending, and each value's rank
-static int ec_rank(sg_ctx* ctx, const EcGen& g, uint64_t vary, uint64_t* u, uint32_t* rank) {
+int ec_rank(sg_ctx* ctx, const EcGen& g, uint64_t vary, uint64_t* u, uint32_t* rank) {
   const dim3 grid(div_up(g.ng, 256)), b(256);
   uint64_t* sorted = nullptr;
   int rc = radix_sort_u64(ctx, g.ka, g.kb, g.ng, g.tail, &sorted, vary ? vary : 1);
@@ -425,6 +418,37 @@ static int ec_rank(sg_ctx* ctx, const EcGen& g, uint64_t vary, uint64_t* u, uint
                      (const uint64_t*)g.pos, g.ng, u);
   hipLaunchKernelGGL(k_ec_rank, grid, b, 0, ctx->stream, (const uint64_t*)g.v, g.ng, (const uint64_t*)u,
                      (const uint64_t*)(g.pos + g.ng), rank);
+  SG_HIP(hipGetLastError());
+  return SG_OK;
+}
+
+// gidx / gcall: the record and the call of each of the ng places of the flagged calls (call c's at gbase[c])
+int ec_fill(sg_ctx* ctx, const uint64_t* call_off, uint64_t ncalls, uint64_t nrecs, const uint8_t* flag,
+            const uint64_t* gbase, uint64_t ng, uint32_t* gidx, uint32_t* gcall) {
+  // places never assigned (none, when the counts are consistent) read record 0 of call 0
+  SG_HIP(hipMemsetAsync(gidx, 0, ng * 4, ctx->stream));
+  SG_HIP(hipMemsetAsync(gcall, 0, ng * 4, ctx->stream));
+  hipLaunchKernelGGL(k_ec_fill, dim3((uint32_t)ncalls), dim3(256), 0, ctx->stream, call_off, nrecs, flag, gbase, ng, gidx,
+                     gcall);
+  SG_HIP(hipGetLastError());
+  return SG_OK;
+}
+
+// The sort of call << 32 | rank (*sorted), its first occurrences (g.flags) and their scan (g.pos), and each
+// call's first place among them (first, [ncalls])
+int ec_call_first(sg_ctx* ctx, const EcGen& g, const uint32_t* gcall, const uint32_t* rank, uint64_t ncalls,
+                  uint64_t* first, uint64_t** sorted) {
+  const dim3 grid(div_up(g.ng, 256)), b(256);
+  SG_HIP(hipMemsetAsync(first, 0, ncalls * 8, ctx->stream));
+  hipLaunchKernelGGL(k_ec_pack, grid, b, 0, ctx->stream, gcall, rank, g.ng, g.v, g.ka);
+  const uint64_t kvary = (ec_bits_below(ncalls) << 32) | ec_bits_below(g.ng);
+  int rc = radix_sort_u64(ctx, g.ka, g.kb, g.ng, g.tail, sorted, kvary ? kvary : 1);
+  if (rc) return rc;
+  hipLaunchKernelGGL(k_ec_mark, grid, b, 0, ctx->stream, (const uint64_t*)*sorted, g.ng, g.flags);
+  rc = scan_counts(ctx, g.flags, g.pos, g.ng, g.tail);
+  if (rc) return rc;
+  hipLaunchKernelGGL(k_ec_first, grid, b, 0, ctx->stream, (const uint64_t*)*sorted, (const uint64_t*)g.pos, g.ng, ncalls,
+                     first);
   SG_HIP(hipGetLastError());
   return SG_OK;
 }
@@ -461,14 +485,9 @@ static int ec_general(sg_ctx* ctx, const EcArgs& a, uint64_t ng, size_t base) {
   uint64_t *ut = (uint64_t*)ws_at(ctx, o_ut), *u1 = (uint64_t*)ws_at(ctx, o_u1), *u2 = (uint64_t*)ws_at(ctx, o_u2),
            *ub = (uint64_t*)ws_at(ctx, o_ub), *uc = (uint64_t*)ws_at(ctx, o_uc);
   const dim3 grid(div_up(ng, 256)), b(256);
-  // places never assigned (none, when the counts are consistent) read record 0 of call 0
-  SG_HIP(hipMemsetAsync(gidx, 0, ng * 4, ctx->stream));
-  SG_HIP(hipMemsetAsync(gcall, 0, ng * 4, ctx->stream));
-  SG_HIP(hipMemsetAsync(first, 0, a.ncalls * 8, ctx->stream));
-  hipLaunchKernelGGL(k_ec_fill, dim3((uint32_t)a.ncalls), b, 0, ctx->stream, a.call_off, a.nrecs,
-                     (const uint8_t*)a.flag, (const uint64_t*)a.gbase, ng, gidx, gcall);
+  int rc = ec_fill(ctx, a.call_off, a.ncalls, a.nrecs, a.flag, a.gbase, ng, gidx, gcall);
+  if (rc) return rc;
   const uint64_t rk = ec_bits_below(ng), packed = (rk << 32) | rk;
-  int rc;
   // 1. distinct arg2 -> A
   hipLaunchKernelGGL(k_ec_field, grid, b, 0, ctx->stream, a.recs, (const uint32_t*)gidx, ng, 2u, g.v, g.ka);
   if ((rc = ec_rank(ctx, g, ~0ull, u2, rlo))) return rc;
@@ -483,16 +502,8 @@ static int ec_general(sg_ctx* ctx, const EcArgs& a, uint64_t ng, size_t base) {
   hipLaunchKernelGGL(k_ec_pack, grid, b, 0, ctx->stream, (const uint32_t*)rhi, (const uint32_t*)rlo, ng, g.v, g.ka);
   if ((rc = ec_rank(ctx, g, packed, uc, rlo))) return rc;
   // 4. sort call << 32 | C; 5. first occurrences; 6. the survivors' triples through the tables
-  hipLaunchKernelGGL(k_ec_pack, grid, b, 0, ctx->stream, (const uint32_t*)gcall, (const uint32_t*)rlo, ng, g.v, g.ka);
   uint64_t* sorted = nullptr;
-  const uint64_t kvary = (ec_bits_below(a.ncalls) << 32) | rk;
-  rc = radix_sort_u64(ctx, g.ka, g.kb, ng, g.tail, &sorted, kvary ? kvary : 1);
-  if (rc) return rc;
-  hipLaunchKernelGGL(k_ec_mark, grid, b, 0, ctx->stream, (const uint64_t*)sorted, ng, g.flags);
-  rc = scan_counts(ctx, g.flags, g.pos, ng, g.tail);
-  if (rc) return rc;
-  hipLaunchKernelGGL(k_ec_first, grid, b, 0, ctx->stream, (const uint64_t*)sorted, (const uint64_t*)g.pos, ng, a.ncalls,
-                     first);
+  if ((rc = ec_call_first(ctx, g, gcall, rlo, a.ncalls, first, &sorted))) return rc;
   EcTables t{ut, u1, u2, ub, uc};
   hipLaunchKernelGGL(k_ec_gwrite, grid, b, 0, ctx->stream, (const uint64_t*)sorted, (const uint32_t*)g.flags,
                      (const uint64_t*)g.pos, ng, t, (const uint64_t*)first, a.call_off, a.ncalls, a.nrecs, a.tmp, a.cnt,

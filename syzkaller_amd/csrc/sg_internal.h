@@ -99,12 +99,13 @@ enum SgOpt : int {
   kOptFlagSkip,             // bucket stage in two launches, the second skipping the flag stores of fully queued
                             // record blocks (sg_bucket.hip): -1 by the last partitioned slice, 0 never, 1 always
   kOptFlagSkipSplit,        // ... the first launch takes the first 1 / 2^k of the bucket list
+  kOptExecCoverPath,        // sg_exec_cover: -1 by each call's distinct PCs, 0 the general path for every call
   kOptCount
 };
 
 struct sg_ctx {
   int device = 0;
-  int64_t opt[kOptCount] = {0, 0, -1, 1, 0, 0, -1, -1, 0, 0, -1, -1, -1, -1, 3};
+  int64_t opt[kOptCount] = {0, 0, -1, 1, 0, 0, -1, -1, 0, 0, -1, -1, -1, -1, 3, -1};
   // the M0 filter's buffers (lazy, sg_m0filter.hip) and its regime state: the
   // last record slice's outcome (1 filtered, 0 partitioned), the queued
   // records of the last partitioned slice (counted on the device, read back
@@ -137,6 +138,8 @@ struct sg_ctx {
   uint64_t hints_cands = 0;
   // the calls the last sg_exec_comps* call sent down the general path (sg_exec_comps.hip)
   uint64_t exec_comps_general = 0;
+  // ... and the last sg_exec_cover* call (sg_exec_cover.hip)
+  uint64_t exec_cover_general = 0;
   // the last merge_dev call's pairs per path (generic, k_diff_small, and
   // k_merge_small's gap / tile forms) and the last canonicalize_dev call's
   // segments per path (a wave each, a workgroup each, the big path) with its
@@ -333,6 +336,40 @@ int exec_comps(sg_ctx* ctx, const uint64_t* d_recs, const uint64_t* d_call_off, 
                uint64_t* d_comp_off, uint64_t* d_comps, uint64_t comps_cap, uint64_t* d_word_off, uint32_t* d_words,
                uint64_t words_cap, EcRaw* raw = nullptr);
 int ec_limits(uint64_t ncalls, uint64_t nrecs);
+// sg_exec_signal_dev's body, and with d_rec_new sg_exec_signal_queued_dev's
+// (sg_exec.hip; ctx lock held, the device ensured).  Plans the workspace from 0.
+int exec_signal_body(sg_ctx* ctx, const uint32_t* d_pcs, const uint64_t* d_call_off, const uint64_t* d_prog_off,
+                     uint64_t nprog, uint64_t ncalls, uint64_t npcs, const uint8_t* d_rec_new, uint32_t* d_sig_vals,
+                     uint64_t* d_sig_off);
+// sg_exec_cover_dev's body (sg_exec_cover.hip; ctx lock held, the device
+// ensured).  With sel ([ncalls], nullable) only the calls with sel[c] != 0 run;
+// the others get empty lists.  Plans the workspace from 0.
+int exec_cover(sg_ctx* ctx, const uint64_t* d_pcs, const uint64_t* d_call_off, uint64_t ncalls, uint64_t npcs, int dedup,
+               uint64_t* d_cov_off, uint32_t* d_cov, uint64_t cov_cap, const uint8_t* sel = nullptr);
+// own_big is 256 B of device counters read by sg_ctx_counter alone: [0]
+// "owned_big_records", [kTrWideSlot] "triage_runs_wide" (sg_triage_runs.hip)
+constexpr uint32_t kTrWideSlot = 16;
+// Stages of the general path that sg_exec_cover.hip shares (sg_exec_comps.hip;
+// ctx lock held).  EcGen: ng values in v with a copy in ka, a second key buffer
+// kb, pos [ng + 1], flags [ng], and the workspace past `tail` for the sort and
+// the scan.  ec_rank: v -> its distinct values u, ascending (their number at
+// pos[ng]), and each value's rank among them.  ec_fill: the member (gidx) and
+// the call (gcall) of each of the ng places of the flagged calls, call c's
+// from gbase[c].  ec_call_first: the sort of gcall << 32 | rank (*sorted), its
+// first occurrences (flags) with their scan (pos), and each call's first
+// place among them (first, [ncalls]).
+struct EcGen {
+  uint64_t ng;
+  uint64_t *v, *ka, *kb, *pos;
+  uint32_t* flags;
+  size_t tail;
+};
+uint64_t ec_bits_below(uint64_t n);
+int ec_rank(sg_ctx* ctx, const EcGen& g, uint64_t vary, uint64_t* u, uint32_t* rank);
+int ec_fill(sg_ctx* ctx, const uint64_t* call_off, uint64_t ncalls, uint64_t nrecs, const uint8_t* flag,
+            const uint64_t* gbase, uint64_t ng, uint32_t* gidx, uint32_t* gcall);
+int ec_call_first(sg_ctx* ctx, const EcGen& g, const uint32_t* gcall, const uint32_t* rank, uint64_t ncalls,
+                  uint64_t* first, uint64_t** sorted);
 // The join and the sorts behind sg_hints_replacers* (sg_hints.hip; ctx lock
 // held).  Plans the context workspace from offset 0 and may move it.  With
 // reps_in_ws the replacers go to a workspace buffer of min(cap, candidates)
