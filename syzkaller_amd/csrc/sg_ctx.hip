@@ -94,6 +94,31 @@ int dstage_reserve(sg_ctx* ctx, size_t bytes) {
   return SG_OK;
 }
 
+static int plan_ok(const WsPlan& plan) {
+  if (!plan.overflow) return SG_OK;
+  set_error("a buffer plan of more than %d regions", WsPlan::kMaxRegions);
+  return SG_EINVAL;
+}
+int ws_reserve(sg_ctx* ctx, const WsPlan& plan) { return plan_ok(plan) ? SG_EINVAL : ws_reserve(ctx, plan.total); }
+int dstage_reserve(sg_ctx* ctx, const WsPlan& plan) {
+  return plan_ok(plan) ? SG_EINVAL : dstage_reserve(ctx, plan.total);
+}
+
+int upload(sg_ctx* ctx, void* d_dst, const void* h_src, size_t bytes) {
+  if (bytes) SG_HIP(hipMemcpyAsync(d_dst, h_src, bytes, hipMemcpyHostToDevice, ctx->stream));
+  return SG_OK;
+}
+
+int csr_download(sg_ctx* ctx, uint64_t* h_off, const uint64_t* d_off, uint64_t n, void* h_vals, const void* d_vals,
+                 size_t elem, uint64_t cap) {
+  SG_HIP(hipMemcpyAsync(h_off, d_off, (n + 1) * 8, hipMemcpyDeviceToHost, ctx->stream));
+  SG_HIP(hipStreamSynchronize(ctx->stream));
+  if (h_off[n] && h_off[n] <= cap)
+    SG_HIP(hipMemcpyAsync(h_vals, d_vals, h_off[n] * elem, hipMemcpyDeviceToHost, ctx->stream));
+  SG_HIP(hipStreamSynchronize(ctx->stream));
+  return SG_OK;
+}
+
 int owner_keys(sg_ctx* ctx, uint64_t nkeys, uint32_t* key_lo) {
   if (nkeys > ctx->owner_key_space) {
     set_error("batch of %llu keys exceeds the first-owner key space (%llu)", (unsigned long long)nkeys,
@@ -1005,8 +1030,7 @@ int sg_set_export(sg_set* set, uint32_t* out, size_t cap, size_t* n) {
   if (m == 0) return SG_OK;
   // output staged in the workspace after the scan area
   size_t used = ((kSetWords / kTile) * 4 + 255) / 256 * 256 + (((kSetWords / kTile) + 1) * 8 + 255) / 256 * 256;
-  size_t o_out = used + scan_ws_bytes(kSetWords / kTile);
-  o_out = (o_out + 255) & ~size_t(255);
+  const size_t o_out = align256(used + scan_ws_bytes(kSetWords / kTile));
   rc = ws_reserve(ctx, o_out + m * 4);
   if (rc) return rc;
   // ws may have been reallocated: recompute the tile bases if so

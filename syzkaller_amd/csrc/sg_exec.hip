@@ -596,32 +596,30 @@ int sg_exec_signal(sg_ctx* ctx, const uint32_t* pcs, const uint64_t* call_off, c
   uint64_t ncalls = prog_off[nprog];
   uint64_t npcs = call_off[ncalls];
   if (prog_off[0] != 0 || call_off[0] != 0 || (npcs && (!pcs || !sig_vals))) return SG_EINVAL;
-  char* st = nullptr;
-  size_t b0 = (npcs * 4 + 255) & ~size_t(255), b1 = ((ncalls + 1) * 8 + 255) & ~size_t(255),
-         b2 = ((nprog + 1) * 8 + 255) & ~size_t(255);
+  WsPlan p;
+  const size_t o_p = p.add(npcs * 4), o_sv = p.add(npcs * 4), o_co = p.add((ncalls + 1) * 8),
+               o_so = p.add((ncalls + 1) * 8), o_po = p.add((nprog + 1) * 8);
+  uint32_t *dp, *dsv;
+  uint64_t *dco, *dso, *dpo;
   {
     std::lock_guard<std::mutex> g(ctx->mu);
     int rc = ensure_device(ctx);
     if (rc) return rc;
-    rc = dstage_reserve(ctx, 2 * b0 + 2 * b1 + b2 + 256);
+    rc = dstage_reserve(ctx, p);
     if (rc) return rc;
-    st = (char*)ctx->dstage;
+    dp = dstage_at<uint32_t>(ctx, o_p);
+    dsv = dstage_at<uint32_t>(ctx, o_sv);
+    dco = dstage_at<uint64_t>(ctx, o_co);
+    dso = dstage_at<uint64_t>(ctx, o_so);
+    dpo = dstage_at<uint64_t>(ctx, o_po);
   }
-  uint32_t* dp = (uint32_t*)st;
-  uint32_t* dsv = (uint32_t*)(st + b0);
-  uint64_t* dco = (uint64_t*)(st + 2 * b0);
-  uint64_t* dso = (uint64_t*)(st + 2 * b0 + b1);
-  uint64_t* dpo = (uint64_t*)(st + 2 * b0 + 2 * b1);
-  if (npcs) SG_HIP(hipMemcpyAsync(dp, pcs, npcs * 4, hipMemcpyHostToDevice, ctx->stream));
-  SG_HIP(hipMemcpyAsync(dco, call_off, (ncalls + 1) * 8, hipMemcpyHostToDevice, ctx->stream));
-  SG_HIP(hipMemcpyAsync(dpo, prog_off, (nprog + 1) * 8, hipMemcpyHostToDevice, ctx->stream));
-  int rc = sg_exec_signal_dev(ctx, dp, dco, dpo, nprog, ncalls, npcs, dsv, dso);
+  int rc;
+  if ((rc = upload(ctx, dp, pcs, npcs * 4))) return rc;
+  if ((rc = upload(ctx, dco, call_off, (ncalls + 1) * 8))) return rc;
+  if ((rc = upload(ctx, dpo, prog_off, (nprog + 1) * 8))) return rc;
+  rc = sg_exec_signal_dev(ctx, dp, dco, dpo, nprog, ncalls, npcs, dsv, dso);
   if (rc) return rc;
-  SG_HIP(hipMemcpyAsync(sig_off, dso, (ncalls + 1) * 8, hipMemcpyDeviceToHost, ctx->stream));
-  SG_HIP(hipStreamSynchronize(ctx->stream));
-  if (sig_off[ncalls]) SG_HIP(hipMemcpyAsync(sig_vals, dsv, sig_off[ncalls] * 4, hipMemcpyDeviceToHost, ctx->stream));
-  SG_HIP(hipStreamSynchronize(ctx->stream));
-  return SG_OK;
+  return csr_download(ctx, sig_off, dso, ncalls, sig_vals, dsv, 4, ~0ull);
 }
 
 // The fuzzer's whole step from host traces: the set-exact triage (flags,
@@ -641,36 +639,35 @@ int sg_triage_traces_queued(sg_ctx* ctx, sg_set* maxsig, sg_set* newsig, const u
     set_error("sg_triage_traces_queued: invalid argument (offsets must start at 0; null buffers)");
     return SG_EINVAL;
   }
-  char* st = nullptr;
-  const size_t b0 = (npcs * 4 + 255) & ~size_t(255), b1 = ((ncalls + 1) * 8 + 255) & ~size_t(255),
-               b2 = ((nprog + 1) * 8 + 255) & ~size_t(255), b3 = (ncalls + 255) & ~size_t(255);
+  WsPlan p;
+  const size_t o_p = p.add(npcs * 4), o_sv = p.add(npcs * 4), o_co = p.add((ncalls + 1) * 8),
+               o_so = p.add((ncalls + 1) * 8), o_po = p.add((nprog + 1) * 8), o_rn = p.add(ncalls);
+  uint32_t *dp, *dsv;
+  uint64_t *dco, *dso, *dpo;
+  uint8_t* drn;
   {
     std::lock_guard<std::mutex> g(ctx->mu);
     int rc = ensure_device(ctx);
     if (rc) return rc;
-    rc = dstage_reserve(ctx, 2 * b0 + 2 * b1 + b2 + b3 + 256);
+    rc = dstage_reserve(ctx, p);
     if (rc) return rc;
-    st = (char*)ctx->dstage;
+    dp = dstage_at<uint32_t>(ctx, o_p);
+    dsv = dstage_at<uint32_t>(ctx, o_sv);
+    dco = dstage_at<uint64_t>(ctx, o_co);
+    dso = dstage_at<uint64_t>(ctx, o_so);
+    dpo = dstage_at<uint64_t>(ctx, o_po);
+    drn = dstage_at<uint8_t>(ctx, o_rn);
   }
-  uint32_t* dp = (uint32_t*)st;
-  uint32_t* dsv = (uint32_t*)(st + b0);
-  uint64_t* dco = (uint64_t*)(st + 2 * b0);
-  uint64_t* dso = (uint64_t*)(st + 2 * b0 + b1);
-  uint64_t* dpo = (uint64_t*)(st + 2 * b0 + 2 * b1);
-  uint8_t* drn = (uint8_t*)(st + 2 * b0 + 2 * b1 + b2);
-  if (npcs) SG_HIP(hipMemcpyAsync(dp, pcs, npcs * 4, hipMemcpyHostToDevice, ctx->stream));
-  SG_HIP(hipMemcpyAsync(dco, call_off, (ncalls + 1) * 8, hipMemcpyHostToDevice, ctx->stream));
-  SG_HIP(hipMemcpyAsync(dpo, prog_off, (nprog + 1) * 8, hipMemcpyHostToDevice, ctx->stream));
-  int rc = sg_triage_traces_dev(ctx, maxsig, newsig, dp, dco, npcs, ncalls, drn);
+  int rc;
+  if ((rc = upload(ctx, dp, pcs, npcs * 4))) return rc;
+  if ((rc = upload(ctx, dco, call_off, (ncalls + 1) * 8))) return rc;
+  if ((rc = upload(ctx, dpo, prog_off, (nprog + 1) * 8))) return rc;
+  rc = sg_triage_traces_dev(ctx, maxsig, newsig, dp, dco, npcs, ncalls, drn);
   if (rc) return rc;
   rc = sg_exec_signal_queued_dev(ctx, dp, dco, dpo, nprog, ncalls, npcs, drn, dsv, dso);
   if (rc) return rc;
   if (ncalls) SG_HIP(hipMemcpyAsync(rec_new, drn, ncalls, hipMemcpyDeviceToHost, ctx->stream));
-  SG_HIP(hipMemcpyAsync(sig_off, dso, (ncalls + 1) * 8, hipMemcpyDeviceToHost, ctx->stream));
-  SG_HIP(hipStreamSynchronize(ctx->stream));
-  if (sig_off[ncalls]) SG_HIP(hipMemcpyAsync(sig_vals, dsv, sig_off[ncalls] * 4, hipMemcpyDeviceToHost, ctx->stream));
-  SG_HIP(hipStreamSynchronize(ctx->stream));
-  return SG_OK;
+  return csr_download(ctx, sig_off, dso, ncalls, sig_vals, dsv, 4, ~0ull);
 }
 
 }  // extern "C"

@@ -455,9 +455,8 @@ int ec_call_first(sg_ctx* ctx, const EcGen& g, const uint32_t* gcall, const uint
 
 // ec_general's workspace: five u32 and eight u64 arrays of ng, the scan's ng + 1, a u64 per call
 static size_t ec_general_bytes(uint64_t ng, uint64_t ncalls) {
-  auto al = [](size_t b) { return (b + 255) & ~size_t(255); };
-  return 5 * al(ng * 4) + 8 * al(ng * 8) + al((ng + 1) * 8) + al(ncalls * 8) + radix_sort_ws(ng) + scan_ws_bytes(ng) +
-         4096;
+  return 5 * align256(ng * 4) + 8 * align256(ng * 8) + align256((ng + 1) * 8) + align256(ncalls * 8) +
+         radix_sort_ws(ng) + scan_ws_bytes(ng) + 4096;
 }
 
 // the flagged calls' ng records (places gbase) -> their workspace triples and counts
@@ -653,30 +652,28 @@ int sg_exec_comps(sg_ctx* ctx, const uint64_t* recs, const uint64_t* call_off, s
                   uint64_t* comps, size_t comps_cap, uint64_t* word_off, uint32_t* words, size_t words_cap) {
   if (!ctx || !call_off || !comp_off || (comps_cap && !comps) || (word_off && words_cap && !words)) return SG_EINVAL;
   const uint64_t nrecs = call_off[ncalls];
-  if (call_off[0] != 0 || (nrecs && !recs)) return SG_EINVAL;
-  for (size_t c = 0; c < ncalls; c++)
-    if (call_off[c + 1] < call_off[c]) return SG_EINVAL;
+  if (!offsets_ok(call_off, ncalls) || (nrecs && !recs)) return SG_EINVAL;
   int rc = ec_limits(ncalls, nrecs);
   if (rc) return rc;
   // nrecs triples and 5 nrecs words always suffice: a smaller cap is staged as it is
   const uint64_t ccap = comps_cap < nrecs ? comps_cap : nrecs;
   const uint64_t wcap = !word_off ? 0 : (words_cap < 5 * nrecs ? words_cap : 5 * nrecs);
-  auto al = [](size_t b) { return (b + 255) & ~size_t(255); };
-  const size_t br = al(nrecs * 32 + 32), bo = al((ncalls + 1) * 8), bc = al(ccap * 24 + 24), bw = al(wcap * 4 + 4);
+  WsPlan p;
+  const size_t o_recs = p.add(nrecs * 32 + 32), o_co = p.add((ncalls + 1) * 8), o_comp_off = p.add((ncalls + 1) * 8),
+               o_word_off = p.add((ncalls + 1) * 8), o_comps = p.add(ccap * 24 + 24), o_words = p.add(wcap * 4 + 4);
   std::lock_guard<std::mutex> g(ctx->mu);
   rc = ensure_device(ctx);
   if (rc) return rc;
-  rc = dstage_reserve(ctx, br + 3 * bo + bc + bw + 256);
+  rc = dstage_reserve(ctx, p);
   if (rc) return rc;
-  char* st = (char*)ctx->dstage;
-  uint64_t* drecs = (uint64_t*)st;
-  uint64_t* dco = (uint64_t*)(st + br);
-  uint64_t* dcomp_off = (uint64_t*)(st + br + bo);
-  uint64_t* dword_off = (uint64_t*)(st + br + 2 * bo);
-  uint64_t* dcomps = (uint64_t*)(st + br + 3 * bo);
-  uint32_t* dwords = (uint32_t*)(st + br + 3 * bo + bc);
-  if (nrecs) SG_HIP(hipMemcpyAsync(drecs, recs, nrecs * 32, hipMemcpyHostToDevice, ctx->stream));
-  SG_HIP(hipMemcpyAsync(dco, call_off, (ncalls + 1) * 8, hipMemcpyHostToDevice, ctx->stream));
+  uint64_t* drecs = dstage_at<uint64_t>(ctx, o_recs);
+  uint64_t* dco = dstage_at<uint64_t>(ctx, o_co);
+  uint64_t* dcomp_off = dstage_at<uint64_t>(ctx, o_comp_off);
+  uint64_t* dword_off = dstage_at<uint64_t>(ctx, o_word_off);
+  uint64_t* dcomps = dstage_at<uint64_t>(ctx, o_comps);
+  uint32_t* dwords = dstage_at<uint32_t>(ctx, o_words);
+  if ((rc = upload(ctx, drecs, recs, nrecs * 32))) return rc;
+  if ((rc = upload(ctx, dco, call_off, (ncalls + 1) * 8))) return rc;
   rc = exec_comps(ctx, drecs, dco, ncalls, nrecs, dcomp_off, ccap ? dcomps : nullptr, ccap,
                   word_off ? dword_off : nullptr, wcap ? dwords : nullptr, wcap);
   if (rc) return rc;

@@ -281,9 +281,8 @@ __global__ __launch_bounds__(256) void k_xc_emit(const uint64_t* __restrict__ ca
 
 // xc_general's workspace: four u32 and four u64 arrays of ng, the scan's ng + 1, a u64 per call
 static size_t xc_general_bytes(uint64_t ng, uint64_t ncalls) {
-  auto al = [](size_t b) { return (b + 255) & ~size_t(255); };
-  return 4 * al(ng * 4) + 4 * al(ng * 8) + al((ng + 1) * 8) + al(ncalls * 8) + radix_sort_ws(ng) + scan_ws_bytes(ng) +
-         4096;
+  return 4 * align256(ng * 4) + 4 * align256(ng * 8) + align256((ng + 1) * 8) + align256(ncalls * 8) +
+         radix_sort_ws(ng) + scan_ws_bytes(ng) + 4096;
 }
 
 // the flagged calls' ng PCs (places gbase) -> their workspace lists and counts
@@ -454,35 +453,28 @@ int sg_exec_cover(sg_ctx* ctx, const uint64_t* pcs, const uint64_t* call_off, si
                   uint64_t* cov_off, uint32_t* cov, size_t cov_cap) {
   if (!ctx || !call_off || !cov_off || (cov_cap && !cov)) return SG_EINVAL;
   const uint64_t npcs = call_off[ncalls];
-  if (call_off[0] != 0 || (npcs && !pcs)) return SG_EINVAL;
-  for (size_t c = 0; c < ncalls; c++)
-    if (call_off[c + 1] < call_off[c]) return SG_EINVAL;
+  if (!offsets_ok(call_off, ncalls) || (npcs && !pcs)) return SG_EINVAL;
   int rc = xc_limits(ncalls, npcs, dedup);
   if (rc) return rc;
   // npcs values always suffice: a smaller cap is staged as it is
   const uint64_t ccap = cov_cap < npcs ? cov_cap : npcs;
-  auto al = [](size_t b) { return (b + 255) & ~size_t(255); };
-  const size_t bp = al(npcs * 8 + 8), bo = al((ncalls + 1) * 8), bc = al(ccap * 4 + 4);
+  WsPlan p;
+  const size_t o_pcs = p.add(npcs * 8 + 8), o_co = p.add((ncalls + 1) * 8), o_cov_off = p.add((ncalls + 1) * 8),
+               o_cov = p.add(ccap * 4 + 4);
   std::lock_guard<std::mutex> g(ctx->mu);
   rc = ensure_device(ctx);
   if (rc) return rc;
-  rc = dstage_reserve(ctx, bp + 2 * bo + bc + 256);
+  rc = dstage_reserve(ctx, p);
   if (rc) return rc;
-  char* st = (char*)ctx->dstage;
-  uint64_t* dpcs = (uint64_t*)st;
-  uint64_t* dco = (uint64_t*)(st + bp);
-  uint64_t* dcov_off = (uint64_t*)(st + bp + bo);
-  uint32_t* dcov = (uint32_t*)(st + bp + 2 * bo);
-  if (npcs) SG_HIP(hipMemcpyAsync(dpcs, pcs, npcs * 8, hipMemcpyHostToDevice, ctx->stream));
-  SG_HIP(hipMemcpyAsync(dco, call_off, (ncalls + 1) * 8, hipMemcpyHostToDevice, ctx->stream));
+  uint64_t* dpcs = dstage_at<uint64_t>(ctx, o_pcs);
+  uint64_t* dco = dstage_at<uint64_t>(ctx, o_co);
+  uint64_t* dcov_off = dstage_at<uint64_t>(ctx, o_cov_off);
+  uint32_t* dcov = dstage_at<uint32_t>(ctx, o_cov);
+  if ((rc = upload(ctx, dpcs, pcs, npcs * 8))) return rc;
+  if ((rc = upload(ctx, dco, call_off, (ncalls + 1) * 8))) return rc;
   rc = exec_cover(ctx, dpcs, dco, ncalls, npcs, dedup, dcov_off, ccap ? dcov : nullptr, ccap);
   if (rc) return rc;
-  SG_HIP(hipMemcpyAsync(cov_off, dcov_off, (ncalls + 1) * 8, hipMemcpyDeviceToHost, ctx->stream));
-  SG_HIP(hipStreamSynchronize(ctx->stream));
-  if (cov_off[ncalls] && cov_off[ncalls] <= cov_cap)
-    SG_HIP(hipMemcpyAsync(cov, dcov, cov_off[ncalls] * 4, hipMemcpyDeviceToHost, ctx->stream));
-  SG_HIP(hipStreamSynchronize(ctx->stream));
-  return SG_OK;
+  return csr_download(ctx, cov_off, dcov_off, ncalls, cov, dcov, 4, cov_cap);
 }
 
 }  // extern "C"

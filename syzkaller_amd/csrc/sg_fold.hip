@@ -27,11 +27,6 @@
 #include <algorithm>
 
 namespace sg {
-
-int merge_dev(sg_ctx* ctx, int op, const uint32_t* da, const uint32_t* db, uint32_t* dout, const uint64_t* a_beg,
-              const uint64_t* a_len, const uint64_t* b_beg, const uint64_t* b_len, const uint64_t* out_beg,
-              size_t npair, uint64_t* out_len);
-
 namespace {
 
 // dst[dst_off[k] ..] = src[src_beg[k] .. + len[k]), one wave per segment
@@ -608,13 +603,13 @@ static int fold_sorted(sg_ctx* ctx, const uint32_t* vals, const uint64_t* off, s
   const uint32_t gb = bits_for(ngroups - 1);
   if (gb + 32 > 64) return SG_EOVERFLOW_FOLD;
   // inputs: values, offsets, groups (device staging)
-  const size_t b_v = (N * 4 + 255) & ~size_t(255), b_o = ((n + 1) * 8 + 255) & ~size_t(255),
-               b_g = (n * 4 + 255) & ~size_t(255);
-  int rc = dstage_reserve(ctx, b_v + b_o + b_g + 256);
+  WsPlan sp;
+  const size_t o_v = sp.add(N * 4), o_off = sp.add((n + 1) * 8), o_grp = sp.add(n * 4);
+  int rc = dstage_reserve(ctx, sp);
   if (rc) return rc;
-  uint32_t* dv = (uint32_t*)ctx->dstage;
-  uint64_t* doff = (uint64_t*)((char*)ctx->dstage + b_v);
-  uint32_t* dgrp = group ? (uint32_t*)((char*)ctx->dstage + b_v + b_o) : nullptr;
+  uint32_t* dv = dstage_at<uint32_t>(ctx, o_v);
+  uint64_t* doff = dstage_at<uint64_t>(ctx, o_off);
+  uint32_t* dgrp = group ? dstage_at<uint32_t>(ctx, o_grp) : nullptr;
   // workspace: keys (2 buffers), keep flags, their scan, group first indices / positions, max j
   WsPlan p;
   const uint64_t ntile = (N + kFuTile - 1) / kFuTile;
@@ -791,11 +786,14 @@ int sg_union_fold(sg_ctx* ctx, const uint32_t* vals, const uint64_t* off, size_t
   // the lists of each group, in input order (the order does not change the result)
   std::vector<std::vector<Item>> items(ngroups);
   for (size_t k = 0; k < n; k++) items[group ? group[k] : 0].push_back({off[k], off[k + 1] - off[k]});
-  // two ping-pong buffers of N values: a level's results never exceed its inputs
-  const size_t b_v = (N * 4 + 255) & ~size_t(255);
-  rc = dstage_reserve(ctx, 2 * b_v + 4 * ((ngroups + 1) * 8 + 256));
+  // two ping-pong buffers of N values (a level's results never exceed its
+  // inputs), and the final pack's begins, lengths and offsets
+  WsPlan sp;
+  const size_t o_buf0 = sp.add(N * 4), o_buf1 = sp.add(N * 4), o_beg = sp.add((ngroups + 1) * 8),
+               o_len = sp.add((ngroups + 1) * 8), o_off = sp.add((ngroups + 1) * 8);
+  rc = dstage_reserve(ctx, sp);
   if (rc) return rc;
-  uint32_t* buf[2] = {(uint32_t*)ctx->dstage, (uint32_t*)((char*)ctx->dstage + b_v)};
+  uint32_t* buf[2] = {dstage_at<uint32_t>(ctx, o_buf0), dstage_at<uint32_t>(ctx, o_buf1)};
   SG_HIP(hipMemcpyAsync(buf[0], vals, N * 4, hipMemcpyHostToDevice, ctx->stream));
   int cur = 0;
   std::vector<uint64_t> ab, al, bb, bl, ob, ol;
@@ -851,9 +849,8 @@ int sg_union_fold(sg_ctx* ctx, const uint32_t* vals, const uint64_t* off, size_t
   }
   if (out_off[ngroups] == 0) return SG_OK;
   if (!out_vals) return SG_EINVAL;
-  const size_t b_o = ((ngroups + 1) * 8 + 255) & ~size_t(255);
-  uint64_t* dmeta = (uint64_t*)((char*)ctx->dstage + 2 * b_v);
-  uint64_t *dbeg = dmeta, *dlen = (uint64_t*)((char*)dmeta + b_o), *doff = (uint64_t*)((char*)dmeta + 2 * b_o);
+  uint64_t *dbeg = dstage_at<uint64_t>(ctx, o_beg), *dlen = dstage_at<uint64_t>(ctx, o_len),
+           *doff = dstage_at<uint64_t>(ctx, o_off);
   SG_HIP(hipMemcpyAsync(dbeg, beg.data(), ngroups * 8, hipMemcpyHostToDevice, ctx->stream));
   SG_HIP(hipMemcpyAsync(dlen, len.data(), ngroups * 8, hipMemcpyHostToDevice, ctx->stream));
   SG_HIP(hipMemcpyAsync(doff, out_off, ngroups * 8, hipMemcpyHostToDevice, ctx->stream));

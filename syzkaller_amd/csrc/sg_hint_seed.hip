@@ -191,26 +191,23 @@ static int hk_limits(uint64_t ncalls, uint64_t nrecs, uint64_t nvals) {
   return ec_limits(ncalls, nrecs);
 }
 
-// The intermediates of the fused call, in the device staging buffer
+// The intermediates of the fused call: regions of the caller's staging plan
 struct HkStage {
-  size_t comp_off, pair_off, pairs, total;
-  HkStage(size_t base, uint64_t ncalls, uint64_t nrecs) {
-    auto al = [](size_t b) { return (b + 255) & ~size_t(255); };
-    comp_off = base;
-    pair_off = comp_off + al((ncalls + 1) * 8);
-    pairs = pair_off + al((ncalls + 1) * 8);
-    total = pairs + al(2 * nrecs * 16 + 16);  // 2 nrecs pairs always suffice
-  }
+  size_t comp_off, pair_off, pairs;
+  HkStage(WsPlan& p, uint64_t ncalls, uint64_t nrecs)
+      : comp_off(p.add((ncalls + 1) * 8)),
+        pair_off(p.add((ncalls + 1) * 8)),
+        pairs(p.add(2 * nrecs * 16 + 16)) {}  // 2 nrecs pairs always suffice
 };
 
-// The three stages; ctx lock held, the device ensured, st: the staging buffer
+// The three stages; ctx lock held, the device ensured, the staging plan of s reserved
 static int hints_from_kcov(sg_ctx* ctx, const uint64_t* d_recs, const uint64_t* d_call_off, uint64_t ncalls,
                            uint64_t nrecs, const uint64_t* d_val_off, const uint64_t* d_vals, uint64_t nvals,
-                           int32_t* d_status, char* st, const HkStage& s, uint64_t* d_rep_off, uint64_t* d_reps,
-                           uint64_t cap, bool reps_in_ws, uint64_t** ws_reps) {
-  uint64_t* d_comp_off = (uint64_t*)(st + s.comp_off);
-  uint64_t* d_pair_off = (uint64_t*)(st + s.pair_off);
-  uint64_t* d_pairs = (uint64_t*)(st + s.pairs);
+                           int32_t* d_status, const HkStage& s, uint64_t* d_rep_off, uint64_t* d_reps, uint64_t cap,
+                           bool reps_in_ws, uint64_t** ws_reps) {
+  uint64_t* d_comp_off = dstage_at<uint64_t>(ctx, s.comp_off);
+  uint64_t* d_pair_off = dstage_at<uint64_t>(ctx, s.pair_off);
+  uint64_t* d_pairs = dstage_at<uint64_t>(ctx, s.pairs);
   EcRaw raw;
   int rc = exec_comps(ctx, d_recs, d_call_off, ncalls, nrecs, d_comp_off, nullptr, 0, nullptr, nullptr, 0, &raw);
   if (rc) return rc;
@@ -253,37 +250,30 @@ int sg_comps_pairs(sg_ctx* ctx, const uint64_t* comp_off, const uint64_t* comps,
   if (!ctx || !comp_off || !status || !pair_off || (cap && !pairs)) return SG_EINVAL;
   if (ncalls >= (1ull << 31)) return cp_limits(ncalls, 0);
   const uint64_t ncomps = comp_off[ncalls];
-  if (comp_off[0] != 0 || (ncomps && !comps)) return SG_EINVAL;
-  for (size_t c = 0; c < ncalls; c++)
-    if (comp_off[c + 1] < comp_off[c]) return SG_EINVAL;
+  if (!offsets_ok(comp_off, ncalls) || (ncomps && !comps)) return SG_EINVAL;
   int rc = cp_limits(ncalls, ncomps);
   if (rc) return rc;
   // 2 ncomps pairs always suffice: a smaller cap is staged as it is
   const uint64_t pcap = cap < 2 * ncomps ? cap : 2 * ncomps;
-  auto al = [](size_t b) { return (b + 255) & ~size_t(255); };
-  const size_t bo = al((ncalls + 1) * 8), bc = al(ncomps * 24 + 24), bs = al(ncalls * 4 + 4), bp = al(pcap * 16 + 16);
+  WsPlan p;
+  const size_t o_co = p.add((ncalls + 1) * 8), o_po = p.add((ncalls + 1) * 8), o_c = p.add(ncomps * 24 + 24),
+               o_st = p.add(ncalls * 4 + 4), o_p = p.add(pcap * 16 + 16);
   std::lock_guard<std::mutex> g(ctx->mu);
   rc = ensure_device(ctx);
   if (rc) return rc;
-  rc = dstage_reserve(ctx, 2 * bo + bc + bs + bp + 256);
+  rc = dstage_reserve(ctx, p);
   if (rc) return rc;
-  char* st = (char*)ctx->dstage;
-  uint64_t* dco = (uint64_t*)st;
-  uint64_t* dpo = (uint64_t*)(st + bo);
-  uint64_t* dc = (uint64_t*)(st + 2 * bo);
-  int32_t* dst = (int32_t*)(st + 2 * bo + bc);
-  uint64_t* dp = (uint64_t*)(st + 2 * bo + bc + bs);
-  SG_HIP(hipMemcpyAsync(dco, comp_off, (ncalls + 1) * 8, hipMemcpyHostToDevice, ctx->stream));
-  if (ncomps) SG_HIP(hipMemcpyAsync(dc, comps, ncomps * 24, hipMemcpyHostToDevice, ctx->stream));
+  uint64_t* dco = dstage_at<uint64_t>(ctx, o_co);
+  uint64_t* dpo = dstage_at<uint64_t>(ctx, o_po);
+  uint64_t* dc = dstage_at<uint64_t>(ctx, o_c);
+  int32_t* dst = dstage_at<int32_t>(ctx, o_st);
+  uint64_t* dp = dstage_at<uint64_t>(ctx, o_p);
+  if ((rc = upload(ctx, dco, comp_off, (ncalls + 1) * 8))) return rc;
+  if ((rc = upload(ctx, dc, comps, ncomps * 24))) return rc;
   rc = comps_pairs_csr(ctx, dco, dc, ncalls, ncomps, dst, dpo, pcap ? dp : nullptr, pcap);
   if (rc) return rc;
-  SG_HIP(hipMemcpyAsync(pair_off, dpo, (ncalls + 1) * 8, hipMemcpyDeviceToHost, ctx->stream));
   if (ncalls) SG_HIP(hipMemcpyAsync(status, dst, ncalls * 4, hipMemcpyDeviceToHost, ctx->stream));
-  SG_HIP(hipStreamSynchronize(ctx->stream));
-  if (pair_off[ncalls] && pair_off[ncalls] <= cap)
-    SG_HIP(hipMemcpyAsync(pairs, dp, pair_off[ncalls] * 16, hipMemcpyDeviceToHost, ctx->stream));
-  SG_HIP(hipStreamSynchronize(ctx->stream));
-  return SG_OK;
+  return csr_download(ctx, pair_off, dpo, ncalls, pairs, dp, 16, cap);
 }
 
 int sg_hints_from_kcov_dev(sg_ctx* ctx, const uint64_t* d_recs, const uint64_t* d_call_off, uint64_t ncalls,
@@ -297,11 +287,12 @@ int sg_hints_from_kcov_dev(sg_ctx* ctx, const uint64_t* d_recs, const uint64_t* 
   std::lock_guard<std::mutex> g(ctx->mu);
   rc = ensure_device(ctx);
   if (rc) return rc;
-  const HkStage s(0, ncalls, nrecs);
-  rc = dstage_reserve(ctx, s.total + 256);  // grow-only: waits only when it has to grow
+  WsPlan p;
+  const HkStage s(p, ncalls, nrecs);
+  rc = dstage_reserve(ctx, p);  // grow-only: waits only when it has to grow
   if (rc) return rc;
-  return hints_from_kcov(ctx, d_recs, d_call_off, ncalls, nrecs, d_val_off, d_vals, nvals, d_status, (char*)ctx->dstage,
-                         s, d_rep_off, d_reps, cap, false, nullptr);
+  return hints_from_kcov(ctx, d_recs, d_call_off, ncalls, nrecs, d_val_off, d_vals, nvals, d_status, s, d_rep_off,
+                         d_reps, cap, false, nullptr);
 }
 
 int sg_hints_from_kcov(sg_ctx* ctx, const uint64_t* recs, const uint64_t* call_off, size_t ncalls,
@@ -310,41 +301,34 @@ int sg_hints_from_kcov(sg_ctx* ctx, const uint64_t* recs, const uint64_t* call_o
   if (!ctx || !call_off || !val_off || !status || !rep_off || (cap && !reps)) return SG_EINVAL;
   if (ncalls >= (1ull << 31)) return hk_limits(ncalls, 0, 0);
   const uint64_t nrecs = call_off[ncalls], nvals = val_off[ncalls];
-  if (call_off[0] != 0 || val_off[0] != 0 || (nrecs && !recs) || (nvals && !vals)) return SG_EINVAL;
-  for (size_t c = 0; c < ncalls; c++)
-    if (call_off[c + 1] < call_off[c] || val_off[c + 1] < val_off[c]) return SG_EINVAL;
+  if (!offsets_ok(call_off, ncalls) || !offsets_ok(val_off, ncalls) || (nrecs && !recs) || (nvals && !vals))
+    return SG_EINVAL;
   int rc = hk_limits(ncalls, nrecs, nvals);
   if (rc) return rc;
-  auto al = [](size_t b) { return (b + 255) & ~size_t(255); };
-  const size_t br = al(nrecs * 32 + 32), bo = al((ncalls + 1) * 8), bv = al(nvals * 8 + 8), bs = al(ncalls * 4 + 4),
-               bro = al((nvals + 1) * 8);
-  const HkStage s(br + 2 * bo + bv + bs + bro, ncalls, nrecs);
+  WsPlan p;
+  const size_t o_recs = p.add(nrecs * 32 + 32), o_co = p.add((ncalls + 1) * 8), o_vo = p.add((ncalls + 1) * 8),
+               o_v = p.add(nvals * 8 + 8), o_st = p.add(ncalls * 4 + 4), o_ro = p.add((nvals + 1) * 8);
+  const HkStage s(p, ncalls, nrecs);
   std::lock_guard<std::mutex> g(ctx->mu);
   rc = ensure_device(ctx);
   if (rc) return rc;
-  rc = dstage_reserve(ctx, s.total + 256);
+  rc = dstage_reserve(ctx, p);
   if (rc) return rc;
-  char* st = (char*)ctx->dstage;
-  uint64_t* drecs = (uint64_t*)st;
-  uint64_t* dco = (uint64_t*)(st + br);
-  uint64_t* dvo = (uint64_t*)(st + br + bo);
-  uint64_t* dv = (uint64_t*)(st + br + 2 * bo);
-  int32_t* dst = (int32_t*)(st + br + 2 * bo + bv);
-  uint64_t* dro = (uint64_t*)(st + br + 2 * bo + bv + bs);
-  if (nrecs) SG_HIP(hipMemcpyAsync(drecs, recs, nrecs * 32, hipMemcpyHostToDevice, ctx->stream));
-  SG_HIP(hipMemcpyAsync(dco, call_off, (ncalls + 1) * 8, hipMemcpyHostToDevice, ctx->stream));
-  SG_HIP(hipMemcpyAsync(dvo, val_off, (ncalls + 1) * 8, hipMemcpyHostToDevice, ctx->stream));
-  if (nvals) SG_HIP(hipMemcpyAsync(dv, vals, nvals * 8, hipMemcpyHostToDevice, ctx->stream));
+  uint64_t* drecs = dstage_at<uint64_t>(ctx, o_recs);
+  uint64_t* dco = dstage_at<uint64_t>(ctx, o_co);
+  uint64_t* dvo = dstage_at<uint64_t>(ctx, o_vo);
+  uint64_t* dv = dstage_at<uint64_t>(ctx, o_v);
+  int32_t* dst = dstage_at<int32_t>(ctx, o_st);
+  uint64_t* dro = dstage_at<uint64_t>(ctx, o_ro);
+  if ((rc = upload(ctx, drecs, recs, nrecs * 32))) return rc;
+  if ((rc = upload(ctx, dco, call_off, (ncalls + 1) * 8))) return rc;
+  if ((rc = upload(ctx, dvo, val_off, (ncalls + 1) * 8))) return rc;
+  if ((rc = upload(ctx, dv, vals, nvals * 8))) return rc;
   uint64_t* dreps = nullptr;
-  rc = hints_from_kcov(ctx, drecs, dco, ncalls, nrecs, dvo, dv, nvals, dst, st, s, dro, nullptr, cap, true, &dreps);
+  rc = hints_from_kcov(ctx, drecs, dco, ncalls, nrecs, dvo, dv, nvals, dst, s, dro, nullptr, cap, true, &dreps);
   if (rc) return rc;
-  SG_HIP(hipMemcpyAsync(rep_off, dro, (nvals + 1) * 8, hipMemcpyDeviceToHost, ctx->stream));
   if (ncalls) SG_HIP(hipMemcpyAsync(status, dst, ncalls * 4, hipMemcpyDeviceToHost, ctx->stream));
-  SG_HIP(hipStreamSynchronize(ctx->stream));
-  if (rep_off[nvals] && rep_off[nvals] <= cap && dreps)
-    SG_HIP(hipMemcpyAsync(reps, dreps, rep_off[nvals] * 8, hipMemcpyDeviceToHost, ctx->stream));
-  SG_HIP(hipStreamSynchronize(ctx->stream));
-  return SG_OK;
+  return csr_download(ctx, rep_off, dro, nvals, reps, dreps, 8, cap);  // (dreps: set whenever a replacer was written)
 }
 
 }  // extern "C"

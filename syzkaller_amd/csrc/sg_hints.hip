@@ -754,38 +754,36 @@ int sg_ipc_comps(sg_ctx* ctx, const uint32_t* out, const uint64_t* out_off, cons
       return SG_EINVAL;
   // a comparison is at least 3 words and yields at most 2 pairs
   const uint64_t bound = 2 * ((nwords + 2) / 3);
-  auto al = [](size_t b) { return (b + 255) & ~size_t(255); };
-  const size_t bw = al(nwords * 4 + 4), bo = al((nprog + 1) * 8), br8 = al((nrec + 1) * 8), br4 = al(nrec * 4 + 4),
-               bp = al(nprog * 4 + 4), bpairs = al(bound * 16 + 16);
-  char* st = nullptr;
+  WsPlan p;
+  const size_t o_w = p.add(nwords * 4 + 4), o_oo = p.add((nprog + 1) * 8), o_co = p.add((nprog + 1) * 8),
+               o_po = p.add((nrec + 1) * 8), o_num = p.add(nrec * 4 + 4), o_st = p.add(nprog * 4 + 4),
+               o_pairs = p.add(bound * 16 + 16);
+  uint32_t *dw, *dnum;
+  uint64_t *doo, *dco, *dpo, *dpairs;
+  int32_t* dst;
   {
     std::lock_guard<std::mutex> g(ctx->mu);
     int rc = ensure_device(ctx);
     if (rc) return rc;
-    rc = dstage_reserve(ctx, bw + 2 * bo + br8 + br4 + bp + bpairs + 256);
+    rc = dstage_reserve(ctx, p);
     if (rc) return rc;
-    st = (char*)ctx->dstage;
+    dw = dstage_at<uint32_t>(ctx, o_w);
+    doo = dstage_at<uint64_t>(ctx, o_oo);
+    dco = dstage_at<uint64_t>(ctx, o_co);
+    dpo = dstage_at<uint64_t>(ctx, o_po);
+    dnum = dstage_at<uint32_t>(ctx, o_num);
+    dst = dstage_at<int32_t>(ctx, o_st);
+    dpairs = dstage_at<uint64_t>(ctx, o_pairs);
   }
-  uint32_t* dw = (uint32_t*)st;
-  uint64_t* doo = (uint64_t*)(st + bw);
-  uint64_t* dco = (uint64_t*)(st + bw + bo);
-  uint64_t* dpo = (uint64_t*)(st + bw + 2 * bo);
-  uint32_t* dnum = (uint32_t*)(st + bw + 2 * bo + br8);
-  int32_t* dst = (int32_t*)(st + bw + 2 * bo + br8 + br4);
-  uint64_t* dpairs = (uint64_t*)(st + bw + 2 * bo + br8 + br4 + bp);
-  if (nwords) SG_HIP(hipMemcpyAsync(dw, out, nwords * 4, hipMemcpyHostToDevice, ctx->stream));
-  SG_HIP(hipMemcpyAsync(doo, out_off, (nprog + 1) * 8, hipMemcpyHostToDevice, ctx->stream));
-  SG_HIP(hipMemcpyAsync(dco, call_off, (nprog + 1) * 8, hipMemcpyHostToDevice, ctx->stream));
-  if (call_nums && nrec) SG_HIP(hipMemcpyAsync(dnum, call_nums, nrec * 4, hipMemcpyHostToDevice, ctx->stream));
-  int rc = sg_ipc_comps_dev(ctx, dw, doo, dco, call_nums ? dnum : nullptr, nprog, nrec, dst, dpo, dpairs, bound);
+  int rc;
+  if ((rc = upload(ctx, dw, out, nwords * 4))) return rc;
+  if ((rc = upload(ctx, doo, out_off, (nprog + 1) * 8))) return rc;
+  if ((rc = upload(ctx, dco, call_off, (nprog + 1) * 8))) return rc;
+  if (call_nums && (rc = upload(ctx, dnum, call_nums, nrec * 4))) return rc;
+  rc = sg_ipc_comps_dev(ctx, dw, doo, dco, call_nums ? dnum : nullptr, nprog, nrec, dst, dpo, dpairs, bound);
   if (rc) return rc;
-  SG_HIP(hipMemcpyAsync(pair_off, dpo, (nrec + 1) * 8, hipMemcpyDeviceToHost, ctx->stream));
   if (nprog) SG_HIP(hipMemcpyAsync(status, dst, nprog * 4, hipMemcpyDeviceToHost, ctx->stream));
-  SG_HIP(hipStreamSynchronize(ctx->stream));
-  if (pair_off[nrec] && pair_off[nrec] <= cap)
-    SG_HIP(hipMemcpyAsync(pairs, dpairs, pair_off[nrec] * 16, hipMemcpyDeviceToHost, ctx->stream));
-  SG_HIP(hipStreamSynchronize(ctx->stream));
-  return SG_OK;
+  return csr_download(ctx, pair_off, dpo, nrec, pairs, dpairs, 16, cap);
 }
 
 int sg_hints_replacers_dev(sg_ctx* ctx, const uint64_t* d_pair_off, const uint64_t* d_pairs, uint64_t nrec,
@@ -803,40 +801,34 @@ int sg_hints_replacers(sg_ctx* ctx, const uint64_t* pair_off, const uint64_t* pa
                        const uint64_t* val_off, const uint64_t* vals, uint64_t* rep_off, uint64_t* reps, size_t cap) {
   if (!ctx || !pair_off || !val_off || !rep_off || (cap && !reps)) return SG_EINVAL;
   const uint64_t npairs = pair_off[nrec], nvals = val_off[nrec];
-  if (pair_off[0] != 0 || val_off[0] != 0 || (npairs && !pairs) || (nvals && !vals)) return SG_EINVAL;
-  for (size_t r = 0; r < nrec; r++)
-    if (pair_off[r + 1] < pair_off[r] || val_off[r + 1] < val_off[r]) return SG_EINVAL;
+  if (!offsets_ok(pair_off, nrec) || !offsets_ok(val_off, nrec) || (npairs && !pairs) || (nvals && !vals))
+    return SG_EINVAL;
   if (npairs >= (1ull << 32) || nvals >= (1ull << 32)) {
     set_error("sg_hints_replacers: %llu pairs, %llu value slots (the limit of each is 2^32 - 1)",
               (unsigned long long)npairs, (unsigned long long)nvals);
     return SG_EINVAL;
   }
-  auto al = [](size_t b) { return (b + 255) & ~size_t(255); };
-  const size_t br = al((nrec + 1) * 8), bp = al(npairs * 16 + 16), bv = al(nvals * 8 + 8), bro = al((nvals + 1) * 8);
+  WsPlan p;
+  const size_t o_po = p.add((nrec + 1) * 8), o_vo = p.add((nrec + 1) * 8), o_p = p.add(npairs * 16 + 16),
+               o_v = p.add(nvals * 8 + 8), o_ro = p.add((nvals + 1) * 8);
   std::lock_guard<std::mutex> g(ctx->mu);
   int rc = ensure_device(ctx);
   if (rc) return rc;
-  rc = dstage_reserve(ctx, 2 * br + bp + bv + bro + 256);
+  rc = dstage_reserve(ctx, p);
   if (rc) return rc;
-  char* st = (char*)ctx->dstage;
-  uint64_t* dpo = (uint64_t*)st;
-  uint64_t* dvo = (uint64_t*)(st + br);
-  uint64_t* dp = (uint64_t*)(st + 2 * br);
-  uint64_t* dv = (uint64_t*)(st + 2 * br + bp);
-  uint64_t* dro = (uint64_t*)(st + 2 * br + bp + bv);
-  SG_HIP(hipMemcpyAsync(dpo, pair_off, (nrec + 1) * 8, hipMemcpyHostToDevice, ctx->stream));
-  SG_HIP(hipMemcpyAsync(dvo, val_off, (nrec + 1) * 8, hipMemcpyHostToDevice, ctx->stream));
-  if (npairs) SG_HIP(hipMemcpyAsync(dp, pairs, npairs * 16, hipMemcpyHostToDevice, ctx->stream));
-  if (nvals) SG_HIP(hipMemcpyAsync(dv, vals, nvals * 8, hipMemcpyHostToDevice, ctx->stream));
-  uint64_t* dreps = nullptr;
+  uint64_t* dpo = dstage_at<uint64_t>(ctx, o_po);
+  uint64_t* dvo = dstage_at<uint64_t>(ctx, o_vo);
+  uint64_t* dp = dstage_at<uint64_t>(ctx, o_p);
+  uint64_t* dv = dstage_at<uint64_t>(ctx, o_v);
+  uint64_t* dro = dstage_at<uint64_t>(ctx, o_ro);
+  if ((rc = upload(ctx, dpo, pair_off, (nrec + 1) * 8))) return rc;
+  if ((rc = upload(ctx, dvo, val_off, (nrec + 1) * 8))) return rc;
+  if ((rc = upload(ctx, dp, pairs, npairs * 16))) return rc;
+  if ((rc = upload(ctx, dv, vals, nvals * 8))) return rc;
+  uint64_t* dreps = nullptr;  // (set whenever a replacer was written)
   rc = hints_replacers(ctx, dpo, dp, nrec, dvo, dv, nvals, dro, nullptr, cap, true, &dreps);
   if (rc) return rc;
-  SG_HIP(hipMemcpyAsync(rep_off, dro, (nvals + 1) * 8, hipMemcpyDeviceToHost, ctx->stream));
-  SG_HIP(hipStreamSynchronize(ctx->stream));
-  if (rep_off[nvals] && rep_off[nvals] <= cap && dreps)
-    SG_HIP(hipMemcpyAsync(reps, dreps, rep_off[nvals] * 8, hipMemcpyDeviceToHost, ctx->stream));
-  SG_HIP(hipStreamSynchronize(ctx->stream));
-  return SG_OK;
+  return csr_download(ctx, rep_off, dro, nvals, reps, dreps, 8, cap);
 }
 
 }  // extern "C"

@@ -110,8 +110,8 @@ int host_pipeline(sg_ctx* ctx, uint32_t* mwords, uint32_t* nwords, const uint32_
     max_r = std::max(max_r, r1 - r0);
     r0 = r1;
   }
-  const size_t b_vals = (max_n * 4 + 255) & ~size_t(255), b_off = ((max_r + 1) * 8 + 255) & ~size_t(255);
-  const size_t b_slot = b_vals + b_off, b_flag = (nrec + 256) & ~size_t(255);
+  const size_t b_vals = align256(max_n * 4), b_off = align256((max_r + 1) * 8);
+  const size_t b_slot = b_vals + b_off, b_flag = align256(nrec + 1);
   std::lock_guard<std::mutex> g(ctx->mu);
   int rc = ensure_device(ctx);
   if (rc) return rc;

@@ -12,6 +12,7 @@
 #include <vector>
 
 #include "../../include/syzsig.h"
+#include "sg_plan.h"
 
 namespace sg {
 
@@ -211,22 +212,27 @@ int hip_fail(hipError_t e, const char* what);
   } while (0)
 
 int ensure_device(sg_ctx* ctx);
-// Carve `n` bump-allocated regions out of the workspace (each 256-B aligned).
-struct WsPlan {
-  size_t off[32];
-  int n = 0;
-  size_t total = 0;
-  size_t add(size_t bytes) {
-    size_t o = total;
-    off[n++] = o;
-    total += (bytes + 255) & ~size_t(255);
-    return o;
-  }
-};
+// Grow-only buffers.  The plan forms (WsPlan, sg_plan.h) reserve plan.total
+// and refuse a plan with more regions than it records.
 int ws_reserve(sg_ctx* ctx, size_t bytes);
+int ws_reserve(sg_ctx* ctx, const WsPlan& plan);
 inline void* ws_at(sg_ctx* ctx, size_t off) { return (char*)ctx->ws + off; }
 int pin_reserve(sg_ctx* ctx, size_t bytes);
+// The host forms' staging: plan the regions, reserve once, then bind each
+// pointer from the offset WsPlan::add returned (the buffer may move in the
+// reserve, never after it).
 int dstage_reserve(sg_ctx* ctx, size_t bytes);
+int dstage_reserve(sg_ctx* ctx, const WsPlan& plan);
+template <typename T>
+inline T* dstage_at(sg_ctx* ctx, size_t off) {
+  return (T*)((char*)ctx->dstage + off);
+}
+// Host -> device on ctx->stream; nothing for zero bytes.
+int upload(sg_ctx* ctx, void* d_dst, const void* h_src, size_t bytes);
+// CSR download on ctx->stream: the n + 1 offsets, a wait, then the off[n] *
+// elem payload bytes when there are any and off[n] <= cap, and a second wait.
+int csr_download(sg_ctx* ctx, uint64_t* h_off, const uint64_t* d_off, uint64_t n, void* h_vals, const void* d_vals,
+                 size_t elem, uint64_t cap);
 // Reserve `nkeys` first-owner keys: returns key_lo such that keys
 // key_lo .. key_lo+nkeys-1 are below every key already stored in the table.
 int owner_keys(sg_ctx* ctx, uint64_t nkeys, uint32_t* key_lo);
@@ -370,6 +376,15 @@ int ec_fill(sg_ctx* ctx, const uint64_t* call_off, uint64_t ncalls, uint64_t nre
             const uint64_t* gbase, uint64_t ng, uint32_t* gidx, uint32_t* gcall);
 int ec_call_first(sg_ctx* ctx, const EcGen& g, const uint32_t* gcall, const uint32_t* rank, uint64_t ncalls,
                   uint64_t* first, uint64_t** sorted);
+// Canonicalize of device segments in place: off (host, nseg + 1), out_len
+// (host) the canonical lengths; and the batched merge of device-resident
+// lists, pair k da[a_beg[k] .. + a_len[k]) op db[b_beg[k] .. + b_len[k]) into
+// dout[out_beg[k] ..), the pair descriptors and out_len host arrays
+// (sg_merge.hip; ctx lock held; both wait for their lengths).
+int canonicalize_dev(sg_ctx* ctx, uint32_t* d_vals, const uint64_t* off, uint64_t nseg, uint64_t* out_len);
+int merge_dev(sg_ctx* ctx, int op, const uint32_t* da, const uint32_t* db, uint32_t* dout, const uint64_t* a_beg,
+              const uint64_t* a_len, const uint64_t* b_beg, const uint64_t* b_len, const uint64_t* out_beg,
+              size_t npair, uint64_t* out_len);
 // The join and the sorts behind sg_hints_replacers* (sg_hints.hip; ctx lock
 // held).  Plans the context workspace from offset 0 and may move it.  With
 // reps_in_ws the replacers go to a workspace buffer of min(cap, candidates)

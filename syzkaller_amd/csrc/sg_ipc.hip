@@ -235,41 +235,43 @@ int sg_ipc_parse(sg_ctx* ctx, const uint32_t* out, const uint64_t* out_off, cons
                  uint64_t* sig_off, uint32_t* sig_vals, uint64_t* cov_off, uint32_t* cov_vals) {
   if (!ctx || !out_off || !call_off || !sig_off || (!cov_off != !cov_vals)) return SG_EINVAL;
   const uint64_t nwords = out_off[nprog], nrec = call_off[nprog];
-  if (out_off[0] != 0 || call_off[0] != 0 || (nwords && (!out || !sig_vals || (cov_off && !cov_vals))) ||
-      (nprog && !status) || (nrec && (!err || !fault)))
+  if (!offsets_ok(out_off, nprog) || !offsets_ok(call_off, nprog) ||
+      (nwords && (!out || !sig_vals || (cov_off && !cov_vals))) || (nprog && !status) || (nrec && (!err || !fault)))
     return SG_EINVAL;
-  for (size_t q = 0; q < nprog; q++)
-    if (out_off[q + 1] < out_off[q] || call_off[q + 1] < call_off[q]) return SG_EINVAL;
-  auto al = [](size_t b) { return (b + 255) & ~size_t(255); };
-  const size_t bw = al(nwords * 4 + 4), bo = al((nprog + 1) * 8), br8 = al((nrec + 1) * 8), br4 = al(nrec * 4 + 4),
-               br1 = al(nrec + 1), bp = al(nprog * 4 + 4);
-  char* st = nullptr;
+  WsPlan p;
+  const size_t o_w = p.add(nwords * 4 + 4), o_sv = p.add(nwords * 4 + 4), o_cv = p.add(nwords * 4 + 4),
+               o_oo = p.add((nprog + 1) * 8), o_co = p.add((nprog + 1) * 8), o_err = p.add((nrec + 1) * 8),
+               o_so = p.add((nrec + 1) * 8), o_cvo = p.add((nrec + 1) * 8), o_num = p.add(nrec * 4 + 4),
+               o_fi = p.add(nrec + 1), o_st = p.add(nprog * 4 + 4);
+  uint32_t *dw, *dsv, *dcv, *dnum;
+  uint64_t *doo, *dco, *derr, *dso, *dcvo;
+  uint8_t* dfi;
+  int32_t* dst;
   {
     std::lock_guard<std::mutex> g(ctx->mu);
     int rc = ensure_device(ctx);
     if (rc) return rc;
-    rc = dstage_reserve(ctx, 3 * bw + 2 * bo + 3 * br8 + br4 + br1 + bp + 256);
+    rc = dstage_reserve(ctx, p);
     if (rc) return rc;
-    st = (char*)ctx->dstage;
+    dw = dstage_at<uint32_t>(ctx, o_w);
+    dsv = dstage_at<uint32_t>(ctx, o_sv);
+    dcv = dstage_at<uint32_t>(ctx, o_cv);
+    doo = dstage_at<uint64_t>(ctx, o_oo);
+    dco = dstage_at<uint64_t>(ctx, o_co);
+    derr = dstage_at<uint64_t>(ctx, o_err);
+    dso = dstage_at<uint64_t>(ctx, o_so);
+    dcvo = dstage_at<uint64_t>(ctx, o_cvo);
+    dnum = dstage_at<uint32_t>(ctx, o_num);
+    dfi = dstage_at<uint8_t>(ctx, o_fi);
+    dst = dstage_at<int32_t>(ctx, o_st);
   }
-  uint32_t* dw = (uint32_t*)st;
-  uint32_t* dsv = (uint32_t*)(st + bw);
-  uint32_t* dcv = (uint32_t*)(st + 2 * bw);
-  char* q = st + 3 * bw;
-  uint64_t* doo = (uint64_t*)q;
-  uint64_t* dco = (uint64_t*)(q + bo);
-  uint64_t* derr = (uint64_t*)(q + 2 * bo);
-  uint64_t* dso = (uint64_t*)(q + 2 * bo + br8);
-  uint64_t* dcvo = (uint64_t*)(q + 2 * bo + 2 * br8);
-  uint32_t* dnum = (uint32_t*)(q + 2 * bo + 3 * br8);
-  uint8_t* dfi = (uint8_t*)(q + 2 * bo + 3 * br8 + br4);
-  int32_t* dst = (int32_t*)(q + 2 * bo + 3 * br8 + br4 + br1);
-  if (nwords) SG_HIP(hipMemcpyAsync(dw, out, nwords * 4, hipMemcpyHostToDevice, ctx->stream));
-  SG_HIP(hipMemcpyAsync(doo, out_off, (nprog + 1) * 8, hipMemcpyHostToDevice, ctx->stream));
-  SG_HIP(hipMemcpyAsync(dco, call_off, (nprog + 1) * 8, hipMemcpyHostToDevice, ctx->stream));
-  if (call_nums && nrec) SG_HIP(hipMemcpyAsync(dnum, call_nums, nrec * 4, hipMemcpyHostToDevice, ctx->stream));
-  int rc = sg_ipc_parse_dev(ctx, dw, doo, dco, call_nums ? dnum : nullptr, nprog, nrec, (int64_t*)derr, dfi, dst, dso,
-                            dsv, cov_off ? dcvo : nullptr, cov_off ? dcv : nullptr);
+  int rc;
+  if ((rc = upload(ctx, dw, out, nwords * 4))) return rc;
+  if ((rc = upload(ctx, doo, out_off, (nprog + 1) * 8))) return rc;
+  if ((rc = upload(ctx, dco, call_off, (nprog + 1) * 8))) return rc;
+  if (call_nums && (rc = upload(ctx, dnum, call_nums, nrec * 4))) return rc;
+  rc = sg_ipc_parse_dev(ctx, dw, doo, dco, call_nums ? dnum : nullptr, nprog, nrec, (int64_t*)derr, dfi, dst, dso,
+                        dsv, cov_off ? dcvo : nullptr, cov_off ? dcv : nullptr);
   if (rc) return rc;
   SG_HIP(hipMemcpyAsync(sig_off, dso, (nrec + 1) * 8, hipMemcpyDeviceToHost, ctx->stream));
   if (cov_off) SG_HIP(hipMemcpyAsync(cov_off, dcvo, (nrec + 1) * 8, hipMemcpyDeviceToHost, ctx->stream));

@@ -1350,14 +1350,15 @@ static int merge_run(sg_ctx* ctx, int op, const uint32_t* a, size_t a_total, con
       return SG_EINVAL;
     }
   }
-  const size_t b_a = (a_total * 4 + 255) & ~size_t(255), b_b = (b_total * 4 + 255) & ~size_t(255);
-  int rc = dstage_reserve(ctx, b_a + b_b + out_total * 4 + 256);
+  WsPlan p;
+  const size_t o_a = p.add(a_total * 4), o_b = p.add(b_total * 4), o_out = p.add(out_total * 4);
+  int rc = dstage_reserve(ctx, p);
   if (rc) return rc;
-  uint32_t* da = (uint32_t*)ctx->dstage;
-  uint32_t* db = (uint32_t*)((char*)ctx->dstage + b_a);
-  uint32_t* dout = (uint32_t*)((char*)ctx->dstage + b_a + b_b);
-  if (a_total) SG_HIP(hipMemcpyAsync(da, a, a_total * 4, hipMemcpyHostToDevice, ctx->stream));
-  if (b_total) SG_HIP(hipMemcpyAsync(db, b, b_total * 4, hipMemcpyHostToDevice, ctx->stream));
+  uint32_t* da = dstage_at<uint32_t>(ctx, o_a);
+  uint32_t* db = dstage_at<uint32_t>(ctx, o_b);
+  uint32_t* dout = dstage_at<uint32_t>(ctx, o_out);
+  if ((rc = upload(ctx, da, a, a_total * 4))) return rc;
+  if ((rc = upload(ctx, db, b, b_total * 4))) return rc;
   rc = merge_dev(ctx, op, da, db, dout, a_beg, a_len, b_beg, b_len, out_beg, npair, out_len);
   if (rc) return rc;
   // copy back only each pair's result range
@@ -1377,9 +1378,7 @@ extern "C" {
 int sg_canonicalize_batch(sg_ctx* ctx, uint32_t* vals, const uint64_t* off, size_t nseg, uint64_t* out_len) {
   if (!ctx || !off || (nseg && !out_len)) return SG_EINVAL;
   if (nseg == 0) return SG_OK;
-  if (off[0] != 0) return SG_EINVAL;
-  for (size_t k = 0; k < nseg; k++)
-    if (off[k + 1] < off[k]) return SG_EINVAL;
+  if (!offsets_ok(off, nseg)) return SG_EINVAL;
   uint64_t n = off[nseg];
   if (n && !vals) return SG_EINVAL;
   if (n == 0) {
@@ -1389,9 +1388,11 @@ int sg_canonicalize_batch(sg_ctx* ctx, uint32_t* vals, const uint64_t* off, size
   std::lock_guard<std::mutex> g(ctx->mu);
   int rc = ensure_device(ctx);
   if (rc) return rc;
-  rc = dstage_reserve(ctx, n * 4);
+  WsPlan p;
+  const size_t o_v = p.add(n * 4);
+  rc = dstage_reserve(ctx, p);
   if (rc) return rc;
-  uint32_t* dv = (uint32_t*)ctx->dstage;
+  uint32_t* dv = dstage_at<uint32_t>(ctx, o_v);
   SG_HIP(hipMemcpyAsync(dv, vals, n * 4, hipMemcpyHostToDevice, ctx->stream));
   rc = canonicalize_dev(ctx, dv, off, nseg, out_len);
   if (rc) return rc;

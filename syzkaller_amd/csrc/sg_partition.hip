@@ -966,7 +966,7 @@ __global__ __launch_bounds__(kScanThreads) void k_scan32_apply(const uint32_t* _
   if (blockIdx.x == b_last && threadIdx.x == kScanThreads - 1) out[n] = run;
 }
 
-static size_t scan32_ws(uint64_t n) { return (((n + kScanTile - 1) / kScanTile) * 4 + 255) & ~size_t(255); }
+static size_t scan32_ws(uint64_t n) { return align256(((n + kScanTile - 1) / kScanTile) * 4); }
 
 // n = host bound; with n_dev the count is (*n_dev) * mul (<= n)
 static int scan32(sg_ctx* ctx, const uint32_t* in, uint32_t* out, uint64_t n, uint32_t* scratch,

@@ -1,0 +1,43 @@
+// sg_plan.h -- layout arithmetic of the context's device buffers (the
+// workspace and the host forms' staging buffer).  Plain C++: no HIP, so a host
+// compiler builds it alone (tests/cpp/plan_test.cc).
+#pragma once
+
+#include <cstddef>
+#include <cstdint>
+
+namespace sg {
+
+constexpr size_t align256(size_t b) { return (b + 255) & ~size_t(255); }
+
+// Bump-allocated regions of one buffer, each 256-B aligned: add returns the
+// region's offset and total is the bytes to reserve.  off[] records the first
+// kMaxRegions offsets in order (sg_part.h indexes it); a region past them is
+// still laid out, and overflow makes ws_reserve / dstage_reserve refuse the
+// plan.
+struct WsPlan {
+  static constexpr int kMaxRegions = 48;
+  size_t off[kMaxRegions];
+  int n = 0;
+  size_t total = 0;
+  bool overflow = false;
+  size_t add(size_t bytes) {
+    const size_t o = total;
+    if (n < kMaxRegions)
+      off[n++] = o;
+    else
+      overflow = true;
+    total += align256(bytes);
+    return o;
+  }
+};
+
+// CSR offsets of n lists: off[0] == 0 and non-decreasing up to off[n].
+inline bool offsets_ok(const uint64_t* off, size_t n) {
+  if (off[0] != 0) return false;
+  for (size_t i = 0; i < n; i++)
+    if (off[i + 1] < off[i]) return false;
+  return true;
+}
+
+}  // namespace sg

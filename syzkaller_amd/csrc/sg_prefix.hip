@@ -131,8 +131,6 @@ __global__ __launch_bounds__(1024) void k_sum_counts(const uint32_t* __restrict_
   }
 }
 
-static size_t align256(size_t x) { return (x + 255) & ~size_t(255); }
-
 // The slot's workspace stands in for the context's during one call (the
 // partition code addresses the workspace through ctx->ws); grown to the exact
 // size, since it is kept.

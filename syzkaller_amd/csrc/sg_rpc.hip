@@ -499,13 +499,6 @@ static bool dec_blocks(const sg_ctx* ctx, uint64_t n, uint64_t nb) {  // (option
 
 inline uint32_t grid_for(uint64_t n) { return (uint32_t)std::min<uint64_t>(div_up(n ? n : 1, 256), 16384); }
 
-bool offsets_ok(const uint64_t* off, size_t n) {
-  if (off[0] != 0) return false;
-  for (size_t k = 0; k < n; k++)
-    if (off[k + 1] < off[k]) return false;
-  return true;
-}
-
 // Encode the n lists at device d_v / d_off (N = elements) into device bytes;
 // h_out_off (host, n+1) gets the byte offsets.  dstage holds d_v / d_off; the
 // scratch and output live in ws from `base`.  Returns the byte buffer.
@@ -661,11 +654,12 @@ int sg_delta_encode_batch(sg_ctx* ctx, const uint32_t* vals, const uint64_t* off
   std::lock_guard<std::mutex> g(ctx->mu);
   int rc = ensure_device(ctx);
   if (rc) return rc;
-  const size_t b_v = (N * 4 + 255) & ~size_t(255);
-  rc = dstage_reserve(ctx, b_v + (n + 1) * 8);
+  WsPlan p;
+  const size_t o_v = p.add(N * 4), o_off = p.add((n + 1) * 8);
+  rc = dstage_reserve(ctx, p);
   if (rc) return rc;
-  uint32_t* dv = (uint32_t*)ctx->dstage;
-  uint64_t* doff = (uint64_t*)((char*)ctx->dstage + b_v);
+  uint32_t* dv = dstage_at<uint32_t>(ctx, o_v);
+  uint64_t* doff = dstage_at<uint64_t>(ctx, o_off);
   SG_HIP(hipMemcpyAsync(dv, vals, N * 4, hipMemcpyHostToDevice, ctx->stream));
   SG_HIP(hipMemcpyAsync(doff, off, (n + 1) * 8, hipMemcpyHostToDevice, ctx->stream));
   uint8_t* bytes = nullptr;
@@ -693,13 +687,14 @@ int sg_delta_decode_batch(sg_ctx* ctx, const uint8_t* in, const uint64_t* in_off
   int rc = ensure_device(ctx);
   if (rc) return rc;
   // every byte can end a value: nb values at most
-  const size_t b_b = (nb + 255) & ~size_t(255), b_o = ((n + 1) * 8 + 255) & ~size_t(255);
-  rc = dstage_reserve(ctx, b_b + 2 * b_o + nb * 4 + 4);
+  WsPlan p;
+  const size_t o_in = p.add(nb), o_io = p.add((n + 1) * 8), o_vo = p.add((n + 1) * 8), o_v = p.add(nb * 4 + 4);
+  rc = dstage_reserve(ctx, p);
   if (rc) return rc;
-  uint8_t* din = (uint8_t*)ctx->dstage;
-  uint64_t* dio = (uint64_t*)((char*)ctx->dstage + b_b);
-  uint64_t* dvo = (uint64_t*)((char*)ctx->dstage + b_b + b_o);
-  uint32_t* dv = (uint32_t*)((char*)ctx->dstage + b_b + 2 * b_o);
+  uint8_t* din = dstage_at<uint8_t>(ctx, o_in);
+  uint64_t* dio = dstage_at<uint64_t>(ctx, o_io);
+  uint64_t* dvo = dstage_at<uint64_t>(ctx, o_vo);
+  uint32_t* dv = dstage_at<uint32_t>(ctx, o_v);
   SG_HIP(hipMemcpyAsync(din, in, nb, hipMemcpyHostToDevice, ctx->stream));
   SG_HIP(hipMemcpyAsync(dio, in_off, (n + 1) * 8, hipMemcpyHostToDevice, ctx->stream));
   rc = decode_dev(ctx, din, dio, n, nb, dv, nb, off, dvo);
@@ -726,11 +721,12 @@ int sg_set_encode(sg_set* set, uint8_t* out, size_t cap, size_t* nbytes) {
   }
   *nbytes = 0;
   if (total == 0) return SG_OK;
-  const size_t b_v = (total * 4 + 255) & ~size_t(255);
-  rc = dstage_reserve(ctx, b_v + 16);
+  WsPlan p;
+  const size_t o_v = p.add(total * 4), o_off = p.add(16);
+  rc = dstage_reserve(ctx, p);
   if (rc) return rc;
-  uint32_t* dv = (uint32_t*)ctx->dstage;
-  uint64_t* doff = (uint64_t*)((char*)ctx->dstage + b_v);
+  uint32_t* dv = dstage_at<uint32_t>(ctx, o_v);
+  uint64_t* doff = dstage_at<uint64_t>(ctx, o_off);
   rc = set_export_dev(set, dv, total, &total);
   if (rc) return rc;
   const uint64_t hoff[2] = {0, total};
@@ -755,13 +751,14 @@ int sg_set_decode_add(sg_set* set, const uint8_t* in, size_t nbytes, uint64_t* c
   std::lock_guard<std::mutex> g(ctx->mu);
   int rc = ensure_device(ctx);
   if (rc) return rc;
-  const size_t b_b = (nbytes + 255) & ~size_t(255);
-  rc = dstage_reserve(ctx, b_b + 512 + nbytes * 4 + 4);
+  WsPlan p;
+  const size_t o_in = p.add(nbytes), o_io = p.add(16), o_vo = p.add(16), o_v = p.add(nbytes * 4 + 4);
+  rc = dstage_reserve(ctx, p);
   if (rc) return rc;
-  uint8_t* din = (uint8_t*)ctx->dstage;
-  uint64_t* dio = (uint64_t*)((char*)ctx->dstage + b_b);
-  uint64_t* dvo = dio + 32;
-  uint32_t* dv = (uint32_t*)((char*)ctx->dstage + b_b + 512);
+  uint8_t* din = dstage_at<uint8_t>(ctx, o_in);
+  uint64_t* dio = dstage_at<uint64_t>(ctx, o_io);
+  uint64_t* dvo = dstage_at<uint64_t>(ctx, o_vo);
+  uint32_t* dv = dstage_at<uint32_t>(ctx, o_v);
   const uint64_t hio[2] = {0, nbytes};
   SG_HIP(hipMemcpyAsync(din, in, nbytes, hipMemcpyHostToDevice, ctx->stream));
   SG_HIP(hipMemcpyAsync(dio, hio, 16, hipMemcpyHostToDevice, ctx->stream));
@@ -785,16 +782,17 @@ int sg_sancov_batch(sg_ctx* ctx, const uint32_t* cov, const uint64_t* cov_off, s
   std::lock_guard<std::mutex> g(ctx->mu);
   int rc = ensure_device(ctx);
   if (rc) return rc;
-  const size_t b_v = (N * 4 + 255) & ~size_t(255), b_o = ((n + 1) * 8 + 255) & ~size_t(255);
-  const size_t b_w = ((N + 31) / 32 * 8 + 255) & ~size_t(255);
-  rc = dstage_reserve(ctx, b_v + b_o + b_w + (N + n) * 8);
+  WsPlan p;
+  const size_t o_v = p.add(N * 4), o_off = p.add((n + 1) * 8), o_kw = p.add((N + 31) / 32 * 8),
+               o_out = p.add((N + n) * 8);
+  rc = dstage_reserve(ctx, p);
   if (rc) return rc;
-  uint32_t* dv = (uint32_t*)ctx->dstage;
-  uint64_t* doff = (uint64_t*)((char*)ctx->dstage + b_v);
-  uint64_t* kw = (uint64_t*)((char*)ctx->dstage + b_v + b_o);
-  uint64_t* dout = (uint64_t*)((char*)ctx->dstage + b_v + b_o + b_w);
-  if (N) SG_HIP(hipMemcpyAsync(dv, cov, N * 4, hipMemcpyHostToDevice, ctx->stream));
-  SG_HIP(hipMemcpyAsync(doff, cov_off, (n + 1) * 8, hipMemcpyHostToDevice, ctx->stream));
+  uint32_t* dv = dstage_at<uint32_t>(ctx, o_v);
+  uint64_t* doff = dstage_at<uint64_t>(ctx, o_off);
+  uint64_t* kw = dstage_at<uint64_t>(ctx, o_kw);
+  uint64_t* dout = dstage_at<uint64_t>(ctx, o_out);
+  if ((rc = upload(ctx, dv, cov, N * 4))) return rc;
+  if ((rc = upload(ctx, doff, cov_off, (n + 1) * 8))) return rc;
   {
     ScopedTimer tm(ctx, "sancov");
     if (N)

@@ -418,9 +418,11 @@ int sg_shard_owners_dev(sg_ctx* ctx, const uint32_t* d_pairs, uint64_t npairs, u
   SG_HIP(hipMemsetAsync(d_rec_bits, 0, ((nrec_total + 31) / 32) * 4, ctx->stream));
   SG_HIP(hipMemsetAsync(d_nnew, 0, 8, ctx->stream));
   if (npairs == 0) return SG_OK;
-  rc = dstage_reserve(ctx, nrec_total + 64);
+  WsPlan sp;
+  const size_t o_flag = sp.add(nrec_total + 64);
+  rc = dstage_reserve(ctx, sp);
   if (rc) return rc;
-  uint8_t* rec_flag = (uint8_t*)ctx->dstage;
+  uint8_t* rec_flag = dstage_at<uint8_t>(ctx, o_flag);
   SG_HIP(hipMemsetAsync(rec_flag, 0, nrec_total, ctx->stream));
   uint32_t key_lo = 0;
   rc = owner_keys(ctx, nrec_total ? nrec_total : 1, &key_lo);

@@ -19,9 +19,6 @@
 #include "sg_tinput.h"
 
 namespace sg {
-
-int canonicalize_dev(sg_ctx* ctx, uint32_t* d_vals, const uint64_t* off, uint64_t nseg, uint64_t* out_len);
-
 namespace {
 
 using namespace tin;  // block_rank, k_tin_diff, tin_intersect (sg_tinput.h)
@@ -55,19 +52,6 @@ __global__ void k_seg_pack(const uint32_t* __restrict__ src, const uint64_t* __r
   for (uint64_t i = threadIdx.x & 63; i < L; i += 64) dst[d + i] = src[s + i];
 }
 
-bool offsets_ok(const uint64_t* off, size_t n) {
-  if (off[0] != 0) return false;
-  for (size_t k = 0; k < n; k++)
-    if (off[k + 1] < off[k]) return false;
-  return true;
-}
-
-// Stage a CSR (host) into dstage at byte offset `at`: values then offsets.
-struct Staged {
-  uint32_t* v;
-  uint64_t* off;
-};
-
 }  // namespace
 }  // namespace sg
 
@@ -90,18 +74,19 @@ int sg_triage_newsig(sg_ctx* ctx, sg_set* corpus, const uint32_t* vals, const ui
   std::lock_guard<std::mutex> g(ctx->mu);
   int rc = ensure_device(ctx);
   if (rc) return rc;
-  // dstage: S vals | S off | diff vals | diff off | canonical lengths | packed off | packed vals
-  const size_t b_v = (N * 4 + 255) & ~size_t(255), b_o = ((n + 1) * 8 + 255) & ~size_t(255);
-  rc = dstage_reserve(ctx, 3 * b_v + 3 * b_o + b_o);
+  // staged: S vals | S off | diff vals | diff off | canonical lengths | packed off | packed vals
+  WsPlan sp;
+  const size_t o_v = sp.add(N * 4), o_off = sp.add((n + 1) * 8), o_diff = sp.add(N * 4), o_doff = sp.add((n + 1) * 8),
+               o_len = sp.add((n + 1) * 8), o_poff = sp.add((n + 1) * 8), o_pack = sp.add(N * 4);
+  rc = dstage_reserve(ctx, sp);
   if (rc) return rc;
-  char* st = (char*)ctx->dstage;
-  uint32_t* dv = (uint32_t*)st;
-  uint64_t* doff = (uint64_t*)(st + b_v);
-  uint32_t* ddiff = (uint32_t*)(st + b_v + b_o);
-  uint64_t* ddoff = (uint64_t*)(st + 2 * b_v + b_o);
-  uint64_t* dlen = (uint64_t*)(st + 2 * b_v + 2 * b_o);
-  uint64_t* dpoff = (uint64_t*)(st + 2 * b_v + 3 * b_o);
-  uint32_t* dpack = (uint32_t*)(st + 2 * b_v + 4 * b_o);
+  uint32_t* dv = dstage_at<uint32_t>(ctx, o_v);
+  uint64_t* doff = dstage_at<uint64_t>(ctx, o_off);
+  uint32_t* ddiff = dstage_at<uint32_t>(ctx, o_diff);
+  uint64_t* ddoff = dstage_at<uint64_t>(ctx, o_doff);
+  uint64_t* dlen = dstage_at<uint64_t>(ctx, o_len);
+  uint64_t* dpoff = dstage_at<uint64_t>(ctx, o_poff);
+  uint32_t* dpack = dstage_at<uint32_t>(ctx, o_pack);
   WsPlan p;
   const size_t o_cnt = p.add(n * 4);
   rc = ws_reserve(ctx, p.total + scan_ws_bytes(n));
@@ -147,21 +132,21 @@ static int tinput_intersect(sg_ctx* ctx, uint32_t* a, const uint64_t* a_off, con
   std::lock_guard<std::mutex> g(ctx->mu);
   int rc = ensure_device(ctx);
   if (rc) return rc;
-  const size_t b_a = (NA * 4 + 255) & ~size_t(255), b_r = (NR * 4 + 255) & ~size_t(255),
-               b_o = ((n + 1) * 8 + 255) & ~size_t(255), b_f = (n + 255) & ~size_t(255);
-  rc = dstage_reserve(ctx, b_a + b_r + 3 * b_o + b_f);
+  WsPlan p;
+  const size_t o_a = p.add(NA * 4), o_r = p.add(NR * 4), o_ao = p.add((n + 1) * 8), o_ro = p.add((n + 1) * 8),
+               o_len = p.add((n + 1) * 8), o_ok = p.add(n);
+  rc = dstage_reserve(ctx, p);
   if (rc) return rc;
-  char* st = (char*)ctx->dstage;
-  uint32_t* da = (uint32_t*)st;
-  uint32_t* dr = (uint32_t*)(st + b_a);
-  uint64_t* dao = (uint64_t*)(st + b_a + b_r);
-  uint64_t* dro = (uint64_t*)(st + b_a + b_r + b_o);
-  uint64_t* dlen = (uint64_t*)(st + b_a + b_r + 2 * b_o);
-  uint8_t* dok = (uint8_t*)(st + b_a + b_r + 3 * b_o);
-  if (NA) SG_HIP(hipMemcpyAsync(da, a, NA * 4, hipMemcpyHostToDevice, ctx->stream));
-  if (NR) SG_HIP(hipMemcpyAsync(dr, r, NR * 4, hipMemcpyHostToDevice, ctx->stream));
-  SG_HIP(hipMemcpyAsync(dao, a_off, (n + 1) * 8, hipMemcpyHostToDevice, ctx->stream));
-  SG_HIP(hipMemcpyAsync(dro, r_off, (n + 1) * 8, hipMemcpyHostToDevice, ctx->stream));
+  uint32_t* da = dstage_at<uint32_t>(ctx, o_a);
+  uint32_t* dr = dstage_at<uint32_t>(ctx, o_r);
+  uint64_t* dao = dstage_at<uint64_t>(ctx, o_ao);
+  uint64_t* dro = dstage_at<uint64_t>(ctx, o_ro);
+  uint64_t* dlen = dstage_at<uint64_t>(ctx, o_len);
+  uint8_t* dok = dstage_at<uint8_t>(ctx, o_ok);
+  if ((rc = upload(ctx, da, a, NA * 4))) return rc;
+  if ((rc = upload(ctx, dr, r, NR * 4))) return rc;
+  if ((rc = upload(ctx, dao, a_off, (n + 1) * 8))) return rc;
+  if ((rc = upload(ctx, dro, r_off, (n + 1) * 8))) return rc;
   {
     ScopedTimer tm(ctx, "tinput_intersect");
     if (out_len)

@@ -965,8 +965,6 @@ static int run_emit(sg_ctx* ctx, const uint32_t* vals, uint64_t n, const uint64_
   return SG_OK;
 }
 
-static size_t al256(size_t x) { return (x + 255) & ~size_t(255); }
-
 // the per-record sweeps of one slice: the wave kernel over the resident grid
 // (records every grid-th, or blocks of 64 by ticket), then the listed large
 // records
@@ -1019,14 +1017,16 @@ static int owned_outputs(sg_ctx* ctx, uint32_t* mwords, uint32_t* nwords, const 
   size_t o[5];
   const size_t scan_b = scratch_plan(p, nvals, o);
   const size_t scan_off = p.total;
-  const size_t S0 = al256(p.total + scan_b);
+  const size_t S0 = align256(p.total + scan_b);
   size_t part = 0, tail = 0;
   for (size_t j = 0; j + 3 < cuts.size(); j += 4) {
     const uint64_t nr = cuts[j + 1] - cuts[j], ns = cuts[j + 3] - cuts[j + 2];
     if (!ns) continue;
-    part = std::max(part, al256(std::max<size_t>(bucket_plan_bytes(ns, nr), ns * 8)));
-    tail = std::max(tail, al256(ns * 8) + al256(std::max(radix_sort_ws(ns), radix_pass_runs_ws(ns, (nr >> 16) + 1))) + al256(nr * 8) + al256((nr + 2) * 4) +
-                               al256((nr + 1) * 8) + al256(((nr >> kRecGroupBits) + 1) * 16));
+    part = std::max(part, align256(std::max<size_t>(bucket_plan_bytes(ns, nr), ns * 8)));
+    tail = std::max(tail, align256(ns * 8) +
+                              align256(std::max(radix_sort_ws(ns), radix_pass_runs_ws(ns, (nr >> 16) + 1))) +
+                              align256(nr * 8) + align256((nr + 2) * 4) + align256((nr + 1) * 8) +
+                              align256(((nr >> kRecGroupBits) + 1) * 16));
   }
   rc = ws_reserve(ctx, S0 + part + tail);
   if (rc) return rc;
@@ -1039,15 +1039,15 @@ static int owned_outputs(sg_ctx* ctx, uint32_t* mwords, uint32_t* nwords, const 
     uint64_t* keys_b = (uint64_t*)ws_at(ctx, S0);
     size_t at = S0 + part;
     uint64_t* keys_a = (uint64_t*)ws_at(ctx, at);
-    at += al256(ns * 8);
+    at += align256(ns * 8);
     const size_t sort_at = at;
-    at += al256(std::max(radix_sort_ws(ns), radix_pass_runs_ws(ns, (nr >> 16) + 1)));
+    at += align256(std::max(radix_sort_ws(ns), radix_pass_runs_ws(ns, (nr >> 16) + 1)));
     uint2* po = (uint2*)ws_at(ctx, at);
-    at += al256(nr * 8);
+    at += align256(nr * 8);
     uint32_t* big = (uint32_t*)ws_at(ctx, at);  // count, records, ticket
-    at += al256((nr + 2) * 4);
+    at += align256((nr + 2) * 4);
     uint64_t* roff = (uint64_t*)ws_at(ctx, at);
-    at += al256((nr + 1) * 8);
+    at += align256((nr + 1) * 8);
     const uint32_t ng = (uint32_t)((nr + (1u << kRecGroupBits) - 1) >> kRecGroupBits);
     unsigned long long* gcur = (unsigned long long*)ws_at(ctx, at);  // ng cursors, then ng starts
     uint64_t* gs = (uint64_t*)(gcur + ng);
@@ -1104,8 +1104,6 @@ static int owned_outputs(sg_ctx* ctx, uint32_t* mwords, uint32_t* nwords, const 
   return run_emit(ctx, d_vals, nvals, s.dmask, s.dcnt, s, scan_off, d_off, nrec, d_out_vals, d_out_off);
 }
 
-static int check_alloc(sg_ctx* ctx) { return ensure_device(ctx); }
-
 }  // namespace sg
 
 using namespace sg;
@@ -1124,7 +1122,7 @@ int sg_triage_batch_dev(sg_ctx* ctx, sg_set* maxsig, sg_set* newsig, const uint3
     return SG_EINVAL;
   }
   std::lock_guard<std::mutex> g(ctx->mu);
-  int rc = check_alloc(ctx);
+  int rc = ensure_device(ctx);
   if (rc) return rc;
   if (!d_diff_vals && !d_diff_off)  // flags + set updates only: partitioned path
     return bucket_triage(ctx, maxsig->words, newsig ? newsig->words : nullptr, d_vals, d_rec_off, nvals, nrec,
@@ -1152,8 +1150,7 @@ int sg_triage_batch(sg_ctx* ctx, sg_set* maxsig, sg_set* newsig, const uint32_t*
       return SG_EINVAL;
     }
   if (nvals && !vals) return SG_EINVAL;
-  bool want_diff = diff_vals || diff_off || n_diff;
-  if (!want_diff) {  // flags and set updates: the pipelined ingest (sg_host.hip)
+  if (!diff_vals && !diff_off && !n_diff) {  // flags and set updates: the pipelined ingest (sg_host.hip)
     if (maxsig->ctx != ctx || (newsig && newsig->ctx != ctx)) {
       set_error("sg_triage_batch: set belongs to another context");
       return SG_EINVAL;
@@ -1162,37 +1159,34 @@ int sg_triage_batch(sg_ctx* ctx, sg_set* maxsig, sg_set* newsig, const uint32_t*
   }
   // device staging: vals, off, rec_new, diff_vals, diff_off  (pipeline scratch
   // is carved behind these by the _dev entry point, which reserves again).
-  uint32_t* dv;
-  uint64_t* doff;
+  uint32_t *dv, *ddv;
+  uint64_t *doff, *ddo;
   uint8_t* dflag;
-  uint32_t* ddv;
-  uint64_t* ddo;
   // staged batch lives in the context's device staging buffer (the workspace
   // stays free for the pipeline)
-  size_t b_vals = (nvals * 4 + 255) & ~size_t(255), b_off = ((nrec + 1) * 8 + 255) & ~size_t(255),
-         b_flag = (nrec + 256) & ~size_t(255);
-  size_t b_dv = want_diff ? b_vals : 0, b_do = want_diff ? b_off : 0;
-  char* stage = nullptr;
+  WsPlan p;
+  const size_t o_v = p.add(nvals * 4), o_off = p.add((nrec + 1) * 8), o_flag = p.add(nrec + 1),
+               o_dv = p.add(nvals * 4), o_do = p.add((nrec + 1) * 8);
   {
     std::lock_guard<std::mutex> g(ctx->mu);
-    int rc = check_alloc(ctx);
+    int rc = ensure_device(ctx);
     if (rc) return rc;
-    rc = dstage_reserve(ctx, b_vals + b_off + b_flag + b_dv + b_do + 256);
+    rc = dstage_reserve(ctx, p);
     if (rc) return rc;
-    stage = (char*)ctx->dstage;
+    dv = dstage_at<uint32_t>(ctx, o_v);
+    doff = dstage_at<uint64_t>(ctx, o_off);
+    dflag = dstage_at<uint8_t>(ctx, o_flag);
+    ddv = dstage_at<uint32_t>(ctx, o_dv);
+    ddo = dstage_at<uint64_t>(ctx, o_do);
   }
-  dv = (uint32_t*)stage;
-  doff = (uint64_t*)(stage + b_vals);
-  dflag = (uint8_t*)(stage + b_vals + b_off);
-  ddv = want_diff ? (uint32_t*)(stage + b_vals + b_off + b_flag) : nullptr;
-  ddo = want_diff ? (uint64_t*)(stage + b_vals + b_off + b_flag + b_dv) : nullptr;
-  if (nvals) SG_HIP(hipMemcpyAsync(dv, vals, nvals * 4, hipMemcpyHostToDevice, ctx->stream));
-  SG_HIP(hipMemcpyAsync(doff, rec_off, (nrec + 1) * 8, hipMemcpyHostToDevice, ctx->stream));
-  int rc = sg_triage_batch_dev(ctx, maxsig, newsig, dv, doff, nvals, nrec, dflag, ddv, ddo);
+  int rc;
+  if ((rc = upload(ctx, dv, vals, nvals * 4))) return rc;
+  if ((rc = upload(ctx, doff, rec_off, (nrec + 1) * 8))) return rc;
+  rc = sg_triage_batch_dev(ctx, maxsig, newsig, dv, doff, nvals, nrec, dflag, ddv, ddo);
   if (rc) return rc;
   if (nrec) SG_HIP(hipMemcpyAsync(rec_new, dflag, nrec, hipMemcpyDeviceToHost, ctx->stream));
   uint64_t total = 0;
-  if (want_diff) SG_HIP(hipMemcpyAsync(&total, ddo + nrec, 8, hipMemcpyDeviceToHost, ctx->stream));
+  SG_HIP(hipMemcpyAsync(&total, ddo + nrec, 8, hipMemcpyDeviceToHost, ctx->stream));
   SG_HIP(hipStreamSynchronize(ctx->stream));
   if (diff_off) SG_HIP(hipMemcpyAsync(diff_off, ddo, (nrec + 1) * 8, hipMemcpyDeviceToHost, ctx->stream));
   if (diff_vals && total) SG_HIP(hipMemcpyAsync(diff_vals, ddv, total * 4, hipMemcpyDeviceToHost, ctx->stream));
@@ -1212,7 +1206,7 @@ int sg_triage_traces_dev(sg_ctx* ctx, sg_set* maxsig, sg_set* newsig, const uint
     return SG_EINVAL;
   }
   std::lock_guard<std::mutex> g(ctx->mu);
-  int rc = check_alloc(ctx);
+  int rc = ensure_device(ctx);
   if (rc) return rc;
   return bucket_triage(ctx, maxsig->words, newsig ? newsig->words : nullptr, d_pcs, d_call_off, npcs, ncalls,
                        d_rec_new, true);
@@ -1250,7 +1244,7 @@ int sg_set_diff(sg_set* set, const uint32_t* sig, size_t n, uint32_t* out, size_
   if (n == 0) return SG_OK;
   sg_ctx* ctx = set->ctx;
   std::lock_guard<std::mutex> g(ctx->mu);
-  int rc = check_alloc(ctx);
+  int rc = ensure_device(ctx);
   if (rc) return rc;
   WsPlan p;
   size_t o[5];
@@ -1286,7 +1280,7 @@ int sg_add_inputs(sg_ctx* ctx, sg_set* corpus, sg_set* maxsig, const uint32_t* v
   if (off[0] != 0 || (nv && !vals)) return SG_EINVAL;
   if (nv == 0) return SG_OK;
   std::lock_guard<std::mutex> g(ctx->mu);
-  int rc = check_alloc(ctx);
+  int rc = ensure_device(ctx);
   if (rc) return rc;
   WsPlan p;
   size_t o[5];
@@ -1316,27 +1310,27 @@ int sg_accept_batch(sg_ctx* ctx, sg_set* corpus_sig, sg_set* corpus_cov, const u
   if (sig_off[0] != 0 || (nv && !sig_vals) || (nc && !cov_vals)) return SG_EINVAL;
   if (n == 0) return SG_OK;
   std::lock_guard<std::mutex> g(ctx->mu);
-  int rc = check_alloc(ctx);
+  int rc = ensure_device(ctx);
   if (rc) return rc;
   // The NewInput loop (manager.go:907-911) is the fuzzer's new-signal loop
   // with corpusSignal as the running set and no newSignal: the partitioned
   // triage path.  The batch is staged in dstage (the workspace is the
   // partition's).
-  const size_t b_in = (nv * 4 + 255) & ~size_t(255), b_off = ((n + 1) * 8 + 255) & ~size_t(255),
-               b_flag = (n + 255) & ~size_t(255), b_cv = (nc * 4 + 255) & ~size_t(255);
-  rc = dstage_reserve(ctx, b_in + 2 * b_off + b_flag + b_cv + 256);
+  WsPlan p;
+  const size_t o_in = p.add(nv * 4), o_off = p.add((n + 1) * 8), o_flag = p.add(n), o_cv = p.add(nc * 4),
+               o_co = p.add((n + 1) * 8);
+  rc = dstage_reserve(ctx, p);
   if (rc) return rc;
-  char* st = (char*)ctx->dstage;
-  uint32_t* din = (uint32_t*)st;
-  uint64_t* doff = (uint64_t*)(st + b_in);
-  uint8_t* dflag = (uint8_t*)(st + b_in + b_off);
-  if (nv) SG_HIP(hipMemcpyAsync(din, sig_vals, nv * 4, hipMemcpyHostToDevice, ctx->stream));
-  SG_HIP(hipMemcpyAsync(doff, sig_off, (n + 1) * 8, hipMemcpyHostToDevice, ctx->stream));
+  uint32_t* din = dstage_at<uint32_t>(ctx, o_in);
+  uint64_t* doff = dstage_at<uint64_t>(ctx, o_off);
+  uint8_t* dflag = dstage_at<uint8_t>(ctx, o_flag);
+  if ((rc = upload(ctx, din, sig_vals, nv * 4))) return rc;
+  if ((rc = upload(ctx, doff, sig_off, (n + 1) * 8))) return rc;
   rc = bucket_triage(ctx, corpus_sig->words, nullptr, din, doff, nv, n, dflag);
   if (rc) return rc;
   if (nc) {
-    uint32_t* dcv = (uint32_t*)(st + b_in + b_off + b_flag);
-    uint64_t* dco = (uint64_t*)(st + b_in + b_off + b_flag + b_cv);
+    uint32_t* dcv = dstage_at<uint32_t>(ctx, o_cv);
+    uint64_t* dco = dstage_at<uint64_t>(ctx, o_co);
     SG_HIP(hipMemcpyAsync(dcv, cov_vals, nc * 4, hipMemcpyHostToDevice, ctx->stream));
     SG_HIP(hipMemcpyAsync(dco, cov_off, (n + 1) * 8, hipMemcpyHostToDevice, ctx->stream));
     hipLaunchKernelGGL(k_add_flagged_segs, dim3(std::min<uint64_t>(div_up(nc, 256), 8192)), dim3(256), 0,
@@ -1354,7 +1348,7 @@ int sg_merge_poll(sg_ctx* ctx, sg_set* mgr_max, const uint32_t* a_vals, const ui
   uint64_t nv = a_off[npoll] - a_off[0];
   if (a_off[0] != 0 || (nv && (!a_vals || !new_vals))) return SG_EINVAL;
   std::lock_guard<std::mutex> g(ctx->mu);
-  int rc = check_alloc(ctx);
+  int rc = ensure_device(ctx);
   if (rc) return rc;
   if (nv == 0) {
     SG_HIP(hipMemsetAsync(ctx->own_big, 0, 4, ctx->stream));  // (no record listed)
@@ -1365,24 +1359,20 @@ int sg_merge_poll(sg_ctx* ctx, sg_set* mgr_max, const uint32_t* a_vals, const ui
   // with mgr.maxSignal as the running set, each poll's new signals in its
   // order, once each (its first occurrence): the ordered-output path with
   // dedup.  The batch is staged in dstage (the workspace is the partition's).
-  const size_t b_in = al256(nv * 4), b_off = al256((npoll + 1) * 8);
-  rc = dstage_reserve(ctx, 2 * b_in + 2 * b_off + 256);
+  WsPlan p;
+  const size_t o_in = p.add(nv * 4), o_off = p.add((npoll + 1) * 8), o_out = p.add(nv * 4),
+               o_oo = p.add((npoll + 1) * 8);
+  rc = dstage_reserve(ctx, p);
   if (rc) return rc;
-  char* st = (char*)ctx->dstage;
-  uint32_t* din = (uint32_t*)st;
-  uint64_t* doff = (uint64_t*)(st + b_in);
-  uint32_t* dout = (uint32_t*)(st + b_in + b_off);
-  uint64_t* doo = (uint64_t*)(st + 2 * b_in + b_off);
+  uint32_t* din = dstage_at<uint32_t>(ctx, o_in);
+  uint64_t* doff = dstage_at<uint64_t>(ctx, o_off);
+  uint32_t* dout = dstage_at<uint32_t>(ctx, o_out);
+  uint64_t* doo = dstage_at<uint64_t>(ctx, o_oo);
   SG_HIP(hipMemcpyAsync(din, a_vals, nv * 4, hipMemcpyHostToDevice, ctx->stream));
   SG_HIP(hipMemcpyAsync(doff, a_off, (npoll + 1) * 8, hipMemcpyHostToDevice, ctx->stream));
   rc = owned_outputs(ctx, mgr_max->words, nullptr, din, doff, nv, npoll, nullptr, dout, doo, true);
   if (rc) return rc;
-  SG_HIP(hipMemcpyAsync(new_off, doo, (npoll + 1) * 8, hipMemcpyDeviceToHost, ctx->stream));
-  SG_HIP(hipStreamSynchronize(ctx->stream));
-  if (new_off[npoll])
-    SG_HIP(hipMemcpyAsync(new_vals, dout, new_off[npoll] * 4, hipMemcpyDeviceToHost, ctx->stream));
-  SG_HIP(hipStreamSynchronize(ctx->stream));
-  return SG_OK;
+  return csr_download(ctx, new_off, doo, npoll, new_vals, dout, 4, ~0ull);
 }
 
 int sg_minimize(sg_ctx* ctx, const uint32_t* vals, const uint64_t* off, size_t n, const uint32_t* order,
@@ -1404,7 +1394,7 @@ int sg_minimize(sg_ctx* ctx, const uint32_t* vals, const uint64_t* off, size_t n
     }
   }
   std::lock_guard<std::mutex> g(ctx->mu);
-  int rc = check_alloc(ctx);
+  int rc = ensure_device(ctx);
   if (rc) return rc;
   WsPlan p;
   size_t o_in = p.add(nv * 4), o_off = p.add((n + 1) * 8), o_ord = p.add(n * 4),

@@ -38,9 +38,6 @@
 #include "sg_tinput.h"
 
 namespace sg {
-
-int canonicalize_dev(sg_ctx* ctx, uint32_t* d_vals, const uint64_t* off, uint64_t nseg, uint64_t* out_len);
-
 namespace {
 
 using namespace tin;
@@ -406,44 +403,28 @@ __global__ __launch_bounds__(256) void k_tr_pack(PackArgs a) {
   }
 }
 
-bool offsets_ok(const uint64_t* off, size_t n) {
-  if (off[0] != 0) return false;
-  for (size_t k = 0; k < n; k++)
-    if (off[k + 1] < off[k]) return false;
-  return true;
-}
-
-size_t al(size_t b) { return (b + 255) & ~size_t(255); }
-
-// the call's intermediates, in the context's device staging buffer
+// the call's intermediates: regions of the caller's staging plan
 struct TrPlan {
   size_t pcs32, sel, selcall, xsig_off, xsig, xcov_off, xcov, diff, diff_off, cnt, cur_len, state, newlen, covlen, covsrc,
-      buf0, buf1, total;
-  TrPlan(size_t base, uint64_t n, uint64_t nexec, uint64_t ncalls, uint64_t npcs, uint64_t nsig) {
-    size_t t = base;
-    auto add = [&](size_t b) {
-      const size_t o = t;
-      t += al(b);
-      return o;
-    };
-    pcs32 = add(npcs * 4 + 4);
-    sel = add(ncalls + 1);
-    selcall = add(nexec * 4 + 4);
-    xsig_off = add((ncalls + 1) * 8);
-    xsig = add(npcs * 4 + 4);
-    xcov_off = add((ncalls + 1) * 8);
-    xcov = add(npcs * 4 + 4);
-    diff = add(nsig * 4 + 4);
-    diff_off = add((n + 1) * 8);
-    cnt = add(n * 4 + 4);
-    cur_len = add(n * 8 + 8);
-    state = add(n * 4 + 4);
-    newlen = add(n * 4 + 4);
-    covlen = add(n * 4 + 4);
-    covsrc = add(n + 1);
-    buf0 = add(npcs * 4 + 4);
-    buf1 = add(npcs * 4 + 4);
-    total = t;
+      buf0, buf1;
+  TrPlan(WsPlan& p, uint64_t n, uint64_t nexec, uint64_t ncalls, uint64_t npcs, uint64_t nsig) {
+    pcs32 = p.add(npcs * 4 + 4);
+    sel = p.add(ncalls + 1);
+    selcall = p.add(nexec * 4 + 4);
+    xsig_off = p.add((ncalls + 1) * 8);
+    xsig = p.add(npcs * 4 + 4);
+    xcov_off = p.add((ncalls + 1) * 8);
+    xcov = p.add(npcs * 4 + 4);
+    diff = p.add(nsig * 4 + 4);
+    diff_off = p.add((n + 1) * 8);
+    cnt = p.add(n * 4 + 4);
+    cur_len = p.add(n * 8 + 8);
+    state = p.add(n * 4 + 4);
+    newlen = p.add(n * 4 + 4);
+    covlen = p.add(n * 4 + 4);
+    covsrc = p.add(n + 1);
+    buf0 = p.add(npcs * 4 + 4);
+    buf1 = p.add(npcs * 4 + 4);
   }
 };
 
@@ -480,27 +461,27 @@ int tr_limits(uint64_t n, uint32_t nruns, uint64_t ncalls, uint64_t npcs, uint64
 }
 
 // the body of both forms: every pointer of io is device memory, the
-// intermediates are at `base` of the staging buffer (reserved by the caller);
-// ctx lock held, the device ensured, n > 0
-int triage_runs(sg_ctx* ctx, sg_set* corpus, const TrIo& io, size_t base) {
+// intermediates are p's regions of the staging buffer (reserved by the
+// caller); ctx lock held, the device ensured, n > 0
+int triage_runs(sg_ctx* ctx, sg_set* corpus, const TrIo& io, const TrPlan& p) {
   const uint64_t n = io.n, nexec = n * io.nruns, ncalls = io.ncalls, npcs = io.npcs;
-  const TrPlan p(base, n, nexec, ncalls, npcs, io.nsig);
-  char* st = (char*)ctx->dstage;
-  uint32_t* pcs32 = (uint32_t*)(st + p.pcs32);
-  uint8_t* sel = (uint8_t*)(st + p.sel);
-  uint32_t* selcall = (uint32_t*)(st + p.selcall);
-  uint64_t* xsig_off = (uint64_t*)(st + p.xsig_off);
-  uint32_t* xsig = (uint32_t*)(st + p.xsig);
-  uint64_t* xcov_off = (uint64_t*)(st + p.xcov_off);
-  uint32_t* xcov = (uint32_t*)(st + p.xcov);
-  uint32_t* diff = (uint32_t*)(st + p.diff);
-  uint64_t* diff_off = (uint64_t*)(st + p.diff_off);
-  uint32_t* cnt = (uint32_t*)(st + p.cnt);
-  uint64_t* cur_len = (uint64_t*)(st + p.cur_len);
-  uint32_t* state = (uint32_t*)(st + p.state);
-  uint32_t* newlen = (uint32_t*)(st + p.newlen);
-  uint32_t* covlen = (uint32_t*)(st + p.covlen);
-  uint8_t* covsrc = (uint8_t*)(st + p.covsrc);
+  uint32_t* pcs32 = dstage_at<uint32_t>(ctx, p.pcs32);
+  uint8_t* sel = dstage_at<uint8_t>(ctx, p.sel);
+  uint32_t* selcall = dstage_at<uint32_t>(ctx, p.selcall);
+  uint64_t* xsig_off = dstage_at<uint64_t>(ctx, p.xsig_off);
+  uint32_t* xsig = dstage_at<uint32_t>(ctx, p.xsig);
+  uint64_t* xcov_off = dstage_at<uint64_t>(ctx, p.xcov_off);
+  uint32_t* xcov = dstage_at<uint32_t>(ctx, p.xcov);
+  uint32_t* diff = dstage_at<uint32_t>(ctx, p.diff);
+  uint64_t* diff_off = dstage_at<uint64_t>(ctx, p.diff_off);
+  uint32_t* cnt = dstage_at<uint32_t>(ctx, p.cnt);
+  uint64_t* cur_len = dstage_at<uint64_t>(ctx, p.cur_len);
+  uint32_t* state = dstage_at<uint32_t>(ctx, p.state);
+  uint32_t* newlen = dstage_at<uint32_t>(ctx, p.newlen);
+  uint32_t* covlen = dstage_at<uint32_t>(ctx, p.covlen);
+  uint8_t* covsrc = dstage_at<uint8_t>(ctx, p.covsrc);
+  uint32_t* buf0 = dstage_at<uint32_t>(ctx, p.buf0);
+  uint32_t* buf1 = dstage_at<uint32_t>(ctx, p.buf1);
   uint32_t* wide = ctx->own_big + kTrWideSlot;
   const dim3 b(256);
   int rc;
@@ -556,7 +537,7 @@ int triage_runs(sg_ctx* ctx, sg_set* corpus, const TrIo& io, size_t base) {
   {
     ScopedTimer tm(ctx, "triage_runs_cover");
     CoverArgs ca{io.nruns, ncalls,      npcs,   io.minimized, selcall, io.prog_off, io.call_off, xcov_off, xcov, state,
-                 cur_len,  io.status,   newlen, covlen,       covsrc,  {(uint32_t*)(st + p.buf0), (uint32_t*)(st + p.buf1)},
+                 cur_len,  io.status,   newlen, covlen,       covsrc,  {buf0, buf1},
                  wide};
     hipLaunchKernelGGL(k_tr_cover, dim3((uint32_t)n), dim3(kTB), 0, ctx->stream, ca);
   }
@@ -567,7 +548,7 @@ int triage_runs(sg_ctx* ctx, sg_set* corpus, const TrIo& io, size_t base) {
   rc = scan_counts(ctx, covlen, io.cov_off, n, 0);
   if (rc) return rc;
   PackArgs pa{n,          ncalls,      npcs,         io.nruns, io.prog_off, io.call_off, diff, diff_off,
-              io.new_off, io.new_vals, io.new_cap,   covsrc,   {(const uint32_t*)(st + p.buf0), (const uint32_t*)(st + p.buf1)},
+              io.new_off, io.new_vals, io.new_cap,   covsrc,   {buf0, buf1},
               io.cov_off, io.cov_vals, io.cov_cap};
   hipLaunchKernelGGL(k_tr_pack, dim3(div_up(n, 4)), b, 0, ctx->stream, pa);
   SG_HIP(hipGetLastError());
@@ -603,12 +584,13 @@ int sg_triage_runs_from_kcov_dev(sg_ctx* ctx, sg_set* corpus, const uint32_t* d_
     SG_HIP(hipMemsetAsync(d_cov_off, 0, 8, ctx->stream));
     return SG_OK;
   }
-  const TrPlan p(0, n, n * nruns, ncalls, npcs, nsig);
-  rc = dstage_reserve(ctx, p.total);
+  WsPlan plan;
+  const TrPlan p(plan, n, n * nruns, ncalls, npcs, nsig);
+  rc = dstage_reserve(ctx, plan);
   if (rc) return rc;
   const TrIo io{d_sig_vals, d_sig_off, n,        nsig,       d_call,  d_minimized, nruns,      d_pcs,     d_call_off, d_prog_off,
                 ncalls,     npcs,      d_status, d_new_off,  d_new_vals, new_cap,  d_cov_off,  d_cov_vals, cov_cap};
-  return triage_runs(ctx, corpus, io, 0);
+  return triage_runs(ctx, corpus, io, p);
 }
 
 int sg_triage_runs_from_kcov(sg_ctx* ctx, sg_set* corpus, const uint32_t* sig_vals, const uint64_t* sig_off, size_t n,
@@ -638,45 +620,39 @@ int sg_triage_runs_from_kcov(sg_ctx* ctx, sg_set* corpus, const uint32_t* sig_va
   }
   // nsig and npcs values always suffice: a smaller cap is staged as it is
   const uint64_t ncap = new_cap < nsig ? new_cap : nsig, ccap = cov_cap < npcs ? cov_cap : npcs;
-  const size_t b_sv = al(nsig * 4 + 4), b_so = al((n + 1) * 8), b_call = al(n * 4), b_min = al(n),
-               b_po = al((nexec + 1) * 8), b_co = al((ncalls + 1) * 8), b_pcs = al(npcs * 8 + 8), b_st = al(n * 4),
-               b_nv = al(ncap * 4 + 4), b_cv = al(ccap * 4 + 4);
-  const size_t base = b_sv + 3 * b_so + b_call + b_min + b_po + b_co + b_pcs + b_st + b_nv + b_cv;
+  WsPlan plan;
+  const size_t o_sv = plan.add(nsig * 4 + 4), o_so = plan.add((n + 1) * 8), o_no = plan.add((n + 1) * 8),
+               o_vo = plan.add((n + 1) * 8), o_call = plan.add(n * 4), o_min = plan.add(n),
+               o_po = plan.add((nexec + 1) * 8), o_co = plan.add((ncalls + 1) * 8), o_pcs = plan.add(npcs * 8 + 8),
+               o_st = plan.add(n * 4), o_nv = plan.add(ncap * 4 + 4), o_cv = plan.add(ccap * 4 + 4);
+  const TrPlan p(plan, n, nexec, ncalls, npcs, nsig);
   std::lock_guard<std::mutex> g(ctx->mu);
   rc = ensure_device(ctx);
   if (rc) return rc;
-  const TrPlan p(base, n, nexec, ncalls, npcs, nsig);
-  rc = dstage_reserve(ctx, p.total);
+  rc = dstage_reserve(ctx, plan);
   if (rc) return rc;
-  char* s = (char*)ctx->dstage;
-  size_t o = 0;
-  auto take = [&](size_t bytes) {
-    char* q = s + o;
-    o += bytes;
-    return q;
-  };
-  uint32_t* dsv = (uint32_t*)take(b_sv);
-  uint64_t* dso = (uint64_t*)take(b_so);
-  uint64_t* dno = (uint64_t*)take(b_so);
-  uint64_t* dvo = (uint64_t*)take(b_so);
-  uint32_t* dcall = (uint32_t*)take(b_call);
-  uint8_t* dmin = (uint8_t*)take(b_min);
-  uint64_t* dpo = (uint64_t*)take(b_po);
-  uint64_t* dco = (uint64_t*)take(b_co);
-  uint64_t* dpcs = (uint64_t*)take(b_pcs);
-  int32_t* dst = (int32_t*)take(b_st);
-  uint32_t* dnv = (uint32_t*)take(b_nv);
-  uint32_t* dcv = (uint32_t*)take(b_cv);
-  if (nsig) SG_HIP(hipMemcpyAsync(dsv, sig_vals, nsig * 4, hipMemcpyHostToDevice, ctx->stream));
-  SG_HIP(hipMemcpyAsync(dso, sig_off, (n + 1) * 8, hipMemcpyHostToDevice, ctx->stream));
-  SG_HIP(hipMemcpyAsync(dcall, call, n * 4, hipMemcpyHostToDevice, ctx->stream));
-  SG_HIP(hipMemcpyAsync(dmin, minimized, n, hipMemcpyHostToDevice, ctx->stream));
-  SG_HIP(hipMemcpyAsync(dpo, prog_off, (nexec + 1) * 8, hipMemcpyHostToDevice, ctx->stream));
-  SG_HIP(hipMemcpyAsync(dco, call_off, (ncalls + 1) * 8, hipMemcpyHostToDevice, ctx->stream));
-  if (npcs) SG_HIP(hipMemcpyAsync(dpcs, pcs, npcs * 8, hipMemcpyHostToDevice, ctx->stream));
+  uint32_t* dsv = dstage_at<uint32_t>(ctx, o_sv);
+  uint64_t* dso = dstage_at<uint64_t>(ctx, o_so);
+  uint64_t* dno = dstage_at<uint64_t>(ctx, o_no);
+  uint64_t* dvo = dstage_at<uint64_t>(ctx, o_vo);
+  uint32_t* dcall = dstage_at<uint32_t>(ctx, o_call);
+  uint8_t* dmin = dstage_at<uint8_t>(ctx, o_min);
+  uint64_t* dpo = dstage_at<uint64_t>(ctx, o_po);
+  uint64_t* dco = dstage_at<uint64_t>(ctx, o_co);
+  uint64_t* dpcs = dstage_at<uint64_t>(ctx, o_pcs);
+  int32_t* dst = dstage_at<int32_t>(ctx, o_st);
+  uint32_t* dnv = dstage_at<uint32_t>(ctx, o_nv);
+  uint32_t* dcv = dstage_at<uint32_t>(ctx, o_cv);
+  if ((rc = upload(ctx, dsv, sig_vals, nsig * 4))) return rc;
+  if ((rc = upload(ctx, dso, sig_off, (n + 1) * 8))) return rc;
+  if ((rc = upload(ctx, dcall, call, n * 4))) return rc;
+  if ((rc = upload(ctx, dmin, minimized, n))) return rc;
+  if ((rc = upload(ctx, dpo, prog_off, (nexec + 1) * 8))) return rc;
+  if ((rc = upload(ctx, dco, call_off, (ncalls + 1) * 8))) return rc;
+  if ((rc = upload(ctx, dpcs, pcs, npcs * 8))) return rc;
   const TrIo io{dsv,    dso,  n,   nsig, dcall, dmin, nruns, dpcs, dco, dpo,
                 ncalls, npcs, dst, dno,  ncap ? dnv : nullptr, ncap, dvo, ccap ? dcv : nullptr, ccap};
-  rc = triage_runs(ctx, corpus, io, base);
+  rc = triage_runs(ctx, corpus, io, p);
   if (rc) return rc;
   SG_HIP(hipMemcpyAsync(status, dst, n * 4, hipMemcpyDeviceToHost, ctx->stream));
   SG_HIP(hipMemcpyAsync(new_off, dno, (n + 1) * 8, hipMemcpyDeviceToHost, ctx->stream));

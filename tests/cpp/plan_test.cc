@@ -1,0 +1,125 @@
+// The buffer planner and the offsets check of syzkaller_amd/csrc/sg_plan.h, on
+// the CPU: alignment, no overlap, the total, the region-count overflow, and
+// the three largest staging layouts against the byte counts their entry points
+// summed by hand before they used the planner.
+#include <cstdio>
+#include <vector>
+
+#include "sg_plan.h"
+
+using sg::WsPlan;
+
+static int fails = 0;
+#define CHECK(c)                                              \
+  do {                                                        \
+    if (!(c)) {                                               \
+      printf("FAIL %s:%d: %s\n", __FILE__, __LINE__, #c);     \
+      fails++;                                                \
+    }                                                         \
+  } while (0)
+
+// adds raw[i] bytes per region and expects region i at the sum of want[0 .. i),
+// `want` being the aligned byte counts of the hand-written layout
+static void layout(const char* name, const std::vector<size_t>& raw, const std::vector<size_t>& want, size_t total) {
+  WsPlan p;
+  size_t at = 0;
+  CHECK(raw.size() == want.size());
+  for (size_t i = 0; i < raw.size(); i++) {
+    const size_t o = p.add(raw[i]);
+    if (o != at) {
+      printf("FAIL %s: region %zu at %zu, expected %zu\n", name, i, o, at);
+      fails++;
+    }
+    CHECK(o == p.off[i]);
+    at += want[i];
+  }
+  CHECK(at == total);
+  CHECK(p.total == total);
+  CHECK(!p.overflow);
+}
+
+int main() {
+  {  // alignment, no overlap, the total; a zero-byte region costs nothing
+    const size_t sizes[] = {0, 1, 255, 256, 257, 0, 1};
+    WsPlan p;
+    size_t prev_end = 0;
+    for (size_t b : sizes) {
+      const size_t before = p.total, o = p.add(b);
+      CHECK(o % 256 == 0);
+      CHECK(o >= prev_end);  // starts at or after the end of every earlier region
+      CHECK(o == before);
+      if (b == 0) CHECK(p.total == before);
+      prev_end = o + b;
+      CHECK(p.total == sg::align256(prev_end));  // the end of the last region, rounded up
+      CHECK(p.total >= prev_end && p.total - prev_end < 256);
+    }
+    CHECK(p.n == 7 && !p.overflow);
+    CHECK(p.total == 0 + 256 + 256 + 256 + 512 + 0 + 256);
+    CHECK(sg::align256(0) == 0 && sg::align256(1) == 256 && sg::align256(256) == 256 && sg::align256(257) == 512);
+  }
+  {  // one region past the capacity: reported, laid out, nothing written past off[]
+    struct {
+      WsPlan p;
+      size_t guard[4];
+    } g;
+    for (size_t& x : g.guard) x = 0xA5A5A5A5u;
+    for (int i = 0; i < WsPlan::kMaxRegions; i++) {
+      CHECK(g.p.add(1) == (size_t)i * 256);
+      CHECK(!g.p.overflow);
+    }
+    CHECK(g.p.n == WsPlan::kMaxRegions);
+    const size_t last = g.p.off[WsPlan::kMaxRegions - 1];
+    CHECK(g.p.add(1) == (size_t)WsPlan::kMaxRegions * 256);
+    CHECK(g.p.overflow);
+    CHECK(g.p.n == WsPlan::kMaxRegions);
+    CHECK(g.p.off[WsPlan::kMaxRegions - 1] == last);
+    CHECK(g.p.total == (size_t)(WsPlan::kMaxRegions + 1) * 256);
+    for (size_t x : g.guard) CHECK(x == 0xA5A5A5A5u);
+    CHECK(WsPlan::kMaxRegions >= 29);  // sg_triage_runs_from_kcov's host form
+  }
+  {  // offsets_ok
+    const uint64_t empty[] = {0}, nonzero[] = {1, 2, 3}, ok[] = {0, 2, 2, 5, 5}, first[] = {3, 2, 4, 6, 8},
+                   d_first[] = {0, 4, 3, 6, 8}, d_mid[] = {0, 2, 5, 4, 8}, d_last[] = {0, 2, 4, 6, 5};
+    CHECK(sg::offsets_ok(empty, 0));
+    CHECK(!sg::offsets_ok(nonzero, 2));
+    CHECK(!sg::offsets_ok(nonzero, 0));
+    CHECK(sg::offsets_ok(ok, 4));  // equal neighbours
+    CHECK(!sg::offsets_ok(first, 4));
+    CHECK(!sg::offsets_ok(d_first, 4));
+    CHECK(!sg::offsets_ok(d_mid, 4));
+    CHECK(!sg::offsets_ok(d_last, 4));
+    CHECK(sg::offsets_ok(d_last, 3));  // the decreasing step lies past n
+  }
+  {  // sg_ipc_parse: 131 words, 37 programs, 71 calls
+    const size_t nwords = 131, nprog = 37, nrec = 71;
+    layout("sg_ipc_parse",
+           {nwords * 4 + 4, nwords * 4 + 4, nwords * 4 + 4, (nprog + 1) * 8, (nprog + 1) * 8, (nrec + 1) * 8,
+            (nrec + 1) * 8, (nrec + 1) * 8, nrec * 4 + 4, nrec + 1, nprog * 4 + 4},
+           {768, 768, 768, 512, 512, 768, 768, 768, 512, 256, 256}, 6656);
+  }
+  {  // sg_triage_runs_from_kcov's host form: 67 candidates x 3 runs, 45 calls,
+     // 301 PCs, 77 signals, new_cap >= 77, cov_cap 99: 12 staged regions, then
+     // the body's 17
+    const size_t n = 67, nexec = 201, ncalls = 45, npcs = 301, nsig = 77, ncap = 77, ccap = 99;
+    layout("sg_triage_runs_from_kcov",
+           {nsig * 4 + 4, (n + 1) * 8,      (n + 1) * 8,  (n + 1) * 8,  n * 4,        n,           (nexec + 1) * 8,
+            (ncalls + 1) * 8, npcs * 8 + 8, n * 4,        ncap * 4 + 4, ccap * 4 + 4,
+            npcs * 4 + 4, ncalls + 1,       nexec * 4 + 4, (ncalls + 1) * 8, npcs * 4 + 4, (ncalls + 1) * 8,
+            npcs * 4 + 4, nsig * 4 + 4,     (n + 1) * 8,  n * 4 + 4,    n * 8 + 8,    n * 4 + 4,   n * 4 + 4,
+            n * 4 + 4,    n + 1,            npcs * 4 + 4, npcs * 4 + 4},
+           {512,  768, 768,  768, 512,  256, 1792, 512, 2560, 512, 512, 512,
+            1280, 256, 1024, 512, 1280, 512, 1280, 512, 768,  512, 768, 512, 512, 512, 256, 1280, 1280},
+           23040);
+  }
+  {  // sg_hints_from_kcov's host form: 21 records, 45 calls, 77 value slots: 6
+     // staged regions, then the body's 3
+    const size_t nrecs = 21, ncalls = 45, nvals = 77;
+    layout("sg_hints_from_kcov",
+           {nrecs * 32 + 32, (ncalls + 1) * 8, (ncalls + 1) * 8, nvals * 8 + 8, ncalls * 4 + 4, (nvals + 1) * 8,
+            (ncalls + 1) * 8, (ncalls + 1) * 8, 2 * nrecs * 16 + 16},
+           {768, 512, 512, 768, 256, 768, 512, 512, 768}, 5376);
+  }
+  if (fails) return 1;
+  printf("PASS\n");
+  return 0;
+}

@@ -237,6 +237,34 @@ def test_without_dedup(ctx, ctx_option):
 
 
 @pytest.mark.gpu
+def test_staging_buffer_growth():
+    """Three calls on one fresh context: a few hundred PCs, a batch whose
+    staging (8 B per PC in, 4 B out) is past the buffer's first 16 MiB, the
+    first batch again.  A region laid out past the reserved total would
+    corrupt the second call, a pointer bound before the buffer moved the third."""
+    from syzkaller_amd import cover as C
+
+    rng = np.random.default_rng(48)
+    small = X.to_arrays([draw(rng, 200, 30), [], distinct(rng, 90)])
+    big = X.to_arrays([draw(rng, 55000, 400) for _ in range(40)])
+    assert big[0].size * 12 > 16 << 20
+    c = C.Context()
+    try:
+        got = []
+        for pcs, off in (small, big, small):
+            e_cov, e_off = X.batch(pcs, off)
+            cov, cvo = C.exec_cover(pcs, off, ctx=c)
+            assert np.array_equal(cvo, e_off) and np.array_equal(cov, e_cov), pcs.size
+            e_cov, e_off = X.batch(pcs, off, dedup=False)
+            raw, rwo = C.exec_cover(pcs, off, dedup=False, ctx=c)
+            assert np.array_equal(rwo, e_off) and np.array_equal(raw, e_cov), pcs.size
+            got.append((cov.copy(), cvo.copy(), raw.copy(), rwo.copy()))
+        assert all(np.array_equal(a, b) for a, b in zip(got[0], got[2]))
+    finally:
+        c.close()
+
+
+@pytest.mark.gpu
 def test_capacity_convention_and_arguments(ctx, ctx_option):
     import torch
 

@@ -68,6 +68,31 @@ def test_union_fold_vs_oracle(ctx, multiset):
 
 
 @pytest.mark.gpu
+def test_union_fold_capacity_and_empty_batch(ctx):
+    """cap equal to the folds' total is enough; one below is SG_EINVAL with
+    nothing written (syzsig.h: cap >= off[n] always suffices); no lists at all."""
+    from syzkaller_amd import _lib
+    from syzkaller_amd import cover as C
+    from syzkaller_amd.cover import _p32, _p64
+
+    lib, h = _lib.lib, ctx.h
+    covs = [np.array(x, np.uint32) for x in ([1, 5, 5, 9], [], [5, 7, 0xFFFFFFFF], [2, 9, 11], [9])]
+    grp = np.array([0, 2, 0, 2, 1], np.uint32)
+    vals, off = C.to_csr(covs)
+    ev, eo = O.union_fold(vals, off, grp, 4)
+    total = int(eo[-1])
+    assert 1 < total < vals.size
+    oo, out = np.zeros(5, np.uint64), np.full(total, 0xA5A5A5A5, np.uint32)
+    assert lib.sg_union_fold(h, _p32(vals), _p64(off), len(covs), _p32(grp), 4, _p32(out), total - 1,
+                             _p64(oo)) == _lib.SG_EINVAL
+    assert (out == 0xA5A5A5A5).all()
+    assert lib.sg_union_fold(h, _p32(vals), _p64(off), len(covs), _p32(grp), 4, _p32(out), total, _p64(oo)) == 0
+    assert np.array_equal(oo, eo) and np.array_equal(out, ev)
+    gv, go = C.union_fold(np.zeros(0, np.uint32), np.zeros(1, np.uint64), None, 3, ctx=ctx)
+    assert gv.size == 0 and go.tolist() == [0, 0, 0, 0]
+
+
+@pytest.mark.gpu
 def test_union_fold_key_width_edges(ctx):
     """The sort path packs (group, value, copy index) into 64 bits: 2^20
     groups (20 bits) with a value repeated 4096 times (copy index 4095: 12

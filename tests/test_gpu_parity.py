@@ -618,6 +618,39 @@ def test_accept_batch_groups_and_empty(C):
     assert 0 < sums[0] < 70_000 and sums[1:] == [0, 0]
 
 
+def test_host_forms_on_empty_batches(C):
+    """The staged host forms on nothing: no programs, calls without PCs, no
+    records, records without signal, no polls, no segments, no pairs.  Each
+    equals the oracle (where it has the form) and leaves the sets as they were."""
+    e, z, z3 = np.zeros(0, np.uint32), np.zeros(1, np.uint64), np.zeros(3, np.uint64)
+    for call_off, prog_off in ((z, z), (np.zeros(4, np.uint64), np.array([0, 1, 3], np.uint64))):
+        sig, off = C.exec_signal(e, call_off, prog_off)
+        es, eo = O.exec_signal(e, call_off, prog_off)
+        assert sig.size == 0 == es.size and np.array_equal(off, eo) and not off.any()
+    ms, om = C.SignalSet(), O.OSet()
+    C.SignalAdd(ms, np.array([1, 2, 3], np.uint32))
+    om.add(np.array([1, 2, 3], np.uint32))
+    for off in (z, z3):
+        flags, dv, do = C.triage_batch(ms, None, e, off)
+        ef, ev, eo = O.triage_batch(om, None, e, off)
+        assert np.array_equal(flags, ef) and dv.size == 0 == ev.size and np.array_equal(do, eo)
+        nv, no = C.merge_poll(ms, e, off)
+        ev, eo = O.merge_poll(om, e, off)
+        assert nv.size == 0 == ev.size and np.array_equal(no, eo)
+        gv, go = C.triage_newsig(ms, e, off)
+        assert gv.size == 0 and go.tolist() == [0] * off.size
+        assert C.canonicalize_batch(np.zeros(0, np.uint32), off).tolist() == [0] * (off.size - 1)
+    flags, vals, off = C.triage_traces_queued(ms, None, e, z, z)
+    assert flags.size == 0 and vals.size == 0 and off.tolist() == [0]
+    flags, vals, off = C.triage_traces_queued(ms, None, e, np.zeros(4, np.uint64), np.array([0, 1, 3], np.uint64))
+    assert flags.tolist() == [0, 0, 0] and vals.size == 0 and off.tolist() == [0, 0, 0, 0]
+    gv, go = C.triage_intersect(e, z, e, z)
+    assert gv.size == 0 and go.tolist() == [0] and C.triage_subset(e, z, e, z).size == 0
+    assert C.merge_batch(2, e, [], [], e, [], []) == []  # (SG_OP_UNION)
+    assert np.array_equal(ms.export(), om.export()) and len(ms) == 3
+    ms.close()
+
+
 def test_merge_poll_vs_oracle(C):
     rng = np.random.default_rng(114)
     mm, om = C.SignalSet(), O.OSet()

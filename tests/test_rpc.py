@@ -134,6 +134,41 @@ def test_delta_codec_list_edges(ctx, ctx_option):
 
 
 @pytest.mark.gpu
+def test_delta_codec_capacity_and_empty_batches(ctx):
+    """The capacities of the two host forms (syzsig.h): the encoder always fills
+    out_off and copies the bytes only when they fit; the decoder rejects a
+    capacity below the value count.  And batches of no lists."""
+    from syzkaller_amd import _lib
+    from syzkaller_amd import cover as C
+    from syzkaller_amd.cover import _p8, _p32, _p64
+
+    lib, h, E = _lib.lib, ctx.h, _lib.SG_EINVAL
+    lists = [np.array(x, np.uint32) for x in ([3, 4, 300, 70000], [], [0, 0xFFFFFFFF], [5, 5, 5], [1 << 28])]
+    vals, off = C.to_csr(lists)
+    exp = b"".join(O.delta_encode(v) for v in lists)
+    e_bo = np.concatenate([[0], np.cumsum([len(O.delta_encode(v)) for v in lists])]).astype(np.uint64)
+    n, nb = len(lists), len(exp)
+    bo, out = np.zeros(n + 1, np.uint64), np.full(nb, 0xA5, np.uint8)
+    # one short: the offsets are filled, the bytes untouched; then exact
+    assert lib.sg_delta_encode_batch(h, _p32(vals), _p64(off), n, _p8(out), nb - 1, _p64(bo)) == 0
+    assert np.array_equal(bo, e_bo) and (out == 0xA5).all()
+    assert lib.sg_delta_encode_batch(h, _p32(vals), _p64(off), n, _p8(out), nb, _p64(bo)) == 0
+    assert out.tobytes() == exp
+    data = np.frombuffer(exp, np.uint8).copy()
+    vo, got = np.zeros(n + 1, np.uint64), np.full(vals.size, 0xA5A5A5A5, np.uint32)
+    assert lib.sg_delta_decode_batch(h, _p8(data), _p64(e_bo), n, _p32(got), vals.size - 1, _p64(vo)) == E
+    assert lib.sg_delta_decode_batch(h, _p8(data), _p64(e_bo), n, _p32(got), vals.size, _p64(vo)) == 0
+    assert np.array_equal(vo, off) and np.array_equal(got, vals)
+    # no lists at all
+    z = np.zeros(1, np.uint64)
+    d, do = C.delta_encode(np.zeros(0, np.uint32), z, ctx=ctx)
+    assert d.size == 0 and do.tolist() == [0]
+    v, o = C.delta_decode(b"", z, ctx=ctx)
+    assert v.size == 0 and o.tolist() == [0]
+    assert C.sancov(np.zeros(0, np.uint32), z, ctx=ctx) == []
+
+
+@pytest.mark.gpu
 def test_set_payload_round_trip(ctx):
     from syzkaller_amd import cover as C
 
