@@ -88,7 +88,18 @@ int sg_ctx_kernel_time(sg_ctx* ctx, const char* name, double* ms, uint64_t* laun
  * "exec_cover_general" and "exec_cover_fast_cap"; "triage_runs_wide" (the
  * candidates of the last sg_triage_runs_from_kcov* call that held a cover list
  * not non-decreasing as u32; counted on the device, read here after a stream
- * sync); "owned_big_records" (the records the last
+ * sync), and of the same call the candidates whose inputCover took each route
+ * of the fold, counted and read the same way: "triage_runs_copied" (one list:
+ * a copy), "triage_runs_sorted" (two or more ascending lists of at most
+ * "triage_runs_sort_cap" values together: sorted in LDS), "triage_runs_ranked"
+ * (more values than that: by ranks), "triage_runs_foreach" (a wide list, one
+ * that starts with the sentinel, or offsets that give the lists more values
+ * than the candidate's PCs: the two-pointer loop itself); candidates with another
+ * status than SG_TIN_OK or without a cover list are in none of the four;
+ * "triage_runs_sort_cap" and "tinput_chunk" (constants: the values of new_k
+ * that sg_triage_intersect / sg_triage_subset and the run loop of
+ * sg_triage_runs_from_kcov* hold in LDS at a time); "owned_big_records" (the
+ * records the last
  * ordered-output call -- sg_triage_batch[_dev] with diff lists, sg_merge_poll
  * -- swept a workgroup each instead of a wave each, summed over its record
  * slices; counted on the device and read here after a stream sync, so the

@@ -79,6 +79,10 @@ class Context:
         """sg_ctx_counter: "owner_resets", "owner_floor", "owner_key_space", "max_launch_records",
         the host ingest's "host_copy_bytes" / "host_copy_ns" / "host_wait_ns" / "host_copy_threads",
         "cpu_quota_milli", "hints_candidates", "exec_cover_general" / "exec_cover_fast_cap", "triage_runs_wide",
+        the last triage_runs_from_kcov call's candidates per route of the cover fold "triage_runs_copied" /
+        "triage_runs_sorted" / "triage_runs_ranked" / "triage_runs_foreach", the constants
+        "triage_runs_sort_cap" (the most values the LDS-sort route folds) and "tinput_chunk" (the values of a
+        new list that Intersection holds in LDS at a time),
         the last ordered-output call's "owned_big_records",
         the last merge's pairs per path "merge_pairs_generic" / "merge_pairs_diff_small" /
         "merge_pairs_gap" / "merge_pairs_tile", the last Canonicalize's "canon_wave_lists" /

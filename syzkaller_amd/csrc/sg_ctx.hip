@@ -742,8 +742,17 @@ int sg_ctx_get_option(sg_ctx* ctx, const char* key, int64_t* out) {
   return SG_EINVAL;
 }
 
+// the cover fold's route named by a "triage_runs_" counter's suffix, or -1
+static int tr_route(const char* suffix) {
+  static const char* const names[kTrRoutes] = {"copied", "sorted", "ranked", "foreach"};  // kTrCopied .. kTrForeach
+  for (int i = 0; i < (int)kTrRoutes; i++)
+    if (!strcmp(suffix, names[i])) return i;
+  return -1;
+}
+
 int sg_ctx_counter(sg_ctx* ctx, const char* name, uint64_t* out) {
   if (!ctx || !name || !out) return SG_EINVAL;
+  int route = -1;
   std::lock_guard<std::mutex> g(ctx->mu);
   if (!strcmp(name, "owner_resets"))
     *out = ctx->owner_resets;
@@ -812,7 +821,16 @@ int sg_ctx_counter(sg_ctx* ctx, const char* name, uint64_t* out) {
     SG_HIP(hipStreamSynchronize(ctx->stream));
     SG_HIP(hipMemcpy(&v, ctx->own_big + kTrWideSlot, 4, hipMemcpyDeviceToHost));
     *out = v;
-  } else if (!strcmp(name, "exec_comps_fast_cap"))  // distinct records a call may hold on the fast shape
+  } else if (!strncmp(name, "triage_runs_", 12) && (route = tr_route(name + 12)) >= 0) {  // ... per route of the cover fold
+    uint32_t v = 0;
+    SG_HIP(hipStreamSynchronize(ctx->stream));
+    SG_HIP(hipMemcpy(&v, ctx->own_big + kTrRouteSlot + route, 4, hipMemcpyDeviceToHost));
+    *out = v;
+  } else if (!strcmp(name, "triage_runs_sort_cap"))  // values a cover fold may hold on the LDS-sort route
+    *out = kTrSort;
+  else if (!strcmp(name, "tinput_chunk"))  // values of new_k per LDS chunk of Intersection (sg_tinput.h)
+    *out = kTinChunk;
+  else if (!strcmp(name, "exec_comps_fast_cap"))  // distinct records a call may hold on the fast shape
     *out = SG_EXEC_COMPS_FAST_CAP;
   else if (!strcmp(name, "exec_cover_fast_cap"))  // distinct PCs a call may hold on the fast shape
     *out = SG_EXEC_COVER_FAST_CAP;

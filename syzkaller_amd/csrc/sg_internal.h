@@ -353,8 +353,15 @@ int exec_signal_body(sg_ctx* ctx, const uint32_t* d_pcs, const uint64_t* d_call_
 int exec_cover(sg_ctx* ctx, const uint64_t* d_pcs, const uint64_t* d_call_off, uint64_t ncalls, uint64_t npcs, int dedup,
                uint64_t* d_cov_off, uint32_t* d_cov, uint64_t cov_cap, const uint8_t* sel = nullptr);
 // own_big is 256 B of device counters read by sg_ctx_counter alone: [0]
-// "owned_big_records", [kTrWideSlot] "triage_runs_wide" (sg_triage_runs.hip)
+// "owned_big_records", [kTrWideSlot] "triage_runs_wide" and after it the four
+// routes of the cover fold, "triage_runs_copied" / "_sorted" / "_ranked" /
+// "_foreach" (sg_triage_runs.hip)
 constexpr uint32_t kTrWideSlot = 16;
+constexpr uint32_t kTrRouteSlot = kTrWideSlot + 1;  // + kTrCopied .. kTrForeach
+enum : uint32_t { kTrCopied = 0, kTrSorted = 1, kTrRanked = 2, kTrForeach = 3, kTrRoutes = 4 };
+// read by sg_ctx_counter as "triage_runs_sort_cap" and "tinput_chunk"
+constexpr uint32_t kTrSort = 8192;    // values the cover fold sorts in LDS (64 KiB of keys)
+constexpr uint32_t kTinChunk = 8192;  // values of a per LDS chunk of tin_intersect (32 KiB)
 // Stages of the general path that sg_exec_cover.hip shares (sg_exec_comps.hip;
 // ctx lock held).  EcGen: ng values in v with a copy in ka, a second key buffer
 // kb, pos [ng + 1], flags [ng], and the workspace past `tail` for the sort and

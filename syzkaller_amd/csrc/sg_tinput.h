@@ -12,7 +12,7 @@ namespace tin {
 
 constexpr uint32_t kSentT = 0xFFFFFFFFu;  // cover.go:17
 constexpr int kTB = 256;                  // threads per input
-constexpr uint32_t kCap = 8192;           // a values per LDS chunk (32 KiB)
+constexpr uint32_t kCap = kTinChunk;      // a values per LDS chunk (32 KiB)
 
 // Order-preserving compaction of one round of kTB flags inside a workgroup:
 // returns this thread's rank among the kept ones; *total = kept in the round.

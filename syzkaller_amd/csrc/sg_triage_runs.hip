@@ -32,7 +32,9 @@
 //     foreach merge is then order-dependent; counter "triage_runs_wide") or
 //     with a list of sentinels only (Union can then return nothing and the
 //     next run is copied) runs the two-pointer foreach itself on one lane,
-//     bounded by the two lengths.
+//     bounded by the two lengths.  Each candidate with a cover adds one to
+//     its route's device counter ("triage_runs_copied" / "_sorted" /
+//     "_ranked" / "_foreach"), so a test can prove which route ran.
 //  6. scan_counts gives new_off and cov_off; k_tr_pack writes each payload when
 //     it fits its capacity.
 #include "sg_tinput.h"
@@ -43,7 +45,6 @@ namespace {
 using namespace tin;
 
 constexpr uint32_t kNoCall = 0xFFFFFFFFu;
-constexpr uint32_t kTrSort = 8192;  // values the cover fold sorts in LDS (64 KiB of keys)
 constexpr uint32_t kTrMaxRuns = 8;
 constexpr uint64_t kTrPad = ~0ull;
 
@@ -130,6 +131,7 @@ struct CoverArgs {
   uint8_t* covsrc;  // which of buf[0] / buf[1] holds the candidate's cover
   uint32_t* buf[2];  // [npcs] each: candidate k's slot starts at its first execution's first PC
   uint32_t* wide;
+  uint32_t* routes;  // [kTrRoutes]: the candidates whose cover took each route
 };
 
 // Union (cover.go:63-70) through foreach (:81-102), literally, on one lane
@@ -233,7 +235,10 @@ __global__ __launch_bounds__(kTB) void k_tr_cover(CoverArgs a) {
     const uint32_t* __restrict__ x = a.xcov + s_lo[0];
     const uint32_t L = (uint32_t)min<uint64_t>(s_ln[0], cap);
     for (uint32_t j = tid; j < L; j += kTB) out[j] = x[j];
-    if (tid == 0) a.covlen[k] = L;
+    if (tid == 0) {
+      a.covlen[k] = L;
+      atomicAdd(a.routes + kTrCopied, 1u);
+    }
     return;
   }
   if (wide || s_alls || total > cap) {  // foreach itself, one lane (total > cap: inconsistent offsets)
@@ -253,6 +258,7 @@ __global__ __launch_bounds__(kTB) void k_tr_cover(CoverArgs a) {
       }
       a.covlen[k] = n;
       a.covsrc[k] = (uint8_t)src;
+      atomicAdd(a.routes + kTrForeach, 1u);
     }
     return;
   }
@@ -313,7 +319,10 @@ __global__ __launch_bounds__(kTB) void k_tr_cover(CoverArgs a) {
       }
       n += s_cnt[q];
     }
-    if (tid == 0) a.covlen[k] = (uint32_t)min<uint64_t>(n, cap);
+    if (tid == 0) {
+      a.covlen[k] = (uint32_t)min<uint64_t>(n, cap);
+      atomicAdd(a.routes + kTrRanked, 1u);
+    }
     return;
   }
   // the LDS sort: keys value << 32 | occurrence, the sentinel left out
@@ -366,7 +375,10 @@ __global__ __launch_bounds__(kTB) void k_tr_cover(CoverArgs a) {
     if (keep && n + rk < cap) out[n + rk] = (uint32_t)(key >> 32);
     n += tot;
   }
-  if (tid == 0) a.covlen[k] = (uint32_t)min<uint64_t>(n, cap);
+  if (tid == 0) {
+    a.covlen[k] = (uint32_t)min<uint64_t>(n, cap);
+    atomicAdd(a.routes + kTrSorted, 1u);
+  }
 }
 
 struct PackArgs {
@@ -485,7 +497,8 @@ int triage_runs(sg_ctx* ctx, sg_set* corpus, const TrIo& io, const TrPlan& p) {
   uint32_t* wide = ctx->own_big + kTrWideSlot;
   const dim3 b(256);
   int rc;
-  SG_HIP(hipMemsetAsync(wide, 0, 4, ctx->stream));  // (read by sg_ctx_counter only: no wait here)
+  static_assert(kTrRouteSlot == kTrWideSlot + 1, "wide and the routes are zeroed together");
+  SG_HIP(hipMemsetAsync(wide, 0, 4 * (1 + kTrRoutes), ctx->stream));  // (read by sg_ctx_counter only: no wait here)
   // 1. the calls that count, the truncated PCs
   SG_HIP(hipMemsetAsync(sel, 0, ncalls + 1, ctx->stream));
   hipLaunchKernelGGL(k_tr_select, dim3(div_up(nexec, 256)), b, 0, ctx->stream, io.prog_off, io.call, nexec, io.nruns,
@@ -538,7 +551,7 @@ int triage_runs(sg_ctx* ctx, sg_set* corpus, const TrIo& io, const TrPlan& p) {
     ScopedTimer tm(ctx, "triage_runs_cover");
     CoverArgs ca{io.nruns, ncalls,      npcs,   io.minimized, selcall, io.prog_off, io.call_off, xcov_off, xcov, state,
                  cur_len,  io.status,   newlen, covlen,       covsrc,  {buf0, buf1},
-                 wide};
+                 wide,     ctx->own_big + kTrRouteSlot};
     hipLaunchKernelGGL(k_tr_cover, dim3((uint32_t)n), dim3(kTB), 0, ctx->stream, ca);
   }
   SG_HIP(hipGetLastError());

@@ -115,3 +115,106 @@ def test_triage_intersect_and_subset_vs_oracle(ctx):
     gv, go = C.triage_intersect(np.zeros(0, np.uint32), z, rv, ro, ctx=ctx)
     assert gv.size == 0 and not go.any()
     assert C.triage_subset(np.zeros(0, np.uint32), z, rv, ro, ctx=ctx).all()
+
+
+# ---- the LDS chunks of Intersection (counter "tinput_chunk") ---------------------------
+def _ascending(L, seed):
+    """L distinct ascending values: a canonical new list."""
+    return (7 + np.cumsum(np.random.default_rng(seed).integers(1, 5, size=L))).astype(np.uint32)
+
+
+def _edge_batch(C, pick, seed):
+    """New lists of C - 1, C, C + 1, 2C and 2C + 1 values with short lists between them; r_k = pick(new_k, rng)."""
+    rng = np.random.default_rng(seed)
+    news, rs = [], []
+    for i, L in enumerate((C - 1, 3, C, 0, C + 1, 300, 2 * C, 1, 2 * C + 1)):
+        a = _ascending(L, seed + i)
+        news.append(a)
+        rs.append(np.asarray(pick(a, rng), dtype=np.uint32))
+    return news, rs
+
+
+def _both(ctx, news, rs, tag):
+    """sg_triage_intersect and sg_triage_subset against the oracle; returns the kept lists."""
+    from syzkaller_amd import cover as C
+
+    nv, no = _csr(news)
+    rv, ro = _csr(rs)
+    gv, go = C.triage_intersect(nv, no, rv, ro, ctx=ctx)
+    ev, eo = O.triage_intersect(nv, no, rv, ro)
+    assert np.array_equal(go, eo), tag
+    assert np.array_equal(gv, ev), tag
+    gok = C.triage_subset(nv, no, rv, ro, ctx=ctx)
+    assert np.array_equal(gok, O.triage_subset(nv, no, rv, ro)), tag
+    return [gv[int(go[k]):int(go[k + 1])] for k in range(len(news))], gok
+
+
+def _shuffled_twice(a, rng):
+    r = np.concatenate([a, a[: a.size // 3]])
+    rng.shuffle(r)
+    return r
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("what", ("everything", "nothing", "chunk 1 only", "chunk ends", "unsorted with duplicates"))
+def test_intersect_and_subset_at_the_chunk_edges(ctx, what):
+    C = ctx.counter("tinput_chunk")
+    assert C == 8192
+    ends = lambda a: a[[j for j in (C - 1, C, 2 * C - 1, 2 * C) if j < a.size]]  # noqa: E731
+    pick = {"everything": lambda a, rng: rng.permutation(a),
+            "nothing": lambda a, rng: np.setdiff1d(a + 1, a),   # next to the values, never equal
+            "chunk 1 only": lambda a, rng: a[C:2 * C],
+            "chunk ends": lambda a, rng: ends(a),
+            "unsorted with duplicates": lambda a, rng: _shuffled_twice(a[rng.random(a.size) < 0.7], rng)}[what]
+    news, rs = _edge_batch(C, pick, 40)
+    kept, ok = _both(ctx, news, rs, what)
+    for a, r, k, o in zip(news, rs, kept, ok):
+        assert o == (k.size == a.size)  # canonical lists: the predicate is "everything was kept"
+        if what == "everything":
+            assert np.array_equal(k, a) and o
+        elif what == "nothing":
+            assert k.size == 0 and o == (a.size == 0)
+        elif what == "chunk 1 only":
+            assert np.array_equal(k, a[C:2 * C])
+        elif what == "chunk ends":
+            assert np.array_equal(k, ends(a))
+
+
+@pytest.mark.gpu
+def test_intersect_runs_of_equal_values_across_the_chunk_edges(ctx):
+    C = ctx.counter("tinput_chunk")
+    base = _ascending(2 * C + 40, 41)
+    x, y, top = int(base[C - 2]), int(base[2 * C - 2]), 0xFFFFFFFF
+    one = base.copy()
+    one[C - 2:C + 3] = x                      # one value over indices C - 2 .. C + 2
+    two = one.copy()
+    two[2 * C - 2:2 * C + 3] = y              # ... and another over the second edge
+    three = base.copy()
+    three[2 * C - 2:2 * C + 3] = y            # the second run alone: chunk 0 is all distinct
+    assert (np.diff(two.astype(np.int64)) >= 0).all() and (two == x).sum() == 5 and (two == y).sum() == 5
+    last = np.concatenate([base[:C], [top]]).astype(np.uint32)  # 0xFFFFFFFF as the last value, the first of chunk 1
+    lasts = np.concatenate([base[:C - 1], [top]]).astype(np.uint32)  # ... the last of chunk 0
+    cases = [("present", one, np.array([x], np.uint32), [x]),
+             ("absent", one, np.setdiff1d(base, [x]), None),
+             ("both present, everything kept", two, two[::-1].copy(), None),
+             ("chunk 0, then y", two, np.concatenate([two[:C], [y]]).astype(np.uint32), np.unique(two[:C]).tolist() + [y]),
+             # chunk 0 is kept whole: the value before chunk 1 has been written in place by the time it is read
+             ("chunk 0 whole, then y", three, np.concatenate([three[:C], [y]]).astype(np.uint32), three[:C].tolist() + [y]),
+             ("chunks 0 and 1 of r, the second run", three, three[:2 * C][::-1].copy(), np.unique(three[:2 * C]).tolist()),
+             ("the second run, everything kept", three, three, np.unique(three).tolist()),
+             ("only y", two, np.array([y, y], np.uint32), [y]),
+             ("both absent", two, np.setdiff1d(base, [x, y]), None),
+             ("sentinel first of chunk 1", last, last, None),
+             ("sentinel last of chunk 0", lasts, lasts[::-1].copy(), None),
+             ("sentinel alone in r", last, np.array([top], np.uint32), [])]
+    kept, ok = _both(ctx, [c[1] for c in cases], [c[2] for c in cases], "runs")
+    for (name, a, r, want), k, o in zip(cases, kept, ok):
+        if want is not None:
+            assert k.tolist() == want, name
+        assert (k == x).sum() == int(x in r and x in a) and (k == y).sum() == int(y in r and y in a), name  # one copy or none
+        assert top not in k and (np.diff(k.astype(np.int64)) > 0).all(), name
+    byname = {c[0]: k for c, k in zip(cases, kept)}
+    assert byname["both present, everything kept"].tolist() == np.unique(two).tolist()
+    assert byname["sentinel first of chunk 1"].tolist() == base[:C].tolist()
+    assert byname["sentinel last of chunk 0"].tolist() == base[:C - 1].tolist()
+    assert not ok.any()  # no list is kept whole: each has repeats or the sentinel

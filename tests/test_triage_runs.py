@@ -14,6 +14,7 @@ import pytest
 
 from oracle import pyoracle as O
 from tests import exec_cover_oracle as XC
+from tests import triage_runs_cases as K
 from tests import triage_runs_oracle as TR
 from tests.conftest import ROOT
 
@@ -296,8 +297,16 @@ def _same(got, exp, tag):
         assert np.array_equal(g, e), (tag, name)
 
 
-def _check(ctx, ctx_option, corpus_vals, cands, exp, wide=None, paths=(-1, 0)):
+def _check(ctx, ctx_option, corpus_vals, cands, exp, wide=None, paths=(-1, 0), counters=None):
+    """Host form and device form on each exec_cover path against exp; counters: the device counters (name ->
+    value) every one of those calls leaves."""
     from syzkaller_amd import cover as C
+
+    def counted(tag):
+        if wide is not None:
+            assert ctx.counter("triage_runs_wide") == wide, tag
+        got = {name: ctx.counter(name) for name in counters or ()}
+        assert got == (counters or {}), tag
 
     corpus = _corpus(ctx, corpus_vals)
     before = corpus.export()
@@ -305,14 +314,12 @@ def _check(ctx, ctx_option, corpus_vals, cands, exp, wide=None, paths=(-1, 0)):
     for path in paths:
         ctx_option(ctx, "exec_cover_path", path)
         _same(C.triage_runs_from_kcov(corpus, *arrs, ctx=ctx), exp, ("host", path))
-        if wide is not None:
-            assert ctx.counter("triage_runs_wide") == wide, path
+        counted(("host", path))
         st, nv, no, cv, vo = _dev(ctx, corpus, arrs)
         n_new, n_cov = int(exp[2][-1]), int(exp[4][-1])
         _same((st, nv[:n_new], no, cv[:n_cov], vo), exp, ("dev", path))
         assert (nv[n_new:] == FILL32).all() and (cv[n_cov:] == FILL32).all(), path
-        if wide is not None:
-            assert ctx.counter("triage_runs_wide") == wide, path
+        counted(("dev", path))
     assert np.array_equal(corpus.export(), before)  # corpusSignal is only read
     corpus.close()
 
@@ -324,7 +331,10 @@ def test_planted_candidates(ctx, ctx_option):
     st = exp[0].tolist()
     assert st[:12] == [TR.NO_NEW, TR.NO_NEW, TR.OK, TR.OK, TR.OK, TR.NOT_EXECUTED, TR.NOT_EXECUTED, TR.OK, TR.NOT_EXECUTED,
                        TR.OK, TR.FLAKY, TR.FLAKY]
-    _check(ctx, ctx_option, corpus, cands, exp, wide=1)
+    oc = O.OSet(corpus)
+    routes = K.counters([K.shape(oc, c) for c in cands])  # the route of every cover fold, from the oracle alone
+    assert routes["triage_runs_ranked"] == 1 and routes["triage_runs_foreach"] == 1 and routes["triage_runs_wide"] == 1
+    _check(ctx, ctx_option, corpus, cands, exp, wide=1, counters=routes)
 
 
 @pytest.mark.gpu
