@@ -611,9 +611,10 @@ int sg_exec_cover_dev(sg_ctx* ctx, const uint64_t* d_pcs, const uint64_t* d_call
  * status (n); new_off (n + 1) / new_vals and cov_off (n + 1) / cov_vals: both
  * lists are empty for every status but SG_TIN_OK.  Offsets are always filled;
  * each payload is written only when it fits its own capacity (sig_off[n] and
- * call_off[ncalls] values always suffice).  The caller then runs prog.Minimize
- * with sg_triage_subset and sends RpcInput{Signal: Canonicalize(inp.signal),
- * Cover: cover} (:596-603).
+ * call_off[ncalls] values always suffice).  prog.Minimize's predicate over the
+ * same raw buffers is sg_minimize_pred_from_kcov (below), which takes new_vals /
+ * new_off as they are; the caller then sends RpcInput{Signal:
+ * Canonicalize(inp.signal), Cover: cover} (:596-603).
  * A Cover_i that is not non-decreasing as u32 (PCs that differ above bit 31)
  * makes foreach order-dependent; such candidates are folded by the literal
  * two-pointer loop and stay exact (counter "triage_runs_wide": the candidates of
@@ -648,6 +649,71 @@ int sg_triage_runs_from_kcov_dev(sg_ctx* ctx, sg_set* corpus, const uint32_t* d_
 				 const uint64_t* d_prog_off, uint64_t ncalls, uint64_t npcs, int32_t* d_status,
 				 uint64_t* d_new_off, uint32_t* d_new_vals, uint64_t new_cap, uint64_t* d_cov_off,
 				 uint32_t* d_cov_vals, uint64_t cov_cap);
+
+/* ---- minimisation predicate from raw buffers (syz-fuzzer/fuzzer.go:578-591) - */
+/* The closure triageInput hands to prog.Minimize (prog/mutation.go:256-450,
+ * which calls it once per removable call and once per simplified argument),
+ * for a batch of n attempts: one predicate call each, drawn from any number of
+ * concurrent Minimize runs.  new_vals / new_off (ncand + 1) are the newSignal
+ * lists, each sorted non-decreasing (canonical lists are the normal case:
+ * sg_triage_runs_from_kcov's output); they are only read.  Attempt e tests list
+ * cand[e] < ncand (many attempts may share a list, in any order) on call
+ * call[e] (call1) of its execution, which owns calls prog_off[e] ..
+ * prog_off[e+1] (n + 1 offsets); call c owns pcs[call_off[c] .. call_off[c+1]),
+ * u64 PCs laid out as sg_triage_runs_from_kcov's.  By definition Signal_e is
+ * call[e]'s list from sg_exec_signal on the execution's PCs truncated as
+ * (uint32_t)pc, the dedup table fresh per execution and shared by its calls in
+ * order.  status[e]:
+ *  - SG_MP_NOT_EXECUTED (:580-582): the execution has fewer than call[e] + 1
+ *    calls, or Signal_e is empty.  This comes first: an empty list against an
+ *    empty Signal_e is not SG_MP_OK.
+ *  - SG_MP_OK: sg_triage_subset(list, Signal_e) says 1, that is the list is
+ *    strictly increasing, holds no 0xFFFFFFFF, and each of its values occurs in
+ *    Signal_e (:584-590); an empty list is SG_MP_OK.
+ *  - SG_MP_LOST (:587-589) otherwise; a list with a repeat or the sentinel always.
+ * With maxsig (newsig nullable; newsig only with maxsig) execute()'s own check
+ * (:665-691) runs first, over all calls of all attempts in batch order, exactly
+ * as sg_triage_traces_dev on the truncated PCs: rec_new[c] for every call and
+ * both set updates.  sig_off (ncalls + 1) / sig_vals are then laid out as
+ * sg_triage_traces_queued's: the executor-exact list of every call that is
+ * queued (rec_new[c] != 0) or selected (call[e] of its execution), an empty
+ * list for every other call.  The executor runs once, up to the last such call
+ * of each execution.  sig_off is always filled; sig_vals (capacity sig_cap) is
+ * written only when sig_off[ncalls] <= sig_cap; call_off[ncalls] values always
+ * suffice.  Without maxsig no set is read or written, only the selected calls
+ * run, and rec_new / sig_off / sig_vals are ignored (they may be NULL).
+ * SG_EINVAL: a NULL ctx, new_off, prog_off or call_off; with attempts, a NULL
+ * cand, call or status; values or PCs NULL where present; a set of another
+ * context; newsig without maxsig; with maxsig, a NULL sig_off, a NULL rec_new
+ * with calls, or sig_vals NULL with sig_cap > 0; offsets that do not start at 0
+ * or decrease; cand[e] >= ncand, or a list that is not sorted; attempts without
+ * any list; 2^28 attempts, 2^31 calls, 2^32 lists, list values or PCs or more
+ * (with maxsig also sg_triage_traces_dev's limits).  n == 0 is SG_OK.
+ * The host form stages once and reads back the status, then with maxsig the
+ * flags, the offsets and the lists. */
+#define SG_MP_OK 0
+#define SG_MP_NOT_EXECUTED 1 /* fuzzer.go:580-582 */
+#define SG_MP_LOST 2         /* :587-589 */
+int sg_minimize_pred_from_kcov(sg_ctx* ctx, sg_set* maxsig, sg_set* newsig, const uint32_t* new_vals,
+			       const uint64_t* new_off, size_t ncand, const uint32_t* cand, const uint32_t* call, size_t n,
+			       const uint64_t* pcs, const uint64_t* call_off, const uint64_t* prog_off, int32_t* status,
+			       uint8_t* rec_new, uint64_t* sig_off, uint32_t* sig_vals, size_t sig_cap);
+/* Device form (nnew = new_off[ncand], ncalls = prog_off[n], npcs =
+ * call_off[ncalls]): every pointer is device memory, e.g. d_new_vals / d_new_off
+ * as sg_triage_runs_from_kcov_dev left them.  The offsets, cand and the lists'
+ * order cannot be checked and are trusted as sg_exec_signal_dev trusts its
+ * offsets (list ranges are clamped to nnew, cand to ncand - 1).  Stream-ordered:
+ * it adds no host wait of its own.  The waits its stages have: with maxsig,
+ * those of sg_triage_traces_dev (one small device-to-host read per record
+ * slice for a batch of more than 2^24 calls); without maxsig none.  Its
+ * intermediates (the truncated PCs, the marks and the lists: 8 bytes per PC,
+ * 9 per call) live in the context's grow-only device staging buffer, which
+ * waits for the stream only when it has to grow. */
+int sg_minimize_pred_from_kcov_dev(sg_ctx* ctx, sg_set* maxsig, sg_set* newsig, const uint32_t* d_new_vals,
+				   const uint64_t* d_new_off, uint64_t ncand, uint64_t nnew, const uint32_t* d_cand,
+				   const uint32_t* d_call, uint64_t n, const uint64_t* d_pcs, const uint64_t* d_call_off,
+				   const uint64_t* d_prog_off, uint64_t ncalls, uint64_t npcs, int32_t* d_status,
+				   uint8_t* d_rec_new, uint64_t* d_sig_off, uint32_t* d_sig_vals, uint64_t sig_cap);
 
 /* ---- synthetic Zipf traces (bench / test input generator) ----------------- */
 /* Zipf(s) over `nranks` PC ranks mapped through a permutation seeded by

@@ -22,6 +22,10 @@ TIN_NO_NEW = 1
 TIN_NOT_EXECUTED = 2
 TIN_FLAKY = 3
 
+MP_OK = 0  # sg_minimize_pred_from_kcov's statuses (include/syzsig.h SG_MP_*)
+MP_NOT_EXECUTED = 1
+MP_LOST = 2
+
 OP_DIFFERENCE = 0
 OP_SYMDIFF = 1
 OP_UNION = 2
@@ -123,6 +127,11 @@ SIGNATURES = {
     "sg_triage_runs_from_kcov_dev": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_uint64, c_uint64, c_void_p,
                                              c_void_p, c_uint32, c_void_p, c_void_p, c_void_p, c_uint64, c_uint64,
                                              c_void_p, c_void_p, c_void_p, c_uint64, c_void_p, c_void_p, c_uint64]),
+    "sg_minimize_pred_from_kcov": (c_int, [c_void_p, c_void_p, c_void_p, P32, P64, c_size_t, P32, P32, c_size_t, P64, P64,
+                                           P64, POINTER(c_int32), P8, P64, P32, c_size_t]),
+    "sg_minimize_pred_from_kcov_dev": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_uint64, c_uint64,
+                                               c_void_p, c_void_p, c_uint64, c_void_p, c_void_p, c_void_p, c_uint64,
+                                               c_uint64, c_void_p, c_void_p, c_void_p, c_void_p, c_uint64]),
     "sg_gen_zipf_traces_dev": (c_int, [c_void_p, c_uint64, c_uint64, c_double, c_uint32, c_uint64, c_uint64, c_uint32,
                                        c_uint32, c_void_p]),
     "sg_gen_population_traces_dev": (c_int, [c_void_p, c_uint64, c_uint64, c_uint64, c_uint64, c_double, c_double,

@@ -544,6 +544,55 @@ def TriageInput(corpus, signal, call, runs, minimized=False):
     return int(status[0]), nv, cv
 
 
+def minimize_pred_from_kcov(new_vals, new_off, cand, call, pcs, call_off, prog_off, maxset=None, newset=None, ctx=None):
+    """The predicate triageInput hands to prog.Minimize (fuzzer.go:578-591) for n
+    attempts from the raw KCOV buffers of their executions: attempt e tests the
+    sorted list new_vals[new_off[cand[e]]:new_off[cand[e] + 1]] on call call[e]
+    of execution e, whose calls are prog_off[e] .. prog_off[e + 1], call c's u64
+    PCs pcs[call_off[c]:call_off[c + 1]].  Returns status int32[n] (MP_OK,
+    MP_NOT_EXECUTED, MP_LOST) and, with maxset, also (rec_new, sig_vals,
+    sig_off): execute()'s new-signal check of every call (both sets updated, as
+    triage_traces) and the executor's lists of the queued or selected calls."""
+    nv, no, cd, cl = _u32(new_vals), _u64(new_off), _u32(cand), _u32(call)
+    p, co, po = _u64(pcs), _u64(call_off), _u64(prog_off)
+    n, ncalls = po.size - 1, co.size - 1
+    assert cd.size == n and cl.size == n and ncalls == int(po[-1]) and p.size == int(co[-1]) and nv.size == int(no[-1])
+    if newset is not None and maxset is None:
+        raise ValueError("newset only with maxset")
+    c = ctx if ctx is not None else (maxset.ctx if maxset is not None else default_context())
+    status = np.empty(max(n, 1), dtype=np.int32)
+    rec_new = np.zeros(max(ncalls, 1), dtype=np.uint8)
+    sv, so = np.empty(max(p.size, 1), dtype=U32), np.zeros(ncalls + 1, dtype=U64)
+    _lib.call("sg_minimize_pred_from_kcov", c.h, maxset.h if maxset is not None else None,
+              newset.h if newset is not None else None, _p32(nv), _p64(no), no.size - 1, _p32(cd), _p32(cl), n, _p64(p),
+              _p64(co), _p64(po), status.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), _p8(rec_new), _p64(so),
+              _p32(sv), p.size)
+    if maxset is None:
+        return status[:n]
+    return status[:n], rec_new[:ncalls], sv[: int(so[-1])], so
+
+
+class MinimizePred:
+    """The closure of fuzzer.go:578-591 for one candidate: pred(run, call1) ->
+    bool, where run is the shortened program's execution as a list of per-call
+    u64 PC arrays (as in TriageInput) and new_signal is triageInput's newSignal.
+    With maxset (and newset) every call also goes through execute()'s
+    new-signal check, as the reference's execute() does."""
+
+    def __init__(self, new_signal, maxset=None, newset=None, ctx=None):
+        self.new = _u32(new_signal)
+        self.maxset, self.newset, self.ctx = maxset, newset, ctx
+
+    def __call__(self, run, call1):
+        calls = [np.asarray(c, dtype=U64).reshape(-1) for c in run]
+        call_off = np.concatenate([[0], np.cumsum([c.size for c in calls])]).astype(U64)
+        pcs = np.concatenate(calls) if calls else np.zeros(0, dtype=U64)
+        res = minimize_pred_from_kcov(self.new, [0, self.new.size], [0], [call1], pcs, call_off, [0, len(calls)],
+                                      self.maxset, self.newset, self.ctx)
+        status = res if self.maxset is None else res[0]
+        return int(status[0]) == _lib.MP_OK
+
+
 def cover_uncovered(cov, base, sym_start, sym_end, all_pcs, ctx=None):
     """syz-manager/cover.go:91-103 + uncoveredPcsInFuncs (:257-307); ascending."""
     c, ss, se, ap = _u32(cov), _u64(sym_start), _u64(sym_end), _u64(all_pcs)

@@ -12,6 +12,7 @@
 // Stages, all on the context's stream:
 //  1. k_tr_select marks call[k] of every execution (an execution with fewer
 //     calls is len(info) == 0); k_tr_trunc truncates the PCs (executor.h:394).
+//     Both are sg_runs.h's, shared with sg_minimize_pred.hip.
 //  2. Signal_i: the queued exec-signal path of sg_exec.hip (exec_signal_body
 //     with the marks as its queued flags: each execution runs up to its call).
 //     Cover_i: exec_cover (sg_exec_cover.hip) restricted to the marked calls.
@@ -37,6 +38,7 @@
 //     "_ranked" / "_foreach"), so a test can prove which route ran.
 //  6. scan_counts gives new_off and cov_off; k_tr_pack writes each payload when
 //     it fits its capacity.
+#include "sg_runs.h"
 #include "sg_tinput.h"
 
 namespace sg {
@@ -44,7 +46,6 @@ namespace {
 
 using namespace tin;
 
-constexpr uint32_t kNoCall = 0xFFFFFFFFu;
 constexpr uint32_t kTrMaxRuns = 8;
 constexpr uint64_t kTrPad = ~0ull;
 
@@ -52,25 +53,6 @@ constexpr uint64_t kTrPad = ~0ull;
 // (counted: bit i = run i's Signal took part, so its Cover does)
 __host__ __device__ inline uint32_t st_make(uint32_t done, uint32_t status, uint32_t skipped, uint32_t counted) {
   return done | (status << 8) | (skipped << 16) | (counted << 24);
-}
-
-__global__ void k_tr_select(const uint64_t* __restrict__ prog_off, const uint32_t* __restrict__ call, uint64_t nexec,
-                            uint32_t nruns, uint64_t ncalls, uint32_t* __restrict__ selcall, uint8_t* __restrict__ sel) {
-  const uint64_t e = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (e >= nexec) return;
-  const uint64_t c0 = min(prog_off[e], ncalls), c1 = min(max(prog_off[e + 1], c0), ncalls);
-  const uint64_t want = call[e / nruns];
-  if (c1 - c0 > want) {  // fuzzer.go:547 / :558: info[inp.call] exists
-    selcall[e] = (uint32_t)(c0 + want);
-    sel[c0 + want] = 1;
-  } else {
-    selcall[e] = kNoCall;
-  }
-}
-
-__global__ void k_tr_trunc(const uint64_t* __restrict__ pcs, uint64_t n, uint32_t* __restrict__ out) {
-  const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
-  for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) out[i] = (uint32_t)pcs[i];
 }
 
 struct RoundArgs {
