@@ -136,7 +136,7 @@ int sg_ctx_counter(sg_ctx* ctx, const char* name, uint64_t* out);
  *   "fold_map"             sg_union_fold's one-group byte map (-1 by range, 0 never)
  *   "minimize_filter"      Minimize's value filter (1 on, 0 off)
  *   "minimize_filter_ranks" Minimize's phase-A inputs (0: the default 4)
- *   "report_direct"        sg_cover_uncovered's global-search form at any size (1)
+ *   "report_direct"        sg_cover_uncovered's and sg_cover_lines' global-search form at any size (1)
  *   "rpc_encode_elems"     delta encode form (-1 by shape, 0 per list, 1 per element)
  *   "rpc_decode_blocks"    delta decode form (-1 by shape, 0 per list, 1 per block)
  *   "host_slice"           host ingest: entries per record slice (0: 64 Mi)
@@ -741,6 +741,76 @@ int sg_gen_population_traces_dev(sg_ctx* ctx, uint64_t universe_seed, uint64_t p
 int sg_cover_uncovered(sg_ctx* ctx, const uint32_t* cov, size_t ncov, uint32_t base, const uint64_t* sym_start,
 		       const uint64_t* sym_end, size_t nsym, const uint64_t* all_pcs, size_t nall, uint64_t* out,
 		       size_t* nout);
+
+/* ---- cover report line tables (syz-manager/cover.go:91-120, :165-196) ------- */
+/* The rest of the /cover page's set math: generateCoverHtml
+ * (syz-manager/cover.go:91-120) symbolises the covered and the uncovered PCs
+ * and fileSet (syz-manager/cover.go:165-196) folds the frames into per-file
+ * line lists, all of it under mgr.mu (httpCover, syz-manager/html.go:169-194).
+ * The frames of a PC depend on vmlinux alone and the PCs a report can ask
+ * about are known at start-up (allCoverPCs, cover.go:64-89), so the caller
+ * symbolises them once into a table that stays on the device; a report is
+ * then one call with no addr2line in it.
+ *
+ * sg_cover_table_create: sym_start / sym_end / all_pcs are sg_cover_uncovered's
+ * inputs under the same ordering conditions.  tab_pcs (sorted, unique) are the
+ * symbolised PCs and must contain every all_pcs entry; the frames of
+ * tab_pcs[j] are entries frame_off[j] .. frame_off[j+1] (frame_off has
+ * ntab + 1 entries, also when ntab == 0) in `addr2line -afi` order, zero
+ * frames being legal (symbolizer.go:173 drops "??" and line <= 0).  A frame is
+ * (file id < nfiles, line > 0, func id < nfuncs).  The caller interns the
+ * strings: fileSet compares File and Func by string, so equal strings MUST get
+ * equal ids (and different strings different ids).  Everything is checked on
+ * the host before the context is touched (SG_EINVAL, sg_last_error says
+ * what): null pointers, a count or the frame total >= 2^32 - 1, symbol or PC
+ * order, frame_off not starting at 0 or decreasing, an id out of range or
+ * line 0, a call site that is not in tab_pcs.  The table owns its device
+ * memory (as an sg_set its words), is immutable, belongs to `ctx` and must be
+ * destroyed before it.  Every distinct (file, line) pair of the table is a
+ * slot; sg_cover_table_slots returns their number, the capacity a report's
+ * lines / covered need.
+ *
+ * sg_cover_lines: pcs[i] = RestorePC(cov[i], base) - 5; uncovered =
+ * uncoveredPcsInFuncs(pcs) exactly as sg_cover_uncovered computes it (query
+ * order kept); the covered frames are the frames of every pcs[i] (duplicates
+ * change nothing).  fileSet: every covered frame sets files[file][line] = true
+ * and funcs[func] = true; an uncovered frame is kept only if its func is in
+ * funcs (inlined covered frames count) and then sets files[file][line] = false
+ * unless the line is there already.  A PC can be both (overlapping symbols):
+ * its lines are covered.  File f's list is lines[file_off[f] .. file_off[f+1]),
+ * ascending, covered[] (1 / 0) alongside; a file with no entry gets an empty
+ * range (the reference's map has no key for it).  file_seen (nfiles, nullable):
+ * bit 0 = the file appears in a covered frame, bit 1 = in an uncovered frame
+ * before the funcs filter -- what symbolize's path prefix (cover.go:358-372) is
+ * taken over.  Prefix strings and HTML stay with the caller; note that the
+ * reference's `prefix == ""` reset makes the prefix depend on frame order only
+ * when file names share no first byte.  *ncovered_frames = the frames of the
+ * distinct covered PCs found in the table: 0 is the reference's "does not have
+ * debug info" error (cover.go:113-115).  missing (capacity ncov; for the set
+ * form the set's size) receives the distinct covered PCs that are not in
+ * tab_pcs, ascending, *nmissing of them: they take part in
+ * uncoveredPcsInFuncs (which needs no symbols) and contribute no frames; when
+ * there are any the caller symbolises them, builds a table that contains them
+ * and calls again.  ncov == 0: all-empty outputs and SG_OK (the reference's
+ * "No coverage data available" is the caller's).  Nothing past file_off[nfiles]
+ * entries of lines / covered and *nmissing entries of missing is meaningful.
+ *
+ * sg_cover_lines_set: the same for the members of `cov` in ascending order --
+ * the reference's canonical cover order -- e.g. the corpus cover that
+ * sg_accept_batch maintains; nothing is uploaded. */
+typedef struct sg_cover_table sg_cover_table;
+int sg_cover_table_create(sg_ctx* ctx, const uint64_t* sym_start, const uint64_t* sym_end, size_t nsym,
+			  const uint64_t* all_pcs, size_t nall, const uint64_t* tab_pcs, size_t ntab,
+			  const uint64_t* frame_off, const uint32_t* frame_file, const uint32_t* frame_line,
+			  const uint32_t* frame_func, uint32_t nfiles, uint32_t nfuncs, sg_cover_table** out);
+void sg_cover_table_destroy(sg_cover_table* table);
+int sg_cover_table_slots(sg_cover_table* table, uint64_t* nslots);
+int sg_cover_lines(sg_cover_table* table, const uint32_t* cov, size_t ncov, uint32_t base, uint64_t* file_off,
+		   uint32_t* lines, uint8_t* covered, uint8_t* file_seen, uint64_t* ncovered_frames, uint64_t* missing,
+		   size_t* nmissing);
+int sg_cover_lines_set(sg_cover_table* table, sg_set* cov, uint32_t base, uint64_t* file_off, uint32_t* lines,
+		       uint8_t* covered, uint8_t* file_seen, uint64_t* ncovered_frames, uint64_t* missing,
+		       size_t* nmissing);
 
 /* ---- executor output ingest (pkg/ipc/ipc_linux.go:168-307) ---------------- */
 /* readOutCoverage over a batch of programs.  Program p's output region (the

@@ -137,6 +137,12 @@ SIGNATURES = {
     "sg_gen_population_traces_dev": (c_int, [c_void_p, c_uint64, c_uint64, c_uint64, c_uint64, c_double, c_double,
                                              c_uint32, c_uint64, c_uint64, c_uint32, c_uint32, c_void_p]),
     "sg_cover_uncovered": (c_int, [c_void_p, P32, c_size_t, c_uint32, P64, P64, c_size_t, P64, c_size_t, P64, PSZ]),
+    "sg_cover_table_create": (c_int, [c_void_p, P64, P64, c_size_t, P64, c_size_t, P64, c_size_t, P64, P32, P32, P32,
+                                      c_uint32, c_uint32, POINTER(c_void_p)]),
+    "sg_cover_table_destroy": (None, [c_void_p]),
+    "sg_cover_table_slots": (c_int, [c_void_p, P64]),
+    "sg_cover_lines": (c_int, [c_void_p, P32, c_size_t, c_uint32, P64, P32, P8, P8, P64, P64, PSZ]),
+    "sg_cover_lines_set": (c_int, [c_void_p, c_void_p, c_uint32, P64, P32, P8, P8, P64, P64, PSZ]),
     "sg_ipc_parse": (c_int, [c_void_p, P32, P64, P64, P32, c_size_t, POINTER(c_int64), P8, POINTER(c_int32), P64, P32,
                              P64, P32]),
     "sg_ipc_parse_dev": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_uint64, c_uint64, c_void_p,

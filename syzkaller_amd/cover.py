@@ -603,6 +603,127 @@ def cover_uncovered(cov, base, sym_start, sym_end, all_pcs, ctx=None):
     return out[: n.value]
 
 
+class CoverTable:
+    """sg_cover_table: the symbols, the call sites and the frames of every
+    symbolised PC, on the device (include/syzsig.h).  The frames of tab_pcs[j]
+    are entries frame_off[j] .. frame_off[j+1] of frame_file / frame_line /
+    frame_func; the caller interns File and Func strings to ids (equal strings,
+    equal ids).  Close it before its context."""
+
+    def __init__(self, sym_start, sym_end, all_pcs, tab_pcs, frame_off, frame_file, frame_line, frame_func, nfiles,
+                 nfuncs, ctx=None):
+        self.ctx = _ctx(ctx)
+        ss, se, ap, tp, fo = _u64(sym_start), _u64(sym_end), _u64(all_pcs), _u64(tab_pcs), _u64(frame_off)
+        ff, fl, fn = _u32(frame_file), _u32(frame_line), _u32(frame_func)
+        if ss.size != se.size or fo.size != tp.size + 1 or not ff.size == fl.size == fn.size == int(fo[-1]):
+            raise ValueError("CoverTable: array lengths do not agree")
+        self.nfiles, self.nfuncs = int(nfiles), int(nfuncs)
+        h = c_void_p()
+        call("sg_cover_table_create", self.ctx.h, _p64(ss), _p64(se), ss.size, _p64(ap), ap.size, _p64(tp), tp.size,
+             _p64(fo), _p32(ff), _p32(fl), _p32(fn), self.nfiles, self.nfuncs, byref(h))
+        self.h = h
+        n = c_uint64()
+        call("sg_cover_table_slots", self.h, byref(n))
+        self.nslots = n.value
+
+    def close(self):
+        if self.h:
+            lib.sg_cover_table_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def cover_lines(table, cov, base):
+    """generateCoverHtml's set math and fileSet (syz-manager/cover.go:91-120, :165-196) on a CoverTable.  cov: an
+    array of cover PCs (low 32 bits), or a SignalSet for the set form (its members, ascending; nothing uploaded).
+    Returns (file_off, lines, covered, file_seen, ncovered_frames, missing): file f's lines are
+    lines[file_off[f]:file_off[f+1]], ascending, covered[] alongside."""
+    nf = table.nfiles
+    file_off = np.zeros(nf + 1, dtype=U64)
+    lines = np.empty(max(table.nslots, 1), dtype=U32)
+    covered = np.empty(max(table.nslots, 1), dtype=np.uint8)
+    seen = np.zeros(max(nf, 1), dtype=np.uint8)
+    ncf, nm = c_uint64(), c_size_t()
+    if isinstance(cov, SignalSet):
+        missing = np.empty(max(len(cov), 1), dtype=U64)
+        call("sg_cover_lines_set", table.h, cov.h, base, _p64(file_off), _p32(lines), _p8(covered), _p8(seen),
+             byref(ncf), _p64(missing), byref(nm))
+    else:
+        c = _u32(cov)
+        missing = np.empty(max(c.size, 1), dtype=U64)
+        call("sg_cover_lines", table.h, _p32(c), c.size, base, _p64(file_off), _p32(lines), _p8(covered), _p8(seen),
+             byref(ncf), _p64(missing), byref(nm))
+    total = int(file_off[nf])
+    return file_off, lines[:total], covered[:total], seen[:nf], ncf.value, missing[: nm.value]
+
+
+class CoverReport:
+    """The string-level mirror of generateCoverHtml up to fileSet.  symbolize(pcs) -> [(pc, func, file, line), ...]
+    is the caller's addr2line (symbolizer.go: a PC's frames in `-afi` order, "??" and line <= 0 already dropped).
+    The constructor symbolises all_pcs (initAllCover's call sites, cover.go:64-89) and interns the names;
+    file_set(cov, base) returns {file: [(line, covered), ...]} as fileSet does.  Covered PCs the table does not
+    know are symbolised and the table rebuilt from the host copies, once per call."""
+
+    def __init__(self, sym_start, sym_end, all_pcs, symbolize, ctx=None):
+        self.ctx = _ctx(ctx)
+        self.sym_start, self.sym_end, self.all_pcs = _u64(sym_start), _u64(sym_end), _u64(all_pcs)
+        self.symbolize = symbolize
+        self.files, self.funcs = {}, {}  # name -> id
+        self.frames = {}                 # pc -> [(file id, line, func id), ...]
+        self.table = None
+        self._add(self.all_pcs)
+        self._build()
+
+    def _add(self, pcs):
+        pcs = [int(pc) for pc in pcs]
+        for pc in pcs:
+            self.frames.setdefault(pc, [])
+        for pc, func, file, line in self.symbolize(pcs):
+            fi = self.files.setdefault(file, len(self.files))
+            fu = self.funcs.setdefault(func, len(self.funcs))
+            self.frames[int(pc)].append((fi, int(line), fu))
+
+    def _build(self):
+        if self.table is not None:
+            self.table.close()
+        tab = sorted(self.frames)
+        off = np.zeros(len(tab) + 1, dtype=U64)
+        off[1:] = np.cumsum([len(self.frames[pc]) for pc in tab])
+        fr = np.array([f for pc in tab for f in self.frames[pc]], dtype=np.int64).reshape(-1, 3)
+        self.table = CoverTable(self.sym_start, self.sym_end, self.all_pcs, tab, off, fr[:, 0], fr[:, 1], fr[:, 2],
+                                len(self.files), len(self.funcs), ctx=self.ctx)
+        self.names = sorted(self.files, key=self.files.get)
+
+    def close(self):
+        if self.table is not None:
+            self.table.close()
+            self.table = None
+
+    def file_set(self, cov, base):
+        if (len(cov) if isinstance(cov, SignalSet) else _u32(cov).size) == 0:
+            raise ValueError("No coverage data available")  # html.go:183
+        res = cover_lines(self.table, cov, base)
+        if res[5].size:
+            self._add(res[5])
+            self._build()
+            res = cover_lines(self.table, cov, base)
+            assert res[5].size == 0
+        file_off, lines, covered, _, ncf, _ = res
+        if ncf == 0:
+            raise ValueError("coverage doesn't match to vmlinux: no frames (does not have debug info?)")  # cover.go:113
+        out = {}
+        for f, name in enumerate(self.names):
+            a, b = int(file_off[f]), int(file_off[f + 1])
+            if b > a:
+                out[name] = [(int(ln), bool(c)) for ln, c in zip(lines[a:b], covered[a:b])]
+        return out
+
+
 # pkg/ipc/ipc_linux.go:168-307 status codes (include/syzsig.h SG_IPC_*)
 IPC_OK, IPC_NO_NCMD, IPC_SHORT_HEADER, IPC_BAD_INDEX, IPC_BAD_CALLNUM, IPC_DOUBLE = 0, 1, 2, 3, 4, 5
 IPC_SIGNAL_SIZE, IPC_COVER_SIZE, IPC_COMPS_SHORT, IPC_COMPS_TYPE = 6, 7, 8, 9

@@ -24,53 +24,21 @@
 // read-check needs.  Symbols must be sorted by start with non-decreasing
 // ends (the condition under which the reference's binary search over ends is
 // meaningful).
-#include "sg_internal.h"
+//
+// The host side is in three pieces (sg_report.h): the tables that depend on
+// the symbols and call sites alone (report_tables_*: the indexes, the symbol
+// leaders, the chunk tables), one query's pipeline over them up to the
+// per-site flag (report_query), and sg_cover_uncovered's compaction of the
+// flagged PCs.  sg_cover_uncovered builds the tables in the workspace per
+// call; a report table (sg_cover_lines.hip) builds them once in its own block
+// and runs report_query on them.
+#include "sg_report.h"
 
 #include <algorithm>
 #include <cstdlib>
 
 
 namespace sg {
-
-__device__ __forceinline__ uint64_t lb64(const uint64_t* a, uint64_t n, uint64_t v) {
-  uint64_t lo = 0, hi = n;
-  while (lo < hi) {
-    uint64_t mid = (lo + hi) >> 1;
-    if (a[mid] < v)
-      lo = mid + 1;
-    else
-      hi = mid;
-  }
-  return lo;
-}
-__device__ __forceinline__ uint64_t ub64(const uint64_t* a, uint64_t n, uint64_t v) {
-  uint64_t lo = 0, hi = n;
-  while (lo < hi) {
-    uint64_t mid = (lo + hi) >> 1;
-    if (a[mid] <= v)
-      lo = mid + 1;
-    else
-      hi = mid;
-  }
-  return lo;
-}
-
-// Radix index over a sorted u64 array A[0..n): r[k] = lower_bound(A, lo + (k
-// << sh)) for k <= nb (lo = A[0]), so a lower_bound of x only searches
-// [r[k], r[k+1]] for x's bucket k (about one entry per bucket): two adjacent
-// loads and a short search instead of log2(n) dependent loads (the C5
-// queries are 100M random lookups into 5M call sites and 50K symbols).
-struct RadixIdx {
-  const uint32_t* r;
-  uint64_t lo;
-  uint32_t sh, nb;
-};
-
-__device__ __forceinline__ uint64_t radix_bucket(uint64_t x, uint64_t lo, uint32_t sh, uint32_t nb) {
-  if (x < lo) return 0;
-  const uint64_t k = (x - lo) >> sh;
-  return k < nb ? k : nb;
-}
 
 __global__ void k_radix_index(const uint64_t* __restrict__ a, uint64_t n, uint64_t lo, uint32_t sh, uint32_t nb,
                               uint32_t* __restrict__ r) {
@@ -79,25 +47,6 @@ __global__ void k_radix_index(const uint64_t* __restrict__ a, uint64_t n, uint64
   const uint64_t d = k << sh;
   const uint64_t x = ((d >> sh) != k || lo + d < lo) ? ~0ull : lo + d;  // saturate past the top of u64
   r[k] = (uint32_t)lb64(a, n, x);
-}
-
-// lower_bound(a, x) through the index
-__device__ __forceinline__ uint64_t lb_idx(const uint64_t* a, uint64_t n, const RadixIdx& I, uint64_t x) {
-  const uint64_t k = radix_bucket(x, I.lo, I.sh, I.nb);
-  uint64_t lo = x < I.lo ? 0 : I.r[k], hi = x < I.lo ? I.r[0] : (k < I.nb ? I.r[k + 1] : n);
-  while (lo < hi) {
-    const uint64_t mid = (lo + hi) >> 1;
-    if (a[mid] < x)
-      lo = mid + 1;
-    else
-      hi = mid;
-  }
-  return lo;
-}
-
-// upper_bound(a, x) = lower_bound(a, x + 1)
-__device__ __forceinline__ uint64_t ub_idx(const uint64_t* a, uint64_t n, const RadixIdx& I, uint64_t x) {
-  return x == ~0ull ? n : lb_idx(a, n, I, x + 1);
 }
 
 struct RepArgs {
@@ -222,8 +171,6 @@ struct ChunkArgs {
   uint32_t* first_q;
   uint32_t* last_del;
 };
-
-__device__ __forceinline__ uint64_t query_pc(uint64_t hi32, uint32_t cov) { return hi32 + (uint64_t)cov - 5; }
 
 // Column of tile t in a chunk's row of the count table: the tiles that run on
 // one XCD (blockIdx % 8, round-robin dispatch: speed only) side by side, so
@@ -783,160 +730,199 @@ __global__ __launch_bounds__(kBlock) void k_scatter_u64(const uint64_t* __restri
   }
 }
 
-}  // namespace sg
+// ---- host side: the tables, then one query's pipeline over them ---------------
+void radix_index_plan(uint64_t n, uint64_t lo, uint64_t hi, RadixIdx& I) {
+  uint32_t nb = 1024;
+  while (nb < (1u << 20) && nb < n) nb <<= 1;
+  uint32_t sh = 0;
+  while (sh < 63 && ((hi - lo) >> sh) >= nb) sh++;
+  I.lo = lo;
+  I.sh = sh;
+  I.nb = nb;
+}
 
-using namespace sg;
+int radix_index_build(sg_ctx* ctx, const uint64_t* d_a, uint64_t n, const RadixIdx& I) {
+  hipLaunchKernelGGL(k_radix_index, dim3(div_up((uint64_t)I.nb + 1, 256)), dim3(256), 0, ctx->stream, d_a, n, I.lo, I.sh,
+                     I.nb, (uint32_t*)I.r);
+  SG_HIP(hipGetLastError());
+  return SG_OK;
+}
 
-extern "C" {
+// chunked query path (k_q_*) up to kMaxChunks chunks of call sites, the
+// per-query search passes (k_rep_first / k_rep_del) past them
+bool report_chunkable(uint64_t nall) { return nall <= (uint64_t)kSites * kMaxChunks; }
 
-int sg_cover_uncovered(sg_ctx* ctx, const uint32_t* cov, size_t ncov, uint32_t base, const uint64_t* sym_start,
-                       const uint64_t* sym_end, size_t nsym, const uint64_t* all_pcs, size_t nall, uint64_t* out,
-                       size_t* nout) {
-  if (!ctx || !nout || (ncov && !cov) || (nsym && (!sym_start || !sym_end)) || (nall && (!all_pcs || !out)))
-    return SG_EINVAL;
-  *nout = 0;
-  if (ncov >= 0xFFFFFFFFull || nsym >= 0xFFFFFFFFull || nall >= 0xFFFFFFFFull) {
-    set_error("sg_cover_uncovered: too many PCs, symbols or call sites for one call");
-    return SG_EINVAL;
-  }
-  for (size_t s = 1; s < nsym; s++)
-    if (sym_start[s] < sym_start[s - 1] || sym_end[s] < sym_end[s - 1]) {
-      set_error("sg_cover_uncovered: symbols must be sorted by start with non-decreasing ends");
-      return SG_EINVAL;
-    }
-  for (size_t j = 1; j < nall; j++)
-    if (all_pcs[j] <= all_pcs[j - 1]) {
-      set_error("sg_cover_uncovered: call-site PCs must be sorted and unique");
-      return SG_EINVAL;
-    }
-  if (ncov == 0 || nsym == 0 || nall == 0) return SG_OK;
-  std::lock_guard<std::mutex> g(ctx->mu);
-  int rc = ensure_device(ctx);
-  if (rc) return rc;
-  uint64_t ntiles = (nall + kTile - 1) / kTile, nchunks = ntiles * kChunksPerTile;
-  WsPlan p;
-  size_t o_cov = p.add(ncov * 4), o_ss = p.add(nsym * 8), o_se = p.add(nsym * 8), o_pcs = p.add(nall * 8),
-         o_fq = p.add(nsym * 4), o_gf = p.add(nsym * 8), o_ld = p.add(nall * 4), o_fl = p.add(nall),
-         o_m = p.add(nchunks * 32), o_c = p.add(nchunks * 4), o_b = p.add((nchunks + 1) * 8),
-         o_out = p.add(nall * 8), o_qb = p.add(((ncov + 63) / 64) * 8);
-
-  // radix indexes: about one entry per bucket, at most 2^20 buckets (4 MiB: one XCD L2)
-  auto plan_idx = [](uint64_t n, uint64_t lo, uint64_t hi, RadixIdx& I) {
-    uint32_t nb = 1024;
-    while (nb < (1u << 20) && nb < n) nb <<= 1;
+void report_tables_plan(WsPlan& p, const uint64_t* sym_start, const uint64_t* sym_end, uint64_t nsym,
+                        const uint64_t* all_pcs, uint64_t nall, bool chunks, RepTables& t, RepTablesOff& o) {
+  t = RepTables{};
+  t.nsym = nsym;
+  t.npcs = nall;
+  t.chunks = chunks;
+  radix_index_plan(nsym, sym_end[0], sym_end[nsym - 1], t.iend);
+  radix_index_plan(nall, all_pcs[0], all_pcs[nall - 1], t.ipcs);
+  radix_index_plan(nsym, sym_start[0], sym_start[nsym - 1], t.istart);
+  t.nch = div_up(nall, kSites);
+  {  // radix shift over [bnd[0], bnd[nch - 1]]
+    const uint64_t b0 = all_pcs[std::min<uint64_t>(kSites, nall) - 1], span = all_pcs[nall - 1] - b0;
     uint32_t sh = 0;
-    while (sh < 63 && ((hi - lo) >> sh) >= nb) sh++;
-    I.lo = lo;
-    I.sh = sh;
-    I.nb = nb;
-  };
-  RadixIdx iend{}, ipcs{}, istart{};
-  plan_idx(nsym, sym_end[0], sym_end[nsym - 1], iend);
-  plan_idx(nall, all_pcs[0], all_pcs[nall - 1], ipcs);
-  plan_idx(nsym, sym_start[0], sym_start[nsym - 1], istart);
-  const size_t o_ie = p.add(((uint64_t)iend.nb + 1) * 4), o_ip = p.add(((uint64_t)ipcs.nb + 1) * 4),
-               o_is = p.add(((uint64_t)istart.nb + 1) * 4), o_ld2 = p.add(nsym * 4);
-  // chunked query path (k_q_*) up to kMaxChunks chunks of call sites, the
-  // per-query search passes (k_rep_first / k_rep_del) past them;
-  // option report_direct 1 takes the latter at any size (a test hook for the
-  // > 16M-site regime)
-  const bool chunked = nall <= (uint64_t)kSites * kMaxChunks && ctx->opt[kOptReportDirect] <= 0;
-  const uint32_t nch = div_up(nall, kSites);
-  // query tiles: 64K queries per count / scatter workgroup
-  const uint32_t ntq = div_up(ncov, (uint64_t)kQT * kSQPer * kSQSub);
-  const uint32_t tw = 8 * div_up(ntq, 8);
-  const uint64_t ntc = chunked ? ((uint64_t)nch + 1) * tw : 1;
-  const size_t o_bnd = p.add((uint64_t)nch * 8), o_sr = p.add(((uint64_t)nch + 1) * 8),
-               o_qo = p.add(((uint64_t)nch + 2) * 8), o_gq = p.add(chunked ? ncov * 8 : 8),
-               o_ci = p.add(((uint64_t)kChunkIdx + 1) * 2), o_sh = p.add((uint64_t)nch * 4),
-               o_si = p.add((uint64_t)nch * (kSiteIdx + 1) * 2), o_sy = p.add(chunked ? nall * 4 : 4),
-               o_tc = p.add(ntc * 4), o_to = p.add((ntc + 1) * 8), o_jp = p.add(((uint64_t)nch + 1) * 4),
-               o_js = p.add(((uint64_t)nch + 2) * 8), o_srt = p.add(4);
-  // the count kernel's per-query chunks, read back by the scatter
-  const size_t o_qc = p.add(chunked ? ncov * 2 : 2);
-  size_t scan_off = p.total;
-  rc = ws_reserve(ctx, p.total + std::max(scan_ws_bytes(nchunks), scan_ws_bytes(ntc)));
-  if (rc) return rc;
+    while (sh < 63 && (span >> sh) >= kChunkIdx) sh++;
+    t.csh = sh;
+  }
+  const uint64_t nch = t.nch;
+  o.ss = p.add(nsym * 8);
+  o.se = p.add(nsym * 8);
+  o.pcs = p.add(nall * 8);
+  o.ie = p.add(((uint64_t)t.iend.nb + 1) * 4);
+  o.ip = p.add(((uint64_t)t.ipcs.nb + 1) * 4);
+  o.is = p.add(((uint64_t)t.istart.nb + 1) * 4);
+  o.ld = p.add(nsym * 4);
+  o.bnd = p.add(nch * 8);
+  o.sr = p.add((nch + 1) * 8);
+  o.ci = p.add(((uint64_t)kChunkIdx + 1) * 2);
+  o.sh = p.add(nch * 4);
+  o.si = p.add(nch * (kSiteIdx + 1) * 2);
+  o.sy = p.add(chunks ? nall * 4 : 4);
+}
+
+void report_tables_bind(void* buf, const RepTablesOff& o, RepTables& t) {
+  char* b = (char*)buf;
+  t.sstart = (uint64_t*)(b + o.ss);
+  t.send = (uint64_t*)(b + o.se);
+  t.pcs = (uint64_t*)(b + o.pcs);
+  t.iend.r = (const uint32_t*)(b + o.ie);
+  t.ipcs.r = (const uint32_t*)(b + o.ip);
+  t.istart.r = (const uint32_t*)(b + o.is);
+  t.leader = (uint32_t*)(b + o.ld);
+  t.bnd = (uint64_t*)(b + o.bnd);
+  t.symr = (uint2*)(b + o.sr);
+  t.cidx = (uint16_t*)(b + o.ci);
+  t.ssh = (uint32_t*)(b + o.sh);
+  t.sidx = (uint16_t*)(b + o.si);
+  t.ssym = (uint32_t*)(b + o.sy);
+}
+
+static RepArgs rep_args(const RepTables& t) {
   RepArgs a{};
-  a.cov = (uint32_t*)ws_at(ctx, o_cov);
+  a.sstart = t.sstart;
+  a.send = t.send;
+  a.nsym = t.nsym;
+  a.pcs = t.pcs;
+  a.npcs = t.npcs;
+  a.iend = t.iend;
+  a.ipcs = t.ipcs;
+  a.istart = t.istart;
+  a.leader = t.leader;
+  return a;
+}
+
+static ChunkArgs chunk_args(const RepTables& t) {
+  ChunkArgs k{};
+  k.pcs = t.pcs;
+  k.npcs = t.npcs;
+  k.sstart = t.sstart;
+  k.send = t.send;
+  k.nsym = t.nsym;
+  k.iend = t.iend;
+  k.nch = t.nch;
+  k.csh = t.csh;
+  k.bnd = t.bnd;
+  k.cidx = t.cidx;
+  k.ssh = t.ssh;
+  k.sidx = t.sidx;
+  k.ssym = t.ssym;
+  k.symr = t.symr;
+  return k;
+}
+
+int report_tables_build(sg_ctx* ctx, RepTables& t, bool chunk_index) {
+  {
+    ScopedTimer tm(ctx, "report_index");
+    int rc = radix_index_build(ctx, t.send, t.nsym, t.iend);
+    if (!rc) rc = radix_index_build(ctx, t.pcs, t.npcs, t.ipcs);
+    if (!rc) rc = radix_index_build(ctx, t.sstart, t.nsym, t.istart);
+    if (rc) return rc;
+    hipLaunchKernelGGL(k_sym_leader, dim3(div_up(t.nsym, 256)), dim3(256), 0, ctx->stream, rep_args(t));
+  }
+  if (t.chunks) {
+    // (timed with the query's chunk offsets: one figure for everything the chunked path prepares)
+    ScopedTimer tm(ctx, "report_count_q");
+    const ChunkArgs k = chunk_args(t);
+    hipLaunchKernelGGL(k_chunk_prep, dim3(div_up((uint64_t)t.nch + 1, 256)), dim3(256), 0, ctx->stream, k);
+    if (chunk_index)
+      hipLaunchKernelGGL(k_chunk_index, dim3(div_up((uint64_t)kChunkIdx + 1, 256)), dim3(256), 0, ctx->stream, k);
+    hipLaunchKernelGGL(k_site_sym, dim3(div_up(t.npcs, 256)), dim3(256), 0, ctx->stream, k);
+    hipLaunchKernelGGL(k_site_index, dim3(div_up((uint64_t)t.nch * (kSiteIdx + 1), 256)), dim3(256), 0, ctx->stream, k);
+    t.cidx_built = chunk_index;
+  }
+  SG_HIP(hipGetLastError());
+  return SG_OK;
+}
+
+// query tiles: 64K queries per count / scatter workgroup
+static uint32_t query_tiles(uint64_t ncov) { return div_up(ncov, (uint64_t)kQT * kSQPer * kSQSub); }
+static uint64_t tile_counts(const RepTables& t, uint64_t ncov, bool chunked) {
+  return chunked ? ((uint64_t)t.nch + 1) * (8 * div_up(query_tiles(ncov), 8)) : 1;
+}
+
+void report_query_plan(WsPlan& p, const RepTables& t, uint64_t ncov, bool chunked, RepQueryOff& q) {
+  const uint64_t nch = t.nch, ntc = tile_counts(t, ncov, chunked);
+  q.fq = p.add(t.nsym * 4);
+  q.gf = p.add(t.nsym * 8);
+  q.ld = p.add(t.npcs * 4);
+  q.fl = p.add(t.npcs);
+  q.qb = p.add(((ncov + 63) / 64) * 8);
+  q.qo = p.add((nch + 2) * 8);
+  q.gq = p.add(chunked ? ncov * 8 : 8);
+  q.tc = p.add(ntc * 4);
+  q.to = p.add((ntc + 1) * 8);
+  q.jp = p.add((nch + 1) * 4);
+  q.js = p.add((nch + 2) * 8);
+  q.srt = p.add(4);
+  // the count kernel's per-query chunks, read back by the scatter
+  q.qc = p.add(chunked ? ncov * 2 : 2);
+}
+
+size_t report_query_scan_bytes(const RepTables& t, uint64_t ncov, bool chunked) {
+  return std::max(scan_ws_bytes(tile_counts(t, ncov, chunked)), scan_ws_bytes((uint64_t)t.nch + 1));
+}
+
+int report_query(sg_ctx* ctx, const RepTables& t, const uint32_t* d_cov, uint64_t ncov, uint32_t base, bool chunked,
+                 const RepQueryOff& q, size_t scan_off, uint8_t** d_flag) {
+  int rc;
+  const uint64_t nsym = t.nsym, nall = t.npcs;
+  RepArgs a = rep_args(t);
+  a.cov = d_cov;
   a.ncov = ncov;
   a.base = base;
-  a.sstart = (uint64_t*)ws_at(ctx, o_ss);
-  a.send = (uint64_t*)ws_at(ctx, o_se);
-  a.nsym = nsym;
-  a.pcs = (uint64_t*)ws_at(ctx, o_pcs);
-  a.npcs = nall;
-  a.first_q = (uint32_t*)ws_at(ctx, o_fq);
-  a.group_first = (uint64_t*)ws_at(ctx, o_gf);
-  a.last_del = (uint32_t*)ws_at(ctx, o_ld);
-  a.flag = (uint8_t*)ws_at(ctx, o_fl);
-  a.qbits = (uint64_t*)ws_at(ctx, o_qb);
-  uint64_t* mask = (uint64_t*)ws_at(ctx, o_m);
-  uint32_t* cnt = (uint32_t*)ws_at(ctx, o_c);
-  uint64_t* bs = (uint64_t*)ws_at(ctx, o_b);
-  uint64_t* dout = (uint64_t*)ws_at(ctx, o_out);
-  iend.r = (const uint32_t*)ws_at(ctx, o_ie);
-  ipcs.r = (const uint32_t*)ws_at(ctx, o_ip);
-  istart.r = (const uint32_t*)ws_at(ctx, o_is);
-  a.iend = iend;
-  a.ipcs = ipcs;
-  a.istart = istart;
-  a.leader = (uint32_t*)ws_at(ctx, o_ld2);
-  SG_HIP(hipMemcpyAsync((void*)a.cov, cov, ncov * 4, hipMemcpyHostToDevice, ctx->stream));
-  SG_HIP(hipMemcpyAsync((void*)a.sstart, sym_start, nsym * 8, hipMemcpyHostToDevice, ctx->stream));
-  SG_HIP(hipMemcpyAsync((void*)a.send, sym_end, nsym * 8, hipMemcpyHostToDevice, ctx->stream));
-  SG_HIP(hipMemcpyAsync((void*)a.pcs, all_pcs, nall * 8, hipMemcpyHostToDevice, ctx->stream));
+  a.first_q = (uint32_t*)ws_at(ctx, q.fq);
+  a.group_first = (uint64_t*)ws_at(ctx, q.gf);
+  a.last_del = (uint32_t*)ws_at(ctx, q.ld);
+  a.flag = (uint8_t*)ws_at(ctx, q.fl);
+  a.qbits = (uint64_t*)ws_at(ctx, q.qb);
+  *d_flag = a.flag;
   SG_HIP(hipMemsetAsync(a.first_q, 0xFF, nsym * 4, ctx->stream));
   SG_HIP(hipMemsetAsync(a.group_first, 0xFF, nsym * 8, ctx->stream));
   SG_HIP(hipMemsetAsync(a.last_del, 0, nall * 4, ctx->stream));
-
-  {
-    ScopedTimer tm(ctx, "report_index");
-    hipLaunchKernelGGL(k_radix_index, dim3(div_up((uint64_t)iend.nb + 1, 256)), dim3(256), 0, ctx->stream, a.send,
-                       (uint64_t)nsym, iend.lo, iend.sh, iend.nb, (uint32_t*)iend.r);
-    hipLaunchKernelGGL(k_radix_index, dim3(div_up((uint64_t)ipcs.nb + 1, 256)), dim3(256), 0, ctx->stream, a.pcs,
-                       (uint64_t)nall, ipcs.lo, ipcs.sh, ipcs.nb, (uint32_t*)ipcs.r);
-    hipLaunchKernelGGL(k_radix_index, dim3(div_up((uint64_t)istart.nb + 1, 256)), dim3(256), 0, ctx->stream,
-                       a.sstart, (uint64_t)nsym, istart.lo, istart.sh, istart.nb, (uint32_t*)istart.r);
-    hipLaunchKernelGGL(k_sym_leader, dim3(div_up(nsym, 256)), dim3(256), 0, ctx->stream, a);
-  }
   if (chunked) {
-    ChunkArgs k{};
-    k.cov = a.cov;
+    const uint32_t nch = t.nch, ntq = query_tiles(ncov), tw = 8 * div_up(ntq, 8);
+    const uint64_t ntc = tile_counts(t, ncov, true);
+    ChunkArgs k = chunk_args(t);
+    k.cov = d_cov;
     k.ncov = ncov;
     k.hi32 = (uint64_t)base << 32;
-    k.pcs = a.pcs;
-    k.npcs = nall;
-    k.sstart = a.sstart;
-    k.send = a.send;
-    k.nsym = nsym;
-    k.iend = iend;
-    k.nch = nch;
-    k.bnd = (uint64_t*)ws_at(ctx, o_bnd);
-    k.cidx = (uint16_t*)ws_at(ctx, o_ci);
-    k.ssh = (uint32_t*)ws_at(ctx, o_sh);
-    k.sidx = (uint16_t*)ws_at(ctx, o_si);
-    k.ssym = (uint32_t*)ws_at(ctx, o_sy);
-    {  // radix shift over [bnd[0], bnd[nch - 1]]
-      const uint64_t b0 = all_pcs[std::min<uint64_t>(kSites, nall) - 1], span = all_pcs[nall - 1] - b0;
-      uint32_t sh = 0;
-      while (sh < 63 && (span >> sh) >= kChunkIdx) sh++;
-      k.csh = sh;
-    }
-    k.symr = (uint2*)ws_at(ctx, o_sr);
     k.ntiles = ntq;
     k.tw = tw;
-    k.jparts = (uint32_t*)ws_at(ctx, o_jp);
-    k.jstart = (uint64_t*)ws_at(ctx, o_js);
-    k.tcount = (uint32_t*)ws_at(ctx, o_tc);
-    k.toff = (uint64_t*)ws_at(ctx, o_to);
-    k.qoff = (uint64_t*)ws_at(ctx, o_qo);
-    k.grouped = (uint2*)ws_at(ctx, o_gq);
-    k.qchunk = (uint16_t*)ws_at(ctx, o_qc);
+    k.jparts = (uint32_t*)ws_at(ctx, q.jp);
+    k.jstart = (uint64_t*)ws_at(ctx, q.js);
+    k.tcount = (uint32_t*)ws_at(ctx, q.tc);
+    k.toff = (uint64_t*)ws_at(ctx, q.to);
+    k.qoff = (uint64_t*)ws_at(ctx, q.qo);
+    k.grouped = (uint2*)ws_at(ctx, q.gq);
+    k.qchunk = (uint16_t*)ws_at(ctx, q.qc);
     k.first_q = a.first_q;
     k.last_del = a.last_del;
     // queries in PC order (the reference's canonical covers) need no regrouping
-    uint32_t* dsorted = (uint32_t*)ws_at(ctx, o_srt);
+    uint32_t* dsorted = (uint32_t*)ws_at(ctx, q.srt);
     uint32_t unsorted = 1;
     {
       // a prefix first: queries in random order show it within the first few
@@ -957,10 +943,6 @@ int sg_cover_uncovered(sg_ctx* ctx, const uint32_t* cov, size_t ncov, uint32_t b
     }
     if (!unsorted) {
       ScopedTimer tm(ctx, "report_count_q");
-      hipLaunchKernelGGL(k_chunk_prep, dim3(div_up((uint64_t)nch + 1, 256)), dim3(256), 0, ctx->stream, k);
-      hipLaunchKernelGGL(k_site_sym, dim3(div_up(nall, 256)), dim3(256), 0, ctx->stream, k);
-      hipLaunchKernelGGL(k_site_index, dim3(div_up((uint64_t)nch * (kSiteIdx + 1), 256)), dim3(256), 0, ctx->stream,
-                         k);
       hipLaunchKernelGGL(k_q_direct_off, dim3(div_up((uint64_t)nch + 2, 256)), dim3(256), 0, ctx->stream, k);
       hipLaunchKernelGGL(k_q_parts, dim3(div_up((uint64_t)nch + 1, 256)), dim3(256), 0, ctx->stream, k);
       rc = scan_counts(ctx, k.jparts, k.jstart, (uint64_t)nch + 1, scan_off);
@@ -968,11 +950,8 @@ int sg_cover_uncovered(sg_ctx* ctx, const uint32_t* cov, size_t ncov, uint32_t b
     }
     if (unsorted) {
       ScopedTimer tm(ctx, "report_count_q");
-      hipLaunchKernelGGL(k_chunk_prep, dim3(div_up((uint64_t)nch + 1, 256)), dim3(256), 0, ctx->stream, k);
-      hipLaunchKernelGGL(k_chunk_index, dim3(div_up((uint64_t)kChunkIdx + 1, 256)), dim3(256), 0, ctx->stream, k);
-      hipLaunchKernelGGL(k_site_sym, dim3(div_up(nall, 256)), dim3(256), 0, ctx->stream, k);
-      hipLaunchKernelGGL(k_site_index, dim3(div_up((uint64_t)nch * (kSiteIdx + 1), 256)), dim3(256), 0, ctx->stream,
-                         k);
+      if (!t.cidx_built)  // (tables of one call: only queries out of PC order need the chunk index)
+        hipLaunchKernelGGL(k_chunk_index, dim3(div_up((uint64_t)kChunkIdx + 1, 256)), dim3(256), 0, ctx->stream, k);
       if (tw != ntq) SG_HIP(hipMemsetAsync(k.tcount, 0, ntc * 4, ctx->stream));  // (the padding columns)
       hipLaunchKernelGGL((k_q_count<kSQPer, kSQSub>), dim3(ntq), dim3(kQT), 0, ctx->stream, k);
       rc = scan_counts(ctx, k.tcount, k.toff, ntc, scan_off);
@@ -1009,11 +988,79 @@ int sg_cover_uncovered(sg_ctx* ctx, const uint32_t* cov, size_t ncov, uint32_t b
     ScopedTimer tm(ctx, "report_sites");
     hipLaunchKernelGGL(k_rep_group, dim3(div_up(nsym, 256)), dim3(256), 0, ctx->stream, a);
     hipLaunchKernelGGL(k_rep_final, dim3(div_up(nall, 256)), dim3(256), 0, ctx->stream, a);
-    hipLaunchKernelGGL(k_flag_mask, dim3(div_up(nchunks, kBlock / 64)), dim3(kBlock), 0, ctx->stream, a.flag,
+  }
+  SG_HIP(hipGetLastError());
+  return SG_OK;
+}
+
+}  // namespace sg
+
+using namespace sg;
+
+extern "C" {
+
+int sg_cover_uncovered(sg_ctx* ctx, const uint32_t* cov, size_t ncov, uint32_t base, const uint64_t* sym_start,
+                       const uint64_t* sym_end, size_t nsym, const uint64_t* all_pcs, size_t nall, uint64_t* out,
+                       size_t* nout) {
+  if (!ctx || !nout || (ncov && !cov) || (nsym && (!sym_start || !sym_end)) || (nall && (!all_pcs || !out)))
+    return SG_EINVAL;
+  *nout = 0;
+  if (ncov >= 0xFFFFFFFFull || nsym >= 0xFFFFFFFFull || nall >= 0xFFFFFFFFull) {
+    set_error("sg_cover_uncovered: too many PCs, symbols or call sites for one call");
+    return SG_EINVAL;
+  }
+  for (size_t s = 1; s < nsym; s++)
+    if (sym_start[s] < sym_start[s - 1] || sym_end[s] < sym_end[s - 1]) {
+      set_error("sg_cover_uncovered: symbols must be sorted by start with non-decreasing ends");
+      return SG_EINVAL;
+    }
+  for (size_t j = 1; j < nall; j++)
+    if (all_pcs[j] <= all_pcs[j - 1]) {
+      set_error("sg_cover_uncovered: call-site PCs must be sorted and unique");
+      return SG_EINVAL;
+    }
+  if (ncov == 0 || nsym == 0 || nall == 0) return SG_OK;
+  std::lock_guard<std::mutex> g(ctx->mu);
+  int rc = ensure_device(ctx);
+  if (rc) return rc;
+  uint64_t ntiles = (nall + kTile - 1) / kTile, nchunks = ntiles * kChunksPerTile;
+  // option report_direct 1 takes the global-search form at any size (a test
+  // hook for the > 16M-site regime)
+  const bool chunked = report_chunkable(nall) && ctx->opt[kOptReportDirect] <= 0;
+  WsPlan p;
+  RepTables t;
+  RepTablesOff to;
+  RepQueryOff qo;
+  const size_t o_cov = p.add(ncov * 4);
+  report_tables_plan(p, sym_start, sym_end, nsym, all_pcs, nall, chunked, t, to);
+  report_query_plan(p, t, ncov, chunked, qo);
+  const size_t o_m = p.add(nchunks * 32), o_c = p.add(nchunks * 4), o_b = p.add((nchunks + 1) * 8),
+               o_out = p.add(nall * 8);
+  const size_t scan_off = p.total;
+  rc = ws_reserve(ctx, p.total + std::max(scan_ws_bytes(nchunks), report_query_scan_bytes(t, ncov, chunked)));
+  if (rc) return rc;
+  report_tables_bind(ctx->ws, to, t);
+  uint32_t* dcov = (uint32_t*)ws_at(ctx, o_cov);
+  uint64_t* mask = (uint64_t*)ws_at(ctx, o_m);
+  uint32_t* cnt = (uint32_t*)ws_at(ctx, o_c);
+  uint64_t* bs = (uint64_t*)ws_at(ctx, o_b);
+  uint64_t* dout = (uint64_t*)ws_at(ctx, o_out);
+  SG_HIP(hipMemcpyAsync(dcov, cov, ncov * 4, hipMemcpyHostToDevice, ctx->stream));
+  SG_HIP(hipMemcpyAsync(t.sstart, sym_start, nsym * 8, hipMemcpyHostToDevice, ctx->stream));
+  SG_HIP(hipMemcpyAsync(t.send, sym_end, nsym * 8, hipMemcpyHostToDevice, ctx->stream));
+  SG_HIP(hipMemcpyAsync(t.pcs, all_pcs, nall * 8, hipMemcpyHostToDevice, ctx->stream));
+  rc = report_tables_build(ctx, t, false);
+  if (rc) return rc;
+  uint8_t* flag = nullptr;
+  rc = report_query(ctx, t, dcov, ncov, base, chunked, qo, scan_off, &flag);
+  if (rc) return rc;
+  {
+    ScopedTimer tm(ctx, "report_sites");
+    hipLaunchKernelGGL(k_flag_mask, dim3(div_up(nchunks, kBlock / 64)), dim3(kBlock), 0, ctx->stream, flag,
                        (uint64_t)nall, nchunks, mask, cnt);
     rc = scan_counts(ctx, cnt, bs, nchunks, scan_off);
     if (rc) return rc;
-    hipLaunchKernelGGL(k_scatter_u64, dim3(div_up(nchunks, kBlock / 64)), dim3(kBlock), 0, ctx->stream, a.pcs,
+    hipLaunchKernelGGL(k_scatter_u64, dim3(div_up(nchunks, kBlock / 64)), dim3(kBlock), 0, ctx->stream, t.pcs,
                        (uint64_t)nall, mask, bs, nchunks, dout);
   }
   SG_HIP(hipGetLastError());
@@ -1027,3 +1074,4 @@ int sg_cover_uncovered(sg_ctx* ctx, const uint32_t* cov, size_t ncov, uint32_t b
 }
 
 }  // extern "C"
+
