@@ -98,7 +98,12 @@ int sg_ctx_kernel_time(sg_ctx* ctx, const char* name, double* ms, uint64_t* laun
  * status than SG_TIN_OK or without a cover list are in none of the four;
  * "triage_runs_sort_cap" and "tinput_chunk" (constants: the values of new_k
  * that sg_triage_intersect / sg_triage_subset and the run loop of
- * sg_triage_runs_from_kcov* hold in LDS at a time); "owned_big_records" (the
+ * sg_triage_runs_from_kcov* hold in LDS at a time); "prio_bad_ids" (the call
+ * ids >= ncalls that sg_prio_table_add_dev has skipped on this context since
+ * it was created; counted on the device, read here after a stream sync),
+ * "prio_band_cells" and "prio_short_len" (constants: the u32 cells of a row
+ * band that the pair count keeps in LDS, and the longest program that takes
+ * the band path); "owned_big_records" (the
  * records the last
  * ordered-output call -- sg_triage_batch[_dev] with diff lists, sg_merge_poll
  * -- swept a workgroup each instead of a wave each, summed over its record
@@ -946,6 +951,92 @@ int sg_hints_from_kcov(sg_ctx* ctx, const uint64_t* recs, const uint64_t* call_o
 int sg_hints_from_kcov_dev(sg_ctx* ctx, const uint64_t* d_recs, const uint64_t* d_call_off, uint64_t ncalls,
 			   uint64_t nrecs, const uint64_t* d_val_off, const uint64_t* d_vals, uint64_t nvals,
 			   int32_t* d_status, uint64_t* d_rep_off, uint64_t* d_reps, uint64_t cap);
+
+/* ---- call priorities: corpus to ChoiceTable (prog/prio.go:27-36, :133-229) -- */
+/* What Manager.Connect computes between minimizeCorpus and the maxSignal export
+ * (syz-manager/manager.go:816-837: target.CalculatePriorities(corpus), at most
+ * every 30 minutes because it is slow), what the /prio page shows a row of
+ * (syz-manager/html.go:196-224, mgr.prios as last computed), and what every
+ * fuzzer makes of the matrix (prog/prio.go:203-229, BuildChoiceTable), from the
+ * programs' call ids.
+ *
+ * Input: a CSR of Call.Meta.ID.  Program p owns call_ids[prog_off[p] ..
+ * prog_off[p+1]), prog_off[0] == 0.  ncalls is len(target.Syscalls); mmap_id is
+ * target.MmapSyscall.ID, or SG_NO_CALL for a target without one.
+ *
+ * Counts (prog/prio.go:138-151): count[i][j] = sum over programs of
+ * n_p(i) * n_p(j) for i != j, i != mmap_id, j != mmap_id, with n_p(i) the calls
+ * of program p with id i (both loops run over p.Calls, repeats included).  The
+ * table keeps them exact, as 64-bit integers.  The reference adds 1.0 to a
+ * float32, which is exact up to 2^24 and then sticks, so its cell is
+ * float32(min(count, 2^24)): the saturation is applied when the counts are
+ * read (sg_call_prios*), never when they are accumulated, and
+ * sg_prio_table_counts returns them unsaturated.
+ *
+ * normalizePrio (prog/prio.go:158-192) per row, every operation rounded to
+ * float32 in the reference's order: max over the row; min over the nonzero
+ * cells from 1e10; nzero, and min /= 2 * float32(nzero) when nzero != 0; a row
+ * with max == 0 becomes all 1; otherwise a zero cell takes min, and
+ * p = (p - min) / (max - min) * 0.9 + 0.1 (float32 constants; the multiply and
+ * the add are two roundings: Go on amd64 does not fuse them), clamped to 1.
+ * The diagonal of the counts is always zero, so nzero >= 1 in every row and
+ * max > min whenever max > 0: no NaN can arise.  That is `dynamic`.
+ *
+ * CalculatePriorities (prog/prio.go:27-36): prios[i][j] = dynamic[i][j] *
+ * static[i][j], one float32 multiply.  The static matrix is an input: it
+ * depends on the target alone, and the reference sums it in Go map order
+ * (prog/prio.go:106-116), so its last bits differ from run to run in the
+ * reference itself.  The caller computes it once.
+ *
+ * BuildChoiceTable (prog/prio.go:203-229): for an enabled row i,
+ * run[i][j] = sum over k <= j with enabled[k] of int(prios[i][k] * 1000), the
+ * product rounded to float32, then truncated.  A disabled row (nil in Go) is
+ * all zeros.  enabled == NULL enables every call.  run is int32: the largest
+ * sum is 1000 * ncalls.
+ *
+ * All matrices are row-major, ncalls * ncalls. */
+#define SG_NO_CALL 0xffffffffu
+#define SG_PRIO_MAX_CALLS 8192
+typedef struct sg_prio_table sg_prio_table;
+/* The table owns one device block: the static matrix, the enabled bytes and
+ * the 64-bit counts (zero at creation).  It lives in ctx and must be destroyed
+ * before it.  static_prios (ncalls * ncalls) and enabled (ncalls bytes, nonzero
+ * = enabled, nullable) are copied.  SG_EINVAL, before the context is touched: a
+ * NULL ctx, static_prios or out; ncalls == 0 or above SG_PRIO_MAX_CALLS;
+ * mmap_id >= ncalls unless it is SG_NO_CALL; a static value that is not finite
+ * or not in [0, 1].  SG_ENODEV without a device. */
+int sg_prio_table_create(sg_ctx* ctx, uint32_t ncalls, uint32_t mmap_id, const float* static_prios,
+			 const uint8_t* enabled, sg_prio_table** out);
+void sg_prio_table_destroy(sg_prio_table* t);
+/* All counts to zero (stream-ordered). */
+int sg_prio_table_clear(sg_prio_table* t);
+/* Adds a corpus' pairs to the counts: two adds equal one add of the
+ * concatenation.  Programs may have any length, zero included.  SG_EINVAL,
+ * before the context is touched: a NULL t or prog_off; prog_off[0] != 0 or
+ * decreasing offsets; 2^32 ids or more; call_ids NULL with ids present; an id
+ * >= ncalls.  Returns once the arrays are the caller's again.
+ * Removing programs is left out: a removal cannot be validated against what
+ * was added.  After minimizeCorpus the caller clears and re-adds. */
+int sg_prio_table_add(sg_prio_table* t, const uint32_t* call_ids, const uint64_t* prog_off, size_t nprogs);
+/* Device form (nids = the ids in d_call_ids): every pointer is device memory,
+ * stream-ordered, nothing is read back.  The offsets cannot be checked: every
+ * program's range is clamped to nids.  An id >= ncalls is skipped, never used
+ * as an index, and counted in the context counter "prio_bad_ids".  SG_EINVAL:
+ * a NULL t or d_prog_off, d_call_ids NULL with nids > 0, nids >= 2^32. */
+int sg_prio_table_add_dev(sg_prio_table* t, const uint32_t* d_call_ids, const uint64_t* d_prog_off, uint64_t nprogs,
+			  uint64_t nids);
+/* The exact counts (ncalls * ncalls); waits. */
+int sg_prio_table_counts(sg_prio_table* t, uint64_t* counts);
+/* dynamic, prios and run (each ncalls * ncalls, each may be NULL) from the
+ * counts, which stay unchanged.  One wait. */
+int sg_call_prios(sg_prio_table* t, float* dynamic, float* prios, int32_t* run);
+/* Device form: stream-ordered, no wait. */
+int sg_call_prios_dev(sg_prio_table* t, float* d_dynamic, float* d_prios, int32_t* d_run);
+/* sg_prio_table_clear, sg_prio_table_add and sg_call_prios in one call, with
+ * one wait: what Connect and the /prio page need.  Rejects what add rejects;
+ * on SG_EINVAL the counts are unchanged. */
+int sg_call_prios_from_progs(sg_prio_table* t, const uint32_t* call_ids, const uint64_t* prog_off, size_t nprogs,
+			     float* dynamic, float* prios, int32_t* run);
 
 #ifdef __cplusplus
 }

@@ -6,7 +6,7 @@ calls fail loudly (ImportError here, SyzSigError from compute calls).
 """
 import ctypes
 import os
-from ctypes import POINTER, c_char_p, c_double, c_int, c_int32, c_int64, c_size_t, c_uint8, c_uint32, c_uint64, c_void_p
+from ctypes import POINTER, c_char_p, c_double, c_float, c_int, c_int32, c_int64, c_size_t, c_uint8, c_uint32, c_uint64, c_void_p
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("SG_LIB_PATH") or os.path.join(_HERE, "libsyzsig.so")  # override: diagnostics builds
@@ -36,6 +36,8 @@ P64 = POINTER(c_uint64)
 P8 = POINTER(c_uint8)
 PSZ = POINTER(c_size_t)
 PINT = POINTER(c_int)
+PF = POINTER(c_float)
+PI32 = POINTER(c_int32)
 
 # name -> (restype, argtypes); mirrors include/syzsig.h one to one.
 SIGNATURES = {
@@ -143,6 +145,15 @@ SIGNATURES = {
     "sg_cover_table_slots": (c_int, [c_void_p, P64]),
     "sg_cover_lines": (c_int, [c_void_p, P32, c_size_t, c_uint32, P64, P32, P8, P8, P64, P64, PSZ]),
     "sg_cover_lines_set": (c_int, [c_void_p, c_void_p, c_uint32, P64, P32, P8, P8, P64, P64, PSZ]),
+    "sg_prio_table_create": (c_int, [c_void_p, c_uint32, c_uint32, PF, P8, POINTER(c_void_p)]),
+    "sg_prio_table_destroy": (None, [c_void_p]),
+    "sg_prio_table_clear": (c_int, [c_void_p]),
+    "sg_prio_table_add": (c_int, [c_void_p, P32, P64, c_size_t]),
+    "sg_prio_table_add_dev": (c_int, [c_void_p, c_void_p, c_void_p, c_uint64, c_uint64]),
+    "sg_prio_table_counts": (c_int, [c_void_p, P64]),
+    "sg_call_prios": (c_int, [c_void_p, PF, PF, PI32]),
+    "sg_call_prios_dev": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p]),
+    "sg_call_prios_from_progs": (c_int, [c_void_p, P32, P64, c_size_t, PF, PF, PI32]),
     "sg_ipc_parse": (c_int, [c_void_p, P32, P64, P64, P32, c_size_t, POINTER(c_int64), P8, POINTER(c_int32), P64, P32,
                              P64, P32]),
     "sg_ipc_parse_dev": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_uint64, c_uint64, c_void_p,

@@ -83,6 +83,8 @@ class Context:
         "triage_runs_sorted" / "triage_runs_ranked" / "triage_runs_foreach", the constants
         "triage_runs_sort_cap" (the most values the LDS-sort route folds) and "tinput_chunk" (the values of a
         new list that Intersection holds in LDS at a time),
+        the call priorities' "prio_bad_ids" (ids the device form skipped) and its constants "prio_band_cells" /
+        "prio_short_len",
         the last ordered-output call's "owned_big_records",
         the last merge's pairs per path "merge_pairs_generic" / "merge_pairs_diff_small" /
         "merge_pairs_gap" / "merge_pairs_tile", the last Canonicalize's "canon_wave_lists" /

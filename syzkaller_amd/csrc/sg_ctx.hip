@@ -826,7 +826,16 @@ int sg_ctx_counter(sg_ctx* ctx, const char* name, uint64_t* out) {
     SG_HIP(hipStreamSynchronize(ctx->stream));
     SG_HIP(hipMemcpy(&v, ctx->own_big + kTrRouteSlot + route, 4, hipMemcpyDeviceToHost));
     *out = v;
-  } else if (!strcmp(name, "triage_runs_sort_cap"))  // values a cover fold may hold on the LDS-sort route
+  } else if (!strcmp(name, "prio_bad_ids")) {  // ids >= ncalls that sg_prio_table_add_dev skipped (sg_call_prios.hip)
+    uint64_t v = 0;
+    SG_HIP(hipStreamSynchronize(ctx->stream));
+    SG_HIP(hipMemcpy(&v, ctx->own_big + kPrioBadSlot, 8, hipMemcpyDeviceToHost));
+    *out = v;
+  } else if (!strcmp(name, "prio_band_cells"))  // u32 cells of a row band of the pair count
+    *out = kPrioBandCells;
+  else if (!strcmp(name, "prio_short_len"))  // calls of a program on the pair count's band path
+    *out = kPrioShort;
+  else if (!strcmp(name, "triage_runs_sort_cap"))  // values a cover fold may hold on the LDS-sort route
     *out = kTrSort;
   else if (!strcmp(name, "tinput_chunk"))  // values of new_k per LDS chunk of Intersection (sg_tinput.h)
     *out = kTinChunk;

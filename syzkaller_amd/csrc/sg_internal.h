@@ -359,6 +359,12 @@ int exec_cover(sg_ctx* ctx, const uint64_t* d_pcs, const uint64_t* d_call_off, u
 constexpr uint32_t kTrWideSlot = 16;
 constexpr uint32_t kTrRouteSlot = kTrWideSlot + 1;  // + kTrCopied .. kTrForeach
 enum : uint32_t { kTrCopied = 0, kTrSorted = 1, kTrRanked = 2, kTrForeach = 3, kTrRoutes = 4 };
+// ... and at u32 slot kPrioBadSlot one 64-bit counter, "prio_bad_ids": the ids
+// >= ncalls that sg_prio_table_add_dev has skipped on this context (sg_call_prios.hip)
+constexpr uint32_t kPrioBadSlot = 24;
+// read by sg_ctx_counter as "prio_band_cells" and "prio_short_len"
+constexpr uint32_t kPrioBandCells = 40960;  // u32 cells of a row band: the CU's 160 KiB of LDS
+constexpr uint32_t kPrioShort = 64;         // calls of a program on the band path; longer ones take k_prio_long
 // read by sg_ctx_counter as "triage_runs_sort_cap" and "tinput_chunk"
 constexpr uint32_t kTrSort = 8192;    // values the cover fold sorts in LDS (64 KiB of keys)
 constexpr uint32_t kTinChunk = 8192;  // values of a per LDS chunk of tin_intersect (32 KiB)
