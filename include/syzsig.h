@@ -103,7 +103,11 @@ int sg_ctx_kernel_time(sg_ctx* ctx, const char* name, double* ms, uint64_t* laun
  * it was created; counted on the device, read here after a stream sync),
  * "prio_band_cells" and "prio_short_len" (constants: the u32 cells of a row
  * band that the pair count keeps in LDS, and the longest program that takes
- * the band path); "owned_big_records" (the
+ * the band path); "sha1_long_progs" (the programs that took the long SHA-1
+ * path of sg_prog_hashes*, sg_sigset_add_progs and sg_hub_sync on this
+ * context since it was created; counted on the device, read here after a
+ * stream sync) and "sha1_long_len" (constant: SG_SHA1_LONG);
+ * "owned_big_records" (the
  * records the last
  * ordered-output call -- sg_triage_batch[_dev] with diff lists, sg_merge_poll
  * -- swept a workgroup each instead of a wave each, summed over its record
@@ -1037,6 +1041,103 @@ int sg_call_prios_dev(sg_prio_table* t, float* d_dynamic, float* d_prios, int32_
  * on SG_EINVAL the counts are unchanged. */
 int sg_call_prios_from_progs(sg_prio_table* t, const uint32_t* call_ids, const uint64_t* prog_off, size_t nprogs,
 			     float* dynamic, float* prios, int32_t* run);
+
+/* ---- program identities: pkg/hash and hubSync's Add / Del ------------------ */
+/* pkg/hash (hash.Hash, hash.String) is SHA-1 of the serialized program, and
+ * the reference recomputes it for the whole corpus under mgr.mu: hubSync
+ * (syz-manager/manager.go:994-1069: at connect :1021-1025, per sync :1053-1056,
+ * the diff against mgr.hubCorpus :1057-1069), minimizeCorpus (:777-781, and its
+ * sweep of corpusDB.Records :788-793), NewInput (:913), the fuzzer's addInput
+ * (syz-fuzzer/fuzzer.go:480-484) and the hub's loadDB (syz-hub/state/state.go:
+ * 91-101).
+ *
+ * Input: a CSR of bytes.  Program k owns bytes[off[k] .. off[k+1]), off[0] == 0.
+ * sigs[20 * k .. 20 * k + 20) is its SHA-1 (FIPS 180-4, what Go's crypto/sha1
+ * computes; the padding's message length is a 64-bit bit count and is computed
+ * as one).  hash.Hash(pieces...) hashes the concatenation of its pieces: the
+ * caller joins them.
+ *
+ * A program longer than SG_SHA1_LONG bytes takes a path of its own (a wave to
+ * itself); the context counter "sha1_long_progs" counts them, "sha1_long_len"
+ * is the constant. */
+#define SG_SIG_BYTES 20
+#define SG_SHA1_LONG 65536
+/* hash.Hash (sigs) and hash.String (hex: hex.EncodeToString, lower case, 40
+ * characters per program, no NUL) of every program; either output may be NULL.
+ * nprogs == 0 is SG_OK and writes nothing.  SG_EINVAL, before the context is
+ * touched: a NULL ctx or off; off[0] != 0 or decreasing offsets; bytes NULL
+ * with bytes present; 2^32 programs or more.  SG_ENODEV without a device.  One
+ * wait. */
+int sg_prog_hashes(sg_ctx* ctx, const uint8_t* bytes, const uint64_t* off, size_t nprogs, uint8_t* sigs, char* hex);
+/* Device form (nbytes = the bytes in d_bytes): every pointer is device memory,
+ * stream-ordered, nothing is read back.  The offsets cannot be checked: each
+ * program's start is clamped to nbytes and its end to [start, nbytes], so
+ * garbage offsets give garbage hashes, never a read outside [d_bytes, d_bytes +
+ * nbytes).  SG_EINVAL: a NULL ctx, d_off or d_sigs with nprogs > 0; d_bytes
+ * NULL with nbytes > 0; nprogs >= 2^32. */
+int sg_prog_hashes_dev(sg_ctx* ctx, const uint8_t* d_bytes, const uint64_t* d_off, uint64_t nprogs, uint64_t nbytes,
+		       uint8_t* d_sigs);
+
+/* map[hash.Sig]bool, device-resident: the fuzzer's corpusHashes (syz-fuzzer/
+ * fuzzer.go:480-484), the manager's hubCorpus (manager.go:1021-1025).
+ *
+ * The set is insertion-ordered: sg_sigset_export returns the identities in the
+ * order in which they first entered, which is batch order within a call.  The
+ * reference's own order is Go map iteration, which is random; insertion order
+ * is this project's pinned choice, not a parity claim.
+ *
+ * Inside: a dense store of 20-byte keys in insertion order, and an open-
+ * addressing table of u32 indices into it with a power-of-two number of slots,
+ * at most half of them used.  A key's home slot is its first four bytes read
+ * as a little-endian u32, masked to the table.  The empty marker is an index
+ * value (0xffffffff), never a key value: the all-zero and the all-0xff identity
+ * are ordinary keys.  The set grows; capacity_hint only sizes the first
+ * allocation.  A set holds fewer than 2^31 identities. */
+typedef struct sg_sigset sg_sigset;
+/* The set lives in ctx and must be destroyed before it.  SG_EINVAL, before
+ * the context is touched: a NULL ctx or out, a hint of 2^31 or more.
+ * SG_ENODEV without a device. */
+int sg_sigset_create(sg_ctx* ctx, uint64_t capacity_hint, sg_sigset** out);
+void sg_sigset_destroy(sg_sigset* s);
+/* Empties the set; its allocations stay. */
+int sg_sigset_clear(sg_sigset* s);
+/* len(map).  No device work: the count is kept on the host. */
+int sg_sigset_count(sg_sigset* s, uint64_t* out);
+/* The identities in insertion order, 20 bytes each; *n is always the count, the
+ * identities are written only when it is <= cap (in identities).  SG_EINVAL: a
+ * NULL s or n, sigs NULL with cap > 0. */
+int sg_sigset_export(sg_sigset* s, uint8_t* sigs, size_t cap, size_t* n);
+/* present[k] = 1 iff sigs[20 * k ..) is in the set; reads only.  It serves
+ * minimizeCorpus' sweep of corpusDB.Records (manager.go:788-793) and loadDB's
+ * check (state.go:91-101).  SG_EINVAL: a NULL s, or sigs or present NULL with
+ * n > 0; 2^31 queries or more. */
+int sg_sigset_contains(sg_sigset* s, const uint8_t* sigs, size_t n, uint8_t* present);
+/* addInput's test (fuzzer.go:480-484) over a batch: is_new[k] = 1 iff sigs[k]
+ * was not in the set before the call and no j < k of the batch has the same 20
+ * bytes.  Afterwards the set is the union, the new identities appended in
+ * batch order.  SG_EINVAL as sg_sigset_contains; also when the set would reach
+ * 2^31 identities. */
+int sg_sigset_add_new(sg_sigset* s, const uint8_t* sigs, size_t n, uint8_t* is_new);
+/* sg_prog_hashes followed by sg_sigset_add_new in one call with one wait; the
+ * hashes leave the device only when sigs is given.  Rejects what both reject. */
+int sg_sigset_add_progs(sg_sigset* s, const uint8_t* bytes, const uint64_t* off, size_t nprogs, uint8_t* sigs,
+			uint8_t* is_new);
+/* hubSync's diff (manager.go:1053-1069) for a corpus given in a fixed order.
+ * add[k] = 1 iff the hash of program k is neither in hub before the call nor
+ * the hash of an earlier program of the call (a.Add, :1057-1061).  del_sigs
+ * holds the identities that were in hub before the call and that no program
+ * hashes to, in the set's order, *ndel of them (a.Del, :1063-1069).
+ * Afterwards hub holds exactly the corpus' identities, in first-occurrence
+ * program order (mgr.hubCorpus after :1061 and :1068).  An empty corpus deletes
+ * everything.  del_cap (in identities) must be at least the set's count before
+ * the call, which sg_sigset_count returns: otherwise SG_EINVAL before any
+ * work, the set untouched.  SG_EINVAL also for what sg_prog_hashes rejects, a
+ * NULL hub, add (with nprogs > 0) or ndel, del_sigs NULL with del_cap > 0.
+ * sigs (20 * nprogs, may be NULL) receives the hashes.  Inside, a fresh table
+ * and store are built from the corpus and swapped in: nothing is ever deleted
+ * from a table, so there are no tombstones. */
+int sg_hub_sync(sg_sigset* hub, const uint8_t* bytes, const uint64_t* off, size_t nprogs, uint8_t* sigs, uint8_t* add,
+		uint8_t* del_sigs, size_t del_cap, size_t* ndel);
 
 #ifdef __cplusplus
 }

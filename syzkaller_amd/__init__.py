@@ -7,18 +7,25 @@ one batch's triage hash-sharded by signal across GPUs (RCCL all-to-all),
 `syzkaller_amd.dist` holds the Poll OR-exchange between independent fuzzers,
 `syzkaller_amd.hints` the comparison hints (executor comparisons to CompMaps,
 shrinkExpand over batches of argument values), and `syzkaller_amd.prio` the
-call priorities (corpus call ids to CalculatePriorities and the ChoiceTable).
+call priorities (corpus call ids to CalculatePriorities and the ChoiceTable),
+and `syzkaller_amd.corpus` the corpus' identities (pkg/hash, the identity sets
+and hubSync's Add / Del).
 """
 from ._lib import LIB_PATH, SyzSigError, lib  # noqa: F401  (fails loudly if the library is missing)
 
-__all__ = ["LIB_PATH", "SyzSigError", "lib", "PrioTable", "CalculatePriorities", "BuildChoiceTable", "ChoiceTable"]
-
 _PRIO = ("PrioTable", "CalculatePriorities", "BuildChoiceTable", "ChoiceTable")
+_CORPUS = ("Hash", "String", "prog_hashes", "SigSet", "HubSync", "VerifyKeys")
+
+__all__ = ["LIB_PATH", "SyzSigError", "lib", *_PRIO, *_CORPUS]
 
 
-def __getattr__(name):  # syzkaller_amd.prio's names, bound on first use (the module needs numpy)
+def __getattr__(name):  # syzkaller_amd.prio's and .corpus' names, bound on first use (the modules need numpy)
     if name in _PRIO:
         from . import prio
 
         return getattr(prio, name)
+    if name in _CORPUS:
+        from . import corpus
+
+        return getattr(corpus, name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

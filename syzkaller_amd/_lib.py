@@ -154,6 +154,17 @@ SIGNATURES = {
     "sg_call_prios": (c_int, [c_void_p, PF, PF, PI32]),
     "sg_call_prios_dev": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p]),
     "sg_call_prios_from_progs": (c_int, [c_void_p, P32, P64, c_size_t, PF, PF, PI32]),
+    "sg_prog_hashes": (c_int, [c_void_p, P8, P64, c_size_t, P8, P8]),  # (hex: char*, bound as bytes)
+    "sg_prog_hashes_dev": (c_int, [c_void_p, c_void_p, c_void_p, c_uint64, c_uint64, c_void_p]),
+    "sg_sigset_create": (c_int, [c_void_p, c_uint64, POINTER(c_void_p)]),
+    "sg_sigset_destroy": (None, [c_void_p]),
+    "sg_sigset_clear": (c_int, [c_void_p]),
+    "sg_sigset_count": (c_int, [c_void_p, P64]),
+    "sg_sigset_export": (c_int, [c_void_p, P8, c_size_t, PSZ]),
+    "sg_sigset_contains": (c_int, [c_void_p, P8, c_size_t, P8]),
+    "sg_sigset_add_new": (c_int, [c_void_p, P8, c_size_t, P8]),
+    "sg_sigset_add_progs": (c_int, [c_void_p, P8, P64, c_size_t, P8, P8]),
+    "sg_hub_sync": (c_int, [c_void_p, P8, P64, c_size_t, P8, P8, P8, c_size_t, PSZ]),
     "sg_ipc_parse": (c_int, [c_void_p, P32, P64, P64, P32, c_size_t, POINTER(c_int64), P8, POINTER(c_int32), P64, P32,
                              P64, P32]),
     "sg_ipc_parse_dev": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_uint64, c_uint64, c_void_p,

@@ -85,6 +85,8 @@ class Context:
         new list that Intersection holds in LDS at a time),
         the call priorities' "prio_bad_ids" (ids the device form skipped) and its constants "prio_band_cells" /
         "prio_short_len",
+        the program identities' "sha1_long_progs" (programs that took the long SHA-1 path on this context) and
+        its constant "sha1_long_len",
         the last ordered-output call's "owned_big_records",
         the last merge's pairs per path "merge_pairs_generic" / "merge_pairs_diff_small" /
         "merge_pairs_gap" / "merge_pairs_tile", the last Canonicalize's "canon_wave_lists" /

@@ -831,7 +831,14 @@ int sg_ctx_counter(sg_ctx* ctx, const char* name, uint64_t* out) {
     SG_HIP(hipStreamSynchronize(ctx->stream));
     SG_HIP(hipMemcpy(&v, ctx->own_big + kPrioBadSlot, 8, hipMemcpyDeviceToHost));
     *out = v;
-  } else if (!strcmp(name, "prio_band_cells"))  // u32 cells of a row band of the pair count
+  } else if (!strcmp(name, "sha1_long_progs")) {  // programs that took the long SHA-1 path on this context (sg_prog_hash.hip)
+    uint64_t v = 0;
+    SG_HIP(hipStreamSynchronize(ctx->stream));
+    SG_HIP(hipMemcpy(&v, ctx->own_big + kSha1LongSlot, 8, hipMemcpyDeviceToHost));
+    *out = v;
+  } else if (!strcmp(name, "sha1_long_len"))  // bytes of the longest program on the short SHA-1 path (SG_SHA1_LONG)
+    *out = kSha1Long;
+  else if (!strcmp(name, "prio_band_cells"))  // u32 cells of a row band of the pair count
     *out = kPrioBandCells;
   else if (!strcmp(name, "prio_short_len"))  // calls of a program on the pair count's band path
     *out = kPrioShort;

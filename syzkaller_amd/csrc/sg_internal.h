@@ -365,6 +365,11 @@ constexpr uint32_t kPrioBadSlot = 24;
 // read by sg_ctx_counter as "prio_band_cells" and "prio_short_len"
 constexpr uint32_t kPrioBandCells = 40960;  // u32 cells of a row band: the CU's 160 KiB of LDS
 constexpr uint32_t kPrioShort = 64;         // calls of a program on the band path; longer ones take k_prio_long
+// ... and at u32 slot kSha1LongSlot one 64-bit counter, "sha1_long_progs": the
+// programs that took sg_prog_hash.hip's long path on this context
+constexpr uint32_t kSha1LongSlot = 28;
+// read by sg_ctx_counter as "sha1_long_len" (SG_SHA1_LONG)
+constexpr uint32_t kSha1Long = SG_SHA1_LONG;
 // read by sg_ctx_counter as "triage_runs_sort_cap" and "tinput_chunk"
 constexpr uint32_t kTrSort = 8192;    // values the cover fold sorts in LDS (64 KiB of keys)
 constexpr uint32_t kTinChunk = 8192;  // values of a per LDS chunk of tin_intersect (32 KiB)
@@ -405,6 +410,16 @@ int merge_dev(sg_ctx* ctx, int op, const uint32_t* da, const uint32_t* db, uint3
 int hints_replacers(sg_ctx* ctx, const uint64_t* d_pair_off, const uint64_t* d_pairs, uint64_t nrec,
                     const uint64_t* d_val_off, const uint64_t* d_vals, uint64_t nvals, uint64_t* d_rep_off,
                     uint64_t* d_reps, uint64_t cap, bool reps_in_ws, uint64_t** ws_reps);
+
+// sg_prog_hashes_dev's body (sg_prog_hash.hip; ctx lock held, the device
+// ensured): d_sigs[20 * p ..) = SHA-1 of program p, every range clamped to
+// nbytes.  Uses prog_hashes_ws(nprogs) bytes of the workspace from ws_used on,
+// reserved by the caller.  nprogs < 2^32.
+size_t prog_hashes_ws(uint64_t nprogs);
+int prog_hashes(sg_ctx* ctx, const uint8_t* d_bytes, const uint64_t* d_off, uint64_t nprogs, uint64_t nbytes,
+                uint8_t* d_sigs, size_t ws_used);
+// what the host forms over program texts reject (fn names the caller)
+int prog_texts_ok(const char* fn, const uint8_t* bytes, const uint64_t* off, size_t nprogs);
 
 }  // namespace sg
 

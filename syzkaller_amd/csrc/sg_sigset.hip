@@ -1,0 +1,587 @@
+// sg_sigset.hip -- map[hash.Sig]bool on the device and hubSync's diff over it:
+// the fuzzer's corpusHashes (syz-fuzzer/fuzzer.go:480-484), the manager's
+// hubCorpus and its Add / Del (syz-manager/manager.go:1021-1025, :1053-1069),
+// minimizeCorpus' sweep (:788-793), loadDB's check (syz-hub/state/state.go:91-101).
+//
+// A set is a dense store of 20-byte keys (five u32 words each, insertion
+// order) and an open-addressing table of u32 indices with a power-of-two number
+// of slots, at most half of them used.  Index i < count names store key i;
+// count <= i < count + n names key i - count of the batch's scratch area,
+// which an earlier launch (the SHA-1 kernels, or a copy) has written: every
+// key a kernel of this file compares is complete and visible since a kernel
+// boundary.  kEmpty is an index value, never a key value.
+//
+// No thread ever waits for another (the first-owner idiom of DESIGN 2):
+//  * k_ss_insert, a thread per batch key, probes from the key's home slot
+//    (its first four bytes, little-endian, masked).  Empty slot: atomicCAS
+//    the own index in.  Occupied (or the CAS lost): compare the 20 bytes the
+//    slot's index names with the own ones; equal: atomicMin the own index in
+//    and stop; unequal: next slot.  A slot's key class never changes once
+//    claimed, so a stale read of a slot is either "empty" (the CAS then
+//    returns the truth) or an index of the class it will always hold.  Only
+//    32-bit words are exchanged inside the launch.
+//  * k_ss_flags (a later launch): is_new[k] iff the slot found for key k holds
+//    k's own index.  An old key's index is below every batch index, so the
+//    atomicMin leaves it in place.
+//  * scan_counts over the flags, then k_ss_compact: owner k's key goes to
+//    store[count + pos[k]] and its slot takes that final index.  The store
+//    stays exactly the set, in insertion order.
+// Growth rebuilds a larger table from the store by the same insert kernel
+// before the batch is inserted; the store is reallocated with a device copy.
+// Every index is checked against count + n before it is used as an address,
+// and every probe loop is bounded by the number of slots.
+#include "sg_internal.h"
+
+#include <algorithm>
+#include <cstddef>
+
+struct sg_sigset {
+  sg_ctx* ctx = nullptr;
+  uint64_t count = 0;  // identities held (kept on the host: every call that changes it waits)
+  uint32_t* store = nullptr;
+  uint64_t store_cap = 0;  // keys
+  uint32_t* table = nullptr;
+  uint64_t nslots = 0;
+  // hub_sync's second pair: built from the corpus, then swapped with the first
+  uint32_t* store2 = nullptr;
+  uint64_t store2_cap = 0;
+  uint32_t* table2 = nullptr;
+  uint64_t nslots2 = 0;
+};
+static_assert(offsetof(sg_sigset, count) == 8, "tests/test_prog_hashes.py plants a count in a readable block");
+
+namespace sg {
+namespace {
+
+constexpr uint32_t kEmpty = 0xFFFFFFFFu;
+constexpr uint32_t kKeyDw = SG_SIG_BYTES / 4;
+constexpr uint64_t kMaxKeys = 1ull << 31;
+constexpr uint64_t kMinSlots = 64;
+constexpr uint32_t kST = 256;
+
+struct View {
+  const uint32_t* store;
+  uint32_t count;
+  const uint64_t* count_dev;  // when set: the count, device-resident (hub_sync's fresh set)
+  const uint32_t* scratch;
+  uint32_t n;
+  uint32_t* table;
+  uint32_t mask;  // slots - 1
+};
+
+__device__ __forceinline__ uint32_t view_count(const View& v) {
+  return v.count_dev ? (uint32_t)min<uint64_t>(*v.count_dev, 0x7FFFFFFFull) : v.count;
+}
+
+// the key index i names, or null for an index that names none
+__device__ __forceinline__ const uint32_t* key_at(const View& v, uint32_t count, uint32_t i) {
+  if (i < count) return v.store + (uint64_t)i * kKeyDw;
+  if (i - count < v.n) return v.scratch + (uint64_t)(i - count) * kKeyDw;
+  return nullptr;
+}
+
+__device__ __forceinline__ bool key_eq(const uint32_t* a, const uint32_t k[kKeyDw]) {
+  bool eq = true;
+#pragma unroll
+  for (uint32_t w = 0; w < kKeyDw; w++) eq = eq && a[w] == k[w];
+  return eq;
+}
+
+__device__ __forceinline__ void key_load(const uint32_t* p, uint32_t k[kKeyDw]) {
+#pragma unroll
+  for (uint32_t w = 0; w < kKeyDw; w++) k[w] = p[w];
+}
+
+// the slot that holds k's class, or kEmpty; reads only
+__device__ __forceinline__ uint32_t find_slot(const View& v, uint32_t count, const uint32_t k[kKeyDw]) {
+  uint32_t s = k[0] & v.mask;
+  for (uint32_t probe = 0; probe <= v.mask; probe++, s = (s + 1) & v.mask) {
+    const uint32_t cur = v.table[s];
+    if (cur == kEmpty) return kEmpty;
+    const uint32_t* kp = key_at(v, count, cur);
+    if (kp && key_eq(kp, k)) return s;
+  }
+  return kEmpty;
+}
+
+// indices [i0, i0 + m) into the table
+__global__ __launch_bounds__(kST) void k_ss_insert(View v, uint32_t i0, uint32_t m) {
+  const uint64_t t = (uint64_t)blockIdx.x * kST + threadIdx.x;
+  if (t >= m) return;
+  const uint32_t idx = i0 + (uint32_t)t;
+  const uint32_t* own = key_at(v, v.count, idx);
+  if (!own) return;
+  uint32_t k[kKeyDw];
+  key_load(own, k);
+  uint32_t s = k[0] & v.mask;
+  for (uint32_t probe = 0; probe <= v.mask; probe++, s = (s + 1) & v.mask) {
+    uint32_t cur = __hip_atomic_load(&v.table[s], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (cur == kEmpty) {
+      cur = atomicCAS(&v.table[s], kEmpty, idx);
+      if (cur == kEmpty) return;  // claimed
+    }
+    const uint32_t* kp = key_at(v, v.count, cur);
+    if (kp && key_eq(kp, k)) {
+      atomicMin(&v.table[s], idx);
+      return;
+    }
+  }
+}
+
+// batch key t: its slot, and whether it owns it
+__global__ __launch_bounds__(kST) void k_ss_flags(View v, uint32_t* __restrict__ flag, uint32_t* __restrict__ slot,
+                                                   uint8_t* __restrict__ is_new) {
+  const uint64_t t = (uint64_t)blockIdx.x * kST + threadIdx.x;
+  if (t >= v.n) return;
+  uint32_t k[kKeyDw];
+  key_load(v.scratch + t * kKeyDw, k);
+  const uint32_t s = find_slot(v, v.count, k);
+  const uint32_t f = s != kEmpty && v.table[s] == v.count + (uint32_t)t;
+  flag[t] = f;
+  slot[t] = s;
+  if (is_new) is_new[t] = (uint8_t)f;
+}
+
+// owners onto the store's tail, their slots to the final indices
+__global__ __launch_bounds__(kST) void k_ss_compact(View v, const uint32_t* __restrict__ flag,
+                                                     const uint32_t* __restrict__ slot, const uint64_t* __restrict__ pos,
+                                                     uint32_t* __restrict__ store, uint64_t store_cap) {
+  const uint64_t t = (uint64_t)blockIdx.x * kST + threadIdx.x;
+  if (t >= v.n || !flag[t]) return;
+  const uint64_t dst = (uint64_t)v.count + pos[t];
+  const uint32_t s = slot[t];
+  if (dst >= store_cap || s > v.mask) return;
+#pragma unroll
+  for (uint32_t w = 0; w < kKeyDw; w++) store[dst * kKeyDw + w] = v.scratch[t * kKeyDw + w];
+  v.table[s] = (uint32_t)dst;
+}
+
+// out[t] = 1 iff key t of `keys` is in the set v (want == 1) or is not (want == 0); with `only`, keys whose
+// only[t] is zero give 0
+__global__ __launch_bounds__(kST) void k_ss_lookup(View v, const uint32_t* __restrict__ keys, uint64_t n,
+                                                    const uint32_t* __restrict__ only, uint32_t want,
+                                                    uint8_t* __restrict__ out8, uint32_t* __restrict__ out32) {
+  const uint64_t t = (uint64_t)blockIdx.x * kST + threadIdx.x;
+  if (t >= n) return;
+  uint32_t r = 0;
+  if (!only || only[t]) {
+    uint32_t k[kKeyDw];
+    key_load(keys + t * kKeyDw, k);
+    const uint32_t found = find_slot(v, view_count(v), k) != kEmpty;
+    r = found == want;
+  }
+  if (out8) out8[t] = (uint8_t)r;
+  if (out32) out32[t] = r;
+}
+
+// keys with flag set, in order, to out[pos[t]]
+__global__ __launch_bounds__(kST) void k_ss_gather(const uint32_t* __restrict__ keys, uint64_t n,
+                                                    const uint32_t* __restrict__ flag, const uint64_t* __restrict__ pos,
+                                                    uint32_t* __restrict__ out, uint64_t cap) {
+  const uint64_t t = (uint64_t)blockIdx.x * kST + threadIdx.x;
+  if (t >= n || !flag[t] || pos[t] >= cap) return;
+#pragma unroll
+  for (uint32_t w = 0; w < kKeyDw; w++) out[pos[t] * kKeyDw + w] = keys[t * kKeyDw + w];
+}
+
+uint64_t slots_for(uint64_t keys) {
+  uint64_t s = kMinSlots;
+  while (s < 2 * keys) s *= 2;
+  return s;
+}
+
+int launch_insert(sg_ctx* ctx, const View& v, uint32_t i0, uint32_t m) {
+  if (!m) return SG_OK;
+  ScopedTimer tm(ctx, "sigset_insert");
+  hipLaunchKernelGGL(k_ss_insert, dim3(div_up(m, kST)), dim3(kST), 0, ctx->stream, v, i0, m);
+  SG_HIP(hipGetLastError());
+  return SG_OK;
+}
+
+// a table of at least `slots` slots, all empty
+int table_fresh(sg_ctx* ctx, uint32_t** table, uint64_t* nslots, uint64_t slots) {
+  if (*nslots < slots) {
+    if (*table) {
+      SG_HIP(hipStreamSynchronize(ctx->stream));
+      SG_HIP(hipFree(*table));
+      *table = nullptr;
+      *nslots = 0;
+    }
+    SG_HIP(hipMalloc(table, slots * 4));
+    *nslots = slots;
+  }
+  SG_HIP(hipMemsetAsync(*table, 0xFF, *nslots * 4, ctx->stream));
+  return SG_OK;
+}
+
+// room for `keys` keys in a store, the first `keep` kept
+int store_reserve(sg_ctx* ctx, uint32_t** store, uint64_t* cap, uint64_t keys, uint64_t keep) {
+  if (keys <= *cap) return SG_OK;
+  uint64_t nc = std::max<uint64_t>(*cap * 2, 1024);
+  while (nc < keys) nc *= 2;
+  uint32_t* ns = nullptr;
+  SG_HIP(hipMalloc(&ns, nc * SG_SIG_BYTES));
+  hipError_t e = hipSuccess;
+  if (*store && keep) e = hipMemcpyAsync(ns, *store, keep * SG_SIG_BYTES, hipMemcpyDeviceToDevice, ctx->stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+  if (e != hipSuccess) {
+    hipFree(ns);
+    return hip_fail(e, "store_reserve");
+  }
+  if (*store) SG_HIP(hipFree(*store));
+  *store = ns;
+  *cap = nc;
+  return SG_OK;
+}
+
+// the table sized for count + n keys: a larger one is rebuilt from the store
+int grow_for(sg_sigset* s, uint64_t n) {
+  sg_ctx* ctx = s->ctx;
+  int rc = store_reserve(ctx, &s->store, &s->store_cap, s->count + n, s->count);
+  if (rc) return rc;
+  const uint64_t need = slots_for(s->count + n);
+  if (need <= s->nslots) return SG_OK;
+  uint32_t* nt = nullptr;
+  uint64_t ns = 0;
+  if ((rc = table_fresh(ctx, &nt, &ns, need))) return rc;
+  const View v{s->store, (uint32_t)s->count, nullptr, nullptr, 0, nt, (uint32_t)(ns - 1)};
+  rc = launch_insert(ctx, v, 0, (uint32_t)s->count);
+  hipError_t e = hipStreamSynchronize(ctx->stream);
+  if (rc || e != hipSuccess) {
+    hipFree(nt);
+    return rc ? rc : hip_fail(e, "grow_for");
+  }
+  if (s->table) SG_HIP(hipFree(s->table));
+  s->table = nt;
+  s->nslots = ns;
+  return SG_OK;
+}
+
+// workspace of an add of n scratch keys: flags, slots, positions, the scan
+struct AddPlan {
+  size_t o_flag, o_slot, o_pos, o_scan, total;
+  AddPlan(size_t base, uint64_t n) {
+    o_flag = base;
+    o_slot = o_flag + align256(n * 4);
+    o_pos = o_slot + align256(n * 4);
+    o_scan = o_pos + align256((n + 1) * 8);
+    total = o_scan + scan_ws_bytes(n);
+  }
+};
+
+// insert, flags, scan, compact of n scratch keys (device) into {store, table} holding `count`; is_new nullable.
+// The new count is count + pos[n] (device, at ws o_pos + 8 * n).
+int add_scratch(sg_ctx* ctx, uint32_t* store, uint64_t store_cap, uint32_t* table, uint64_t nslots, uint64_t count,
+                const uint32_t* d_keys, uint64_t n, const AddPlan& ap, uint8_t* d_is_new) {
+  const View v{store, (uint32_t)count, nullptr, d_keys, (uint32_t)n, table, (uint32_t)(nslots - 1)};
+  uint32_t* flag = (uint32_t*)ws_at(ctx, ap.o_flag);
+  uint32_t* slot = (uint32_t*)ws_at(ctx, ap.o_slot);
+  uint64_t* pos = (uint64_t*)ws_at(ctx, ap.o_pos);
+  int rc = launch_insert(ctx, v, (uint32_t)count, (uint32_t)n);
+  if (rc) return rc;
+  if (n) {
+    ScopedTimer tm(ctx, "sigset_flags");
+    hipLaunchKernelGGL(k_ss_flags, dim3(div_up(n, kST)), dim3(kST), 0, ctx->stream, v, flag, slot, d_is_new);
+  }
+  SG_HIP(hipGetLastError());
+  if ((rc = scan_counts(ctx, flag, pos, n, ap.o_scan))) return rc;
+  if (n) {
+    ScopedTimer tm(ctx, "sigset_compact");
+    hipLaunchKernelGGL(k_ss_compact, dim3(div_up(n, kST)), dim3(kST), 0, ctx->stream, v, (const uint32_t*)flag,
+                       (const uint32_t*)slot, (const uint64_t*)pos, store, store_cap);
+  }
+  SG_HIP(hipGetLastError());
+  return SG_OK;
+}
+
+int sigs_ok(const char* fn, const sg_sigset* s, const uint8_t* sigs, size_t n, const uint8_t* out) {
+  if (!s || (n && (!sigs || !out))) {
+    set_error("%s: invalid argument", fn);
+    return SG_EINVAL;
+  }
+  if ((uint64_t)n >= kMaxKeys) {
+    set_error("%s: %llu identities (the limit is 2^31 - 1)", fn, (unsigned long long)n);
+    return SG_EINVAL;
+  }
+  return SG_OK;
+}
+
+int room_ok(const char* fn, const sg_sigset* s, uint64_t n) {
+  if (s->count + n >= kMaxKeys) {
+    set_error("%s: the set would reach 2^31 identities", fn);
+    return SG_EINVAL;
+  }
+  return SG_OK;
+}
+
+void set_free(sg_sigset* s) {
+  if (s->store) hipFree(s->store);
+  if (s->table) hipFree(s->table);
+  if (s->store2) hipFree(s->store2);
+  if (s->table2) hipFree(s->table2);
+  delete s;
+}
+
+// sg_sigset_add_new / _add_progs after the checks; keys: host identities, or null to hash the programs
+int add_common(sg_sigset* s, const uint8_t* keys, const uint8_t* bytes, const uint64_t* off, size_t n, uint8_t* sigs,
+               uint8_t* is_new) {
+  sg_ctx* ctx = s->ctx;
+  std::lock_guard<std::mutex> g(ctx->mu);
+  int rc = ensure_device(ctx);
+  if (rc) return rc;
+  if (n == 0) return SG_OK;
+  const uint64_t nbytes = keys ? 0 : off[n];
+  WsPlan plan;
+  const size_t o_keys = plan.add(n * SG_SIG_BYTES), o_new = plan.add(n), o_bytes = plan.add(nbytes + 4),
+               o_off = plan.add((n + 1) * 8);
+  if ((rc = dstage_reserve(ctx, plan))) return rc;
+  const size_t hash_ws = keys ? 0 : align256(prog_hashes_ws(n));
+  const AddPlan ap(hash_ws, n);
+  if ((rc = ws_reserve(ctx, ap.total))) return rc;
+  if ((rc = grow_for(s, n))) return rc;
+  uint32_t* dkeys = dstage_at<uint32_t>(ctx, o_keys);
+  uint8_t* dnew = dstage_at<uint8_t>(ctx, o_new);
+  if (keys) {
+    if ((rc = upload(ctx, dkeys, keys, n * SG_SIG_BYTES))) return rc;
+  } else {
+    uint8_t* dbytes = dstage_at<uint8_t>(ctx, o_bytes);
+    uint64_t* doff = dstage_at<uint64_t>(ctx, o_off);
+    if ((rc = upload(ctx, dbytes, bytes, nbytes))) return rc;
+    if ((rc = upload(ctx, doff, off, (n + 1) * 8))) return rc;
+    if ((rc = prog_hashes(ctx, dbytes, doff, n, nbytes, (uint8_t*)dkeys, 0))) return rc;
+    if (sigs) SG_HIP(hipMemcpyAsync(sigs, dkeys, n * SG_SIG_BYTES, hipMemcpyDeviceToHost, ctx->stream));
+  }
+  if ((rc = add_scratch(ctx, s->store, s->store_cap, s->table, s->nslots, s->count, dkeys, n, ap, dnew))) return rc;
+  uint64_t added = 0;
+  SG_HIP(hipMemcpyAsync(is_new, dnew, n, hipMemcpyDeviceToHost, ctx->stream));
+  SG_HIP(hipMemcpyAsync(&added, (uint64_t*)ws_at(ctx, ap.o_pos) + n, 8, hipMemcpyDeviceToHost, ctx->stream));
+  SG_HIP(hipStreamSynchronize(ctx->stream));
+  s->count += std::min<uint64_t>(added, n);
+  return SG_OK;
+}
+
+}  // namespace
+}  // namespace sg
+
+using namespace sg;
+
+extern "C" {
+
+int sg_sigset_create(sg_ctx* ctx, uint64_t capacity_hint, sg_sigset** out) {
+  const char* fn = "sg_sigset_create";
+  if (!ctx || !out) {
+    set_error("%s: invalid argument", fn);
+    return SG_EINVAL;
+  }
+  *out = nullptr;
+  if (capacity_hint >= kMaxKeys) {
+    set_error("%s: a hint of %llu identities (the limit is 2^31 - 1)", fn, (unsigned long long)capacity_hint);
+    return SG_EINVAL;
+  }
+  std::lock_guard<std::mutex> g(ctx->mu);
+  int rc = ensure_device(ctx);
+  if (rc) return rc;
+  sg_sigset* s = new sg_sigset();
+  s->ctx = ctx;
+  rc = grow_for(s, std::max<uint64_t>(capacity_hint, 1));
+  if (rc) {
+    set_free(s);
+    return rc;
+  }
+  *out = s;
+  return SG_OK;
+}
+
+void sg_sigset_destroy(sg_sigset* s) {
+  if (!s) return;
+  {
+    std::lock_guard<std::mutex> g(s->ctx->mu);
+    hipSetDevice(s->ctx->device);
+    hipStreamSynchronize(s->ctx->stream);
+  }
+  set_free(s);
+}
+
+int sg_sigset_clear(sg_sigset* s) {
+  if (!s) {
+    set_error("sg_sigset_clear: invalid argument");
+    return SG_EINVAL;
+  }
+  sg_ctx* ctx = s->ctx;
+  std::lock_guard<std::mutex> g(ctx->mu);
+  int rc = ensure_device(ctx);
+  if (rc) return rc;
+  SG_HIP(hipMemsetAsync(s->table, 0xFF, s->nslots * 4, ctx->stream));
+  s->count = 0;
+  return SG_OK;
+}
+
+int sg_sigset_count(sg_sigset* s, uint64_t* out) {
+  if (!s || !out) {
+    set_error("sg_sigset_count: invalid argument");
+    return SG_EINVAL;
+  }
+  std::lock_guard<std::mutex> g(s->ctx->mu);
+  *out = s->count;
+  return SG_OK;
+}
+
+int sg_sigset_export(sg_sigset* s, uint8_t* sigs, size_t cap, size_t* n) {
+  if (!s || !n || (cap && !sigs)) {
+    set_error("sg_sigset_export: invalid argument");
+    return SG_EINVAL;
+  }
+  sg_ctx* ctx = s->ctx;
+  std::lock_guard<std::mutex> g(ctx->mu);
+  int rc = ensure_device(ctx);
+  if (rc) return rc;
+  *n = s->count;
+  if (s->count && s->count <= cap) {
+    SG_HIP(hipMemcpyAsync(sigs, s->store, s->count * SG_SIG_BYTES, hipMemcpyDeviceToHost, ctx->stream));
+    SG_HIP(hipStreamSynchronize(ctx->stream));
+  }
+  return SG_OK;
+}
+
+int sg_sigset_contains(sg_sigset* s, const uint8_t* sigs, size_t n, uint8_t* present) {
+  int rc = sigs_ok("sg_sigset_contains", s, sigs, n, present);
+  if (rc) return rc;
+  sg_ctx* ctx = s->ctx;
+  std::lock_guard<std::mutex> g(ctx->mu);
+  rc = ensure_device(ctx);
+  if (rc) return rc;
+  if (n == 0) return SG_OK;
+  WsPlan plan;
+  const size_t o_keys = plan.add(n * SG_SIG_BYTES), o_out = plan.add(n);
+  if ((rc = dstage_reserve(ctx, plan))) return rc;
+  uint32_t* dkeys = dstage_at<uint32_t>(ctx, o_keys);
+  uint8_t* dout = dstage_at<uint8_t>(ctx, o_out);
+  if ((rc = upload(ctx, dkeys, sigs, n * SG_SIG_BYTES))) return rc;
+  const View v{s->store, (uint32_t)s->count, nullptr, nullptr, 0, s->table, (uint32_t)(s->nslots - 1)};
+  {
+    ScopedTimer tm(ctx, "sigset_lookup");
+    hipLaunchKernelGGL(k_ss_lookup, dim3(div_up(n, kST)), dim3(kST), 0, ctx->stream, v, (const uint32_t*)dkeys, (uint64_t)n,
+                       (const uint32_t*)nullptr, 1u, dout, (uint32_t*)nullptr);
+  }
+  SG_HIP(hipGetLastError());
+  SG_HIP(hipMemcpyAsync(present, dout, n, hipMemcpyDeviceToHost, ctx->stream));
+  SG_HIP(hipStreamSynchronize(ctx->stream));
+  return SG_OK;
+}
+
+int sg_sigset_add_new(sg_sigset* s, const uint8_t* sigs, size_t n, uint8_t* is_new) {
+  const char* fn = "sg_sigset_add_new";
+  int rc = sigs_ok(fn, s, sigs, n, is_new);
+  if (rc) return rc;
+  if ((rc = room_ok(fn, s, n))) return rc;
+  return add_common(s, sigs, nullptr, nullptr, n, nullptr, is_new);
+}
+
+int sg_sigset_add_progs(sg_sigset* s, const uint8_t* bytes, const uint64_t* off, size_t nprogs, uint8_t* sigs,
+                        uint8_t* is_new) {
+  const char* fn = "sg_sigset_add_progs";
+  if (!s || (nprogs && !is_new)) {
+    set_error("%s: invalid argument", fn);
+    return SG_EINVAL;
+  }
+  int rc = prog_texts_ok(fn, bytes, off, nprogs);
+  if (rc) return rc;
+  if ((uint64_t)nprogs >= kMaxKeys) {
+    set_error("%s: %llu programs (the limit is 2^31 - 1)", fn, (unsigned long long)nprogs);
+    return SG_EINVAL;
+  }
+  if ((rc = room_ok(fn, s, nprogs))) return rc;
+  return add_common(s, nullptr, bytes, off, nprogs, sigs, is_new);
+}
+
+int sg_hub_sync(sg_sigset* hub, const uint8_t* bytes, const uint64_t* off, size_t nprogs, uint8_t* sigs, uint8_t* add,
+                uint8_t* del_sigs, size_t del_cap, size_t* ndel) {
+  const char* fn = "sg_hub_sync";
+  if (!hub || !ndel || (nprogs && !add) || (del_cap && !del_sigs)) {
+    set_error("%s: invalid argument", fn);
+    return SG_EINVAL;
+  }
+  int rc = prog_texts_ok(fn, bytes, off, nprogs);
+  if (rc) return rc;
+  if ((uint64_t)nprogs >= kMaxKeys) {
+    set_error("%s: %llu programs (the limit is 2^31 - 1)", fn, (unsigned long long)nprogs);
+    return SG_EINVAL;
+  }
+  if ((uint64_t)del_cap < hub->count) {  // (read before the lock: a set is one caller's at a time, as the map is under mgr.mu)
+    set_error("%s: del_cap %llu below the set's %llu identities", fn, (unsigned long long)del_cap,
+              (unsigned long long)hub->count);
+    return SG_EINVAL;
+  }
+  sg_ctx* ctx = hub->ctx;
+  std::lock_guard<std::mutex> g(ctx->mu);
+  rc = ensure_device(ctx);
+  if (rc) return rc;
+  const uint64_t n = nprogs, c = hub->count, nbytes = off[nprogs];
+  // staging: the corpus, its identities, add, the deleted identities; workspace: the hashes', the add's, the del's
+  WsPlan plan;
+  const size_t o_keys = plan.add(n * SG_SIG_BYTES + 4), o_add = plan.add(n + 1), o_bytes = plan.add(nbytes + 4),
+               o_off = plan.add((n + 1) * 8), o_del = plan.add(c * SG_SIG_BYTES + 4);
+  if ((rc = dstage_reserve(ctx, plan))) return rc;
+  const AddPlan ap(align256(prog_hashes_ws(n)), n);
+  const size_t o_dflag = ap.total, o_dpos = o_dflag + align256(c * 4 + 4), o_dscan = o_dpos + align256((c + 1) * 8);
+  if ((rc = ws_reserve(ctx, o_dscan + scan_ws_bytes(c)))) return rc;
+  if ((rc = store_reserve(ctx, &hub->store2, &hub->store2_cap, std::max<uint64_t>(n, 1), 0))) return rc;
+  if ((rc = table_fresh(ctx, &hub->table2, &hub->nslots2, slots_for(n)))) return rc;
+  uint32_t* dkeys = dstage_at<uint32_t>(ctx, o_keys);
+  uint8_t* dadd = dstage_at<uint8_t>(ctx, o_add);
+  uint32_t* ddel = dstage_at<uint32_t>(ctx, o_del);
+  if (n) {
+    uint8_t* dbytes = dstage_at<uint8_t>(ctx, o_bytes);
+    uint64_t* doff = dstage_at<uint64_t>(ctx, o_off);
+    if ((rc = upload(ctx, dbytes, bytes, nbytes))) return rc;
+    if ((rc = upload(ctx, doff, off, (n + 1) * 8))) return rc;
+    if ((rc = prog_hashes(ctx, dbytes, doff, n, nbytes, (uint8_t*)dkeys, 0))) return rc;
+    if (sigs) SG_HIP(hipMemcpyAsync(sigs, dkeys, n * SG_SIG_BYTES, hipMemcpyDeviceToHost, ctx->stream));
+  }
+  // the fresh set: the corpus' identities in first-occurrence order
+  if ((rc = add_scratch(ctx, hub->store2, hub->store2_cap, hub->table2, hub->nslots2, 0, dkeys, n, ap, nullptr))) return rc;
+  const uint32_t* flag = (const uint32_t*)ws_at(ctx, ap.o_flag);
+  const uint64_t* count2 = (const uint64_t*)ws_at(ctx, ap.o_pos) + n;
+  const View vold{hub->store, (uint32_t)c, nullptr, nullptr, 0, hub->table, (uint32_t)(hub->nslots - 1)};
+  const View vnew{hub->store2, 0, count2, nullptr, 0, hub->table2, (uint32_t)(hub->nslots2 - 1)};
+  uint32_t* dflag = (uint32_t*)ws_at(ctx, o_dflag);
+  uint64_t* dpos = (uint64_t*)ws_at(ctx, o_dpos);
+  {
+    ScopedTimer tm(ctx, "hub_sync_diff");
+    // Add: the owners the old set does not hold
+    if (n)
+      hipLaunchKernelGGL(k_ss_lookup, dim3(div_up(n, kST)), dim3(kST), 0, ctx->stream, vold, (const uint32_t*)dkeys, n, flag,
+                         0u, dadd, (uint32_t*)nullptr);
+    // Del: the old identities the fresh set does not hold
+    if (c)
+      hipLaunchKernelGGL(k_ss_lookup, dim3(div_up(c, kST)), dim3(kST), 0, ctx->stream, vnew, (const uint32_t*)hub->store, c,
+                         (const uint32_t*)nullptr, 0u, (uint8_t*)nullptr, dflag);
+  }
+  SG_HIP(hipGetLastError());
+  if ((rc = scan_counts(ctx, dflag, dpos, c, o_dscan))) return rc;
+  if (c) {
+    ScopedTimer tm(ctx, "hub_sync_gather");
+    hipLaunchKernelGGL(k_ss_gather, dim3(div_up(c, kST)), dim3(kST), 0, ctx->stream, (const uint32_t*)hub->store, c,
+                       (const uint32_t*)dflag, (const uint64_t*)dpos, ddel, c);
+  }
+  SG_HIP(hipGetLastError());
+  uint64_t got[2] = {0, 0};  // the fresh set's count, the deleted identities
+  if (n) SG_HIP(hipMemcpyAsync(add, dadd, n, hipMemcpyDeviceToHost, ctx->stream));
+  SG_HIP(hipMemcpyAsync(&got[0], count2, 8, hipMemcpyDeviceToHost, ctx->stream));
+  SG_HIP(hipMemcpyAsync(&got[1], dpos + c, 8, hipMemcpyDeviceToHost, ctx->stream));
+  SG_HIP(hipStreamSynchronize(ctx->stream));
+  const uint64_t nd = std::min(got[1], c);
+  if (nd) {
+    SG_HIP(hipMemcpyAsync(del_sigs, ddel, nd * SG_SIG_BYTES, hipMemcpyDeviceToHost, ctx->stream));
+    SG_HIP(hipStreamSynchronize(ctx->stream));
+  }
+  *ndel = nd;
+  std::swap(hub->store, hub->store2);
+  std::swap(hub->store_cap, hub->store2_cap);
+  std::swap(hub->table, hub->table2);
+  std::swap(hub->nslots, hub->nslots2);
+  hub->count = std::min(got[0], n);
+  return SG_OK;
+}
+
+}  // extern "C"
