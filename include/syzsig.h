@@ -1139,6 +1139,165 @@ int sg_sigset_add_progs(sg_sigset* s, const uint8_t* bytes, const uint64_t* off,
 int sg_hub_sync(sg_sigset* hub, const uint8_t* bytes, const uint64_t* off, size_t nprogs, uint8_t* sigs, uint8_t* add,
 		uint8_t* del_sigs, size_t del_cap, size_t* ndel);
 
+/* ---- the hub's corpus: prog.CallSet, pendingInputs, purgeCorpus ------------ */
+/* syz-hub/state/state.go keeps the union of all managers' corpora, and under
+ * the hub's lock State.Sync (state.go:175-195) walks all of it for every
+ * manager's every sync: pendingInputs (state.go:265-308) tests rec.Seq, probes
+ * the manager's corpus map and re-parses every record's text with prog.CallSet
+ * (prog/encoding.go:559-592); purgeCorpus (state.go:338-354) rebuilds a `used`
+ * map from every manager's corpus and sweeps the hub's; addInputs (state.go:
+ * 310-336) parses, hashes and probes two maps per program; loadDB (state.go:
+ * 83-110) does CallSet and the hash check over the whole database.
+ *
+ * prog.CallSet, pinned (encoding.go:559-592 over bufio.Scanner / ScanLines).  A
+ * text is split at '\n'; the bytes after the last '\n' are a line only if there
+ * are any; one trailing '\r' is dropped from each line; a line that is then
+ * empty, or whose first byte is '#', is skipped.  Of any other line, bracket is
+ * the first '(' and call = ln[:bracket]; if call contains '=', it starts after
+ * the first '=' and after every ' ' (0x20 only, not a tab) that follows it.  The
+ * name is exactly those bytes: trailing blanks, tabs, NUL and bytes >= 0x80 are
+ * all part of it.  A program's status is its first failure in line order:
+ *   SG_CALLSET_OK 0; SG_CALLSET_NO_BRACKET 1 "line does not contain opening
+ *   bracket"; SG_CALLSET_EMPTY_NAME 2 "call name is empty"; SG_CALLSET_TOO_LONG
+ *   3 the scanner's ErrTooLong; SG_CALLSET_NO_CALLS 4 "program does not contain
+ *   any calls" (no failure and no call line).
+ * Too long: the scanner's buffer limit is maxLineLen = 256 << 10 (encoding.go:
+ * 382).  As bufio.Scanner.Scan is read here, a line fails exactly when its
+ * content -- the bytes before its '\n', or before the end of the text, the
+ * '\r' counted -- is SG_CALLSET_MAX_LINE bytes or more, whichever of the two
+ * ends it; it fails when the scan reaches it, so an earlier line's status 1 or
+ * 2 wins and a later one's does not.  That boundary is read, not run (Go is
+ * not needed to build or test this library): parity unpinned at this edge. */
+#define SG_CALLSET_OK 0
+#define SG_CALLSET_NO_BRACKET 1
+#define SG_CALLSET_EMPTY_NAME 2
+#define SG_CALLSET_TOO_LONG 3
+#define SG_CALLSET_NO_CALLS 4
+#define SG_CALLSET_MAX_LINE 262144
+
+/* The name dictionary: an exact interning table of call names (byte strings of
+ * any length >= 1), ids dense in order of first insertion.  It is built on the
+ * host (a target has a few thousand names): open addressing over ids, a power-
+ * of-two number of slots, at most half of them used, a name's home slot the low
+ * bits of its 64-bit FNV-1a hash with the constants below, which the kernel
+ * shares.  The device holds a mirror (name bytes, name offsets, the 64-bit
+ * hashes, the slots), uploaded again after every add that added.  Equality is
+ * always decided by comparing the bytes; the stored hash only spares most
+ * mismatches the byte compare. */
+#define SG_FNV64_OFFSET 0xcbf29ce484222325ull
+#define SG_FNV64_PRIME 0x100000001b3ull
+#define SG_NAME_UNKNOWN 0xffffffffu
+typedef struct sg_nametab sg_nametab;
+/* SG_EINVAL: a NULL ctx or out.  SG_ENODEV without a device. */
+int sg_nametab_create(sg_ctx* ctx, sg_nametab** out);
+void sg_nametab_destroy(sg_nametab* t);
+int sg_nametab_count(sg_nametab* t, uint64_t* out);
+/* ids[k] = the id of name k = bytes[off[k] .. off[k+1]), an existing name
+ * keeping its id.  SG_EINVAL, nothing added: a NULL t, ids NULL with n > 0, what
+ * sg_prog_hashes rejects of a CSR, an empty name. */
+int sg_nametab_add(sg_nametab* t, const uint8_t* bytes, const uint64_t* off, size_t n, uint32_t* ids);
+
+/* prog.CallSet (encoding.go:559-592) of every program of a CSR of texts, as
+ * each program's call lines in text order, repeats kept -- which is also what
+ * PrioTable.add takes.  status[k] as above.  Program k owns call lines
+ * line_off[k] .. line_off[k+1]; a program with status != 0 owns none.  Of call
+ * line i, name_pos[i] is the name's byte offset into `bytes`, name_len[i] its
+ * length and name_id[i] (nullable) its id in tab, SG_NAME_UNKNOWN for a name
+ * that is not in it and for every line when tab is NULL.  *nlines is always
+ * the total; the three arrays are written only when it is <= cap.  The number
+ * of '(' bytes in the batch always suffices as cap.  SG_EINVAL, before the
+ * context is touched: a NULL ctx, line_off or nlines, status NULL with nprogs
+ * > 0, name_pos or name_len NULL with cap > 0, a tab of another context, what
+ * sg_prog_hashes rejects of the CSR, 2^33 bytes of text or more.  SG_ENODEV
+ * without a device.  Two waits. */
+int sg_call_sets(sg_ctx* ctx, sg_nametab* tab, const uint8_t* bytes, const uint64_t* off, size_t nprogs, uint8_t* status,
+		 uint64_t* line_off, uint64_t* name_pos, uint32_t* name_len, uint32_t* name_id, size_t cap,
+		 size_t* nlines);
+/* Device form: every pointer is device memory (tab stays the handle), stream-
+ * ordered, nothing is read back; d_line_off[nprogs] is the total, and the
+ * arrays are written only when it is <= cap.  The offsets follow
+ * sg_prog_hashes_dev's rule: each start is clamped to nbytes and each end to
+ * [start, nbytes]; garbage offsets give garbage lines, never a read outside
+ * [d_bytes, d_bytes + nbytes).  With offsets that make programs overlap the
+ * '(' count no longer bounds the total. */
+int sg_call_sets_dev(sg_ctx* ctx, sg_nametab* tab, const uint8_t* d_bytes, const uint64_t* d_off, uint64_t nprogs,
+		     uint64_t nbytes, uint8_t* d_status, uint64_t* d_line_off, uint64_t* d_name_pos, uint32_t* d_name_len,
+		     uint32_t* d_name_id, uint64_t cap);
+
+/* mgr.Corpus.Delete(sig) over a batch (state.go:181-183): removed[k] = 1 iff
+ * sigs[k] was in the set and no j < k of the batch has the same 20 bytes.
+ * Afterwards the set is without them, the rest in their old order.  A fresh
+ * table and store are built from the survivors and swapped in, as sg_hub_sync
+ * does: no tombstones.  SG_EINVAL as sg_sigset_contains. */
+int sg_sigset_remove(sg_sigset* s, const uint8_t* sigs, size_t n, uint8_t* removed);
+
+/* st.Corpus on the device.  A record is (key, seq, call ids): the keys live in
+ * an identity set (sg_sigset's store and table), a record's index is its
+ * store index, so records are in insertion order; seq[] and a CSR of each
+ * record's call ids (line order, repeats kept) run parallel to it.  The texts
+ * stay in the host's database: the calls return keys.  Deletion rebuilds
+ * (gathered keys, seqs and ids, a fresh table), as sg_hub_sync does.
+ * Orders are insertion order and (seq, record index): the reference's are Go
+ * map iteration and an unstable sort, so these are pinned choices, not a parity
+ * claim; the selected sets, max_seq and more are parity.
+ * A seq is below SG_HUB_SEQ_LIMIT = 2^33: pending orders (seq << 31 | record
+ * index) keys with radix_sort_u64, and a corpus holds fewer than 2^31 records. */
+#define SG_HUB_SEQ_LIMIT (1ull << 33)
+typedef struct sg_hubcorpus sg_hubcorpus;
+/* The corpus lives in ctx, takes its ids from tab (of the same ctx), and must be
+ * destroyed before both.  SG_EINVAL: a NULL argument, a tab of another context. */
+int sg_hubcorpus_create(sg_ctx* ctx, sg_nametab* tab, sg_hubcorpus** out);
+void sg_hubcorpus_destroy(sg_hubcorpus* h);
+int sg_hubcorpus_count(sg_hubcorpus* h, uint64_t* nrecs);
+/* Keys (20 bytes each), seqs, call_off (*nrecs + 1) and call_ids of all
+ * records, in record order.  *nrecs and *nids are always the counts; the arrays
+ * are written only when *nrecs <= cap_recs and *nids <= cap_ids. */
+int sg_hubcorpus_export(sg_hubcorpus* h, uint8_t* sigs, uint64_t* seqs, uint64_t* call_off, uint32_t* call_ids,
+			size_t cap_recs, size_t cap_ids, size_t* nrecs, size_t* nids);
+/* addInputs' loop (state.go:314-317, :326-336) and loadDB's (:91-105).
+ * status[k] is program k's CallSet status.  *nunk is the number of call lines
+ * of status-0 programs whose name is not in the dictionary.  If *nunk > 0
+ * NOTHING changes, neither the corpus nor mgr: the first min(*nunk, unk_cap)
+ * spans (offset into bytes, length) are written in text order, the caller
+ * interns them with sg_nametab_add and calls again.  So every stored record's
+ * ids are known ids for good: no cached SG_NAME_UNKNOWN can go stale when a
+ * later manager brings the name -- that is the reason for this protocol.
+ * Otherwise, for each status-0 program in batch order: its SHA-1 enters mgr
+ * (nullable; sg_sigset_add_new's semantics; :332); if it is neither in the
+ * corpus nor an earlier program's of the batch it is appended with seqs[k] and
+ * its ids (:333-335), and is_new[k] says so.  Programs with status != 0 are
+ * skipped (:327-330, :92-96).  sigs (nullable) receives all nprogs hashes.
+ * SG_EINVAL, before the context is touched: a NULL h, nunk, or with nprogs > 0
+ * seqs, status or is_new; unk_pos or unk_len NULL with unk_cap > 0; a mgr of
+ * another context; what sg_call_sets rejects of the CSR; a seqs value of
+ * SG_HUB_SEQ_LIMIT or more; the corpus or mgr would reach 2^31 records. */
+int sg_hubcorpus_add(sg_hubcorpus* h, sg_sigset* mgr, const uint8_t* bytes, const uint64_t* off, size_t nprogs,
+		     const uint64_t* seqs, uint8_t* status, uint8_t* is_new, uint8_t* sigs, uint64_t* unk_pos,
+		     uint32_t* unk_len, size_t unk_cap, size_t* nunk);
+/* pendingInputs (state.go:265-308); reads only.  With mgr_seq == hub_seq: *n =
+ * 0, *more = 0, *max_seq = hub_seq (the early return, :266-268).  Otherwise the
+ * records with seq > mgr_seq, key not in mgr, and every call id's bit set in
+ * mask (nwords 64-bit words; an id at or beyond 64 * nwords is not supported)
+ * are selected; *max_seq = hub_seq, *more = 0; and if more than max_records
+ * were selected they are ordered by seq, pos = max_records, *max_seq =
+ * seq[pos], pos extends over equal seqs, pos++, *more = len - pos and [0, pos)
+ * is kept (:286-300; index max_records is record number max_records + 1).
+ * Output: keys and seqs in ascending (seq, record index) order.  *n is always
+ * the count; the arrays are written only when it is <= cap; the corpus' count
+ * always suffices.  SG_EINVAL: a NULL h, mgr, n, max_seq or more; mask NULL with
+ * nwords > 0; sigs or seqs NULL with cap > 0; a mgr of another context. */
+int sg_hubcorpus_pending(sg_hubcorpus* h, sg_sigset* mgr, uint64_t mgr_seq, uint64_t hub_seq, const uint64_t* mask,
+			 size_t nwords, uint64_t max_records, uint8_t* sigs, uint64_t* seqs, size_t cap, size_t* n,
+			 uint64_t* max_seq, uint64_t* more);
+/* purgeCorpus (state.go:338-354): every record whose key is in none of the
+ * nmgrs sets is deleted (nmgrs == 0 deletes all); the rest keep their order.
+ * del_sigs receives the deleted keys in record order.  del_cap below the
+ * corpus' count is SG_EINVAL before any work; so are a NULL h or ndel, mgrs
+ * NULL (or a NULL or foreign entry) with nmgrs > 0, del_sigs NULL with del_cap
+ * > 0. */
+int sg_hubcorpus_purge(sg_hubcorpus* h, sg_sigset* const* mgrs, size_t nmgrs, uint8_t* del_sigs, size_t del_cap,
+		       size_t* ndel);
+
 #ifdef __cplusplus
 }
 #endif

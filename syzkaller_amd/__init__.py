@@ -9,17 +9,19 @@ one batch's triage hash-sharded by signal across GPUs (RCCL all-to-all),
 shrinkExpand over batches of argument values), and `syzkaller_amd.prio` the
 call priorities (corpus call ids to CalculatePriorities and the ChoiceTable),
 and `syzkaller_amd.corpus` the corpus' identities (pkg/hash, the identity sets
-and hubSync's Add / Del).
+and hubSync's Add / Del), and `syzkaller_amd.hub` the hub's corpus (prog.CallSet,
+the name dictionary, addInputs, pendingInputs and purgeCorpus).
 """
 from ._lib import LIB_PATH, SyzSigError, lib  # noqa: F401  (fails loudly if the library is missing)
 
 _PRIO = ("PrioTable", "CalculatePriorities", "BuildChoiceTable", "ChoiceTable")
 _CORPUS = ("Hash", "String", "prog_hashes", "SigSet", "HubSync", "VerifyKeys")
+_HUB = ("NameTable", "call_sets", "CallSet", "HubCorpus", "HubState")
 
-__all__ = ["LIB_PATH", "SyzSigError", "lib", *_PRIO, *_CORPUS]
+__all__ = ["LIB_PATH", "SyzSigError", "lib", *_PRIO, *_CORPUS, *_HUB]
 
 
-def __getattr__(name):  # syzkaller_amd.prio's and .corpus' names, bound on first use (the modules need numpy)
+def __getattr__(name):  # syzkaller_amd.prio's, .corpus' and .hub's names, bound on first use (the modules need numpy)
     if name in _PRIO:
         from . import prio
 
@@ -28,4 +30,8 @@ def __getattr__(name):  # syzkaller_amd.prio's and .corpus' names, bound on firs
         from . import corpus
 
         return getattr(corpus, name)
+    if name in _HUB:
+        from . import hub
+
+        return getattr(hub, name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

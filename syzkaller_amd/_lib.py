@@ -165,7 +165,23 @@ SIGNATURES = {
     "sg_sigset_add_new": (c_int, [c_void_p, P8, c_size_t, P8]),
     "sg_sigset_add_progs": (c_int, [c_void_p, P8, P64, c_size_t, P8, P8]),
     "sg_hub_sync": (c_int, [c_void_p, P8, P64, c_size_t, P8, P8, P8, c_size_t, PSZ]),
-    "sg_ipc_parse": (c_int, [c_void_p, P32, P64, P64, P32, c_size_t, POINTER(c_int64), P8, POINTER(c_int32), P64, P32,
+    "sg_sigset_remove": (c_int, [c_void_p, P8, c_size_t, P8]),
+    "sg_nametab_create": (c_int, [c_void_p, POINTER(c_void_p)]),
+    "sg_nametab_destroy": (None, [c_void_p]),
+    "sg_nametab_count": (c_int, [c_void_p, P64]),
+    "sg_nametab_add": (c_int, [c_void_p, P8, P64, c_size_t, P32]),
+    "sg_call_sets": (c_int, [c_void_p, c_void_p, P8, P64, c_size_t, P8, P64, P64, P32, P32, c_size_t, PSZ]),
+    "sg_call_sets_dev": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_uint64, c_uint64, c_void_p, c_void_p, c_void_p,
+                                 c_void_p, c_void_p, c_uint64]),
+    "sg_hubcorpus_create": (c_int, [c_void_p, c_void_p, POINTER(c_void_p)]),
+    "sg_hubcorpus_destroy": (None, [c_void_p]),
+    "sg_hubcorpus_count": (c_int, [c_void_p, P64]),
+    "sg_hubcorpus_export": (c_int, [c_void_p, P8, P64, P64, P32, c_size_t, c_size_t, PSZ, PSZ]),
+    "sg_hubcorpus_add": (c_int, [c_void_p, c_void_p, P8, P64, c_size_t, P64, P8, P8, P8, P64, P32, c_size_t, PSZ]),
+    "sg_hubcorpus_pending": (c_int, [c_void_p, c_void_p, c_uint64, c_uint64, P64, c_size_t, c_uint64, P8, P64, c_size_t,
+                                     PSZ, P64, P64]),
+    "sg_hubcorpus_purge": (c_int, [c_void_p, POINTER(c_void_p), c_size_t, P8, c_size_t, PSZ]),
+    "sg_ipc_parse": (c_int,[c_void_p, P32, P64, P64, P32, c_size_t, POINTER(c_int64), P8, POINTER(c_int32), P64, P32,
                              P64, P32]),
     "sg_ipc_parse_dev": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_uint64, c_uint64, c_void_p,
                                  c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),

@@ -129,6 +129,15 @@ class SigSet:
             call("sg_sigset_add_new", self.h, _p8(a), a.shape[0], _p8(out))
         return out.astype(bool)
 
+    def remove(self, sigs):
+        """mgr.Corpus.Delete over a batch (syz-hub/state/state.go:181-183): the mask of identities that were in
+        the set, first occurrences only; the rest of the set keeps its order."""
+        a = _sigs(sigs)
+        out = np.zeros(a.shape[0], U8)
+        if a.shape[0]:
+            call("sg_sigset_remove", self.h, _p8(a), a.shape[0], _p8(out))
+        return out.astype(bool)
+
     def add_progs(self, progs=None, csr=None, sigs=False):
         """Hashes the programs and adds them: the mask of new ones, and with sigs also the (n, 20) identities."""
         b, off = texts_csr(progs, csr)

@@ -201,6 +201,21 @@ struct sg_set {
   bool owned = true;
 };
 
+// map[hash.Sig]bool on the device (sg_sigset.hip)
+struct sg_sigset {
+  sg_ctx* ctx = nullptr;
+  uint64_t count = 0;  // identities held (kept on the host: every call that changes it waits)
+  uint32_t* store = nullptr;
+  uint64_t store_cap = 0;  // keys
+  uint32_t* table = nullptr;
+  uint64_t nslots = 0;
+  // the second pair: hub_sync, remove and the hub corpus' purge build the new set in it, then swap
+  uint32_t* store2 = nullptr;
+  uint64_t store2_cap = 0;
+  uint32_t* table2 = nullptr;
+  uint64_t nslots2 = 0;
+};
+
 namespace sg {
 
 // ---- host helpers (sg_ctx.hip) ----
@@ -420,6 +435,47 @@ int prog_hashes(sg_ctx* ctx, const uint8_t* d_bytes, const uint64_t* d_off, uint
                 uint8_t* d_sigs, size_t ws_used);
 // what the host forms over program texts reject (fn names the caller)
 int prog_texts_ok(const char* fn, const uint8_t* bytes, const uint64_t* off, size_t nprogs);
+
+// What sg_hub_state.hip takes from sg_sigset.hip (ctx lock held, the device
+// ensured; keys are device memory, five u32 words each).
+constexpr uint64_t kSigsetMaxKeys = 1ull << 31;
+int sigset_new(sg_ctx* ctx, uint64_t hint, sg_sigset** out);
+void sigset_delete(sg_sigset* s);
+// sg_sigset_add_new of n device keys: d_is_new ([n], nullable) as is_new; waits,
+// and s->count is the new count on return.  Leaves in the workspace, until its
+// next use, flag ([n] u32: key k entered the store) at ws_base and pos ([n + 1],
+// the flags' scan: key k went to store index old count + pos[k]) at *o_pos.
+// Uses sigset_add_ws(n) bytes from ws_base on, reserved by the caller.
+size_t sigset_add_ws(uint64_t n);
+int sigset_add_dev(sg_sigset* s, const uint32_t* d_keys, uint64_t n, uint8_t* d_is_new, size_t ws_base, size_t* o_pos);
+// out32[k] = 1 iff d_keys[k] is in s (want 1) or is not (want 0)
+int sigset_lookup_dev(sg_sigset* s, const uint32_t* d_keys, uint64_t n, uint32_t want, uint32_t* out32);
+// acc[k] |= d_keys[k] is in s
+int sigset_lookup_or_dev(sg_sigset* s, const uint32_t* d_keys, uint64_t n, uint32_t* acc);
+// The set without the keys whose keep[i] is zero, the rest in their order:
+// pos is keep's scan ([count + 1]) and newcount its total, read back by the
+// caller.  A fresh store and table, swapped in (no tombstones); waits.
+int sigset_rebuild_dev(sg_sigset* s, const uint32_t* d_keep, const uint64_t* d_pos, uint64_t newcount);
+// out[pos[t]] = keys[t] for the t < n with flag[t] != 0 and pos[t] < cap
+int sigset_gather_dev(sg_ctx* ctx, const uint32_t* d_keys, uint64_t n, const uint32_t* d_flag, const uint64_t* d_pos,
+                      uint32_t* d_out, uint64_t cap);
+
+// prog.CallSet over a batch (sg_call_set.hip; ctx lock held, the device ensured).
+// call_sets_count: d_status [nprogs] and d_line_off [nprogs + 1] (its last
+// entry the batch's call lines), from call_sets_ws(nprogs, nbytes) bytes of the
+// workspace at ws_used, reserved by the caller; offsets_checked: the host has
+// seen that they do not decrease (prog_texts_ok).  call_sets_emit, with that
+// workspace untouched since: the lines' spans and ids when the total is <= cap
+// (compared on the device).  tab may be null (every id SG_NAME_UNKNOWN).
+size_t call_sets_ws(uint64_t nprogs, uint64_t nbytes);
+int call_sets_limits(const char* fn, uint64_t nprogs, uint64_t nbytes);
+int call_sets_count(sg_ctx* ctx, const uint8_t* d_bytes, const uint64_t* d_off, uint64_t nprogs, uint64_t nbytes,
+                    uint8_t* d_status, uint64_t* d_line_off, size_t ws_used, bool offsets_checked);
+int call_sets_emit(sg_ctx* ctx, sg_nametab* tab, const uint8_t* d_bytes, const uint64_t* d_off, uint64_t nprogs,
+                   uint64_t nbytes, const uint8_t* d_status, const uint64_t* d_line_off, uint64_t* d_name_pos,
+                   uint32_t* d_name_len, uint32_t* d_name_id, uint64_t cap, size_t ws_used);
+sg_ctx* nametab_ctx(const sg_nametab* tab);
+uint64_t nametab_names(const sg_nametab* tab);
 
 }  // namespace sg
 

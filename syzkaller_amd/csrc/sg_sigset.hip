@@ -26,6 +26,12 @@
 //  * scan_counts over the flags, then k_ss_compact: owner k's key goes to
 //    store[count + pos[k]] and its slot takes that final index.  The store
 //    stays exactly the set, in insertion order.
+//  * sg_sigset_remove (mgr.Corpus.Delete, syz-hub/state/state.go:181-183):
+//    k_ss_remove_mark finds each batch key's store index and atomicMin's the
+//    batch position into first[index]; a later launch flags the removed keys
+//    (first[index] is their own position) and the survivors (first[] still
+//    empty); the survivors are gathered into the second store and a fresh
+//    table is built from it, as sg_hub_sync does: no tombstones.
 // Growth rebuilds a larger table from the store by the same insert kernel
 // before the batch is inserted; the store is reallocated with a device copy.
 // Every index is checked against count + n before it is used as an address,
@@ -35,19 +41,7 @@
 #include <algorithm>
 #include <cstddef>
 
-struct sg_sigset {
-  sg_ctx* ctx = nullptr;
-  uint64_t count = 0;  // identities held (kept on the host: every call that changes it waits)
-  uint32_t* store = nullptr;
-  uint64_t store_cap = 0;  // keys
-  uint32_t* table = nullptr;
-  uint64_t nslots = 0;
-  // hub_sync's second pair: built from the corpus, then swapped with the first
-  uint32_t* store2 = nullptr;
-  uint64_t store2_cap = 0;
-  uint32_t* table2 = nullptr;
-  uint64_t nslots2 = 0;
-};
+// (struct sg_sigset: sg_internal.h; the hub corpus of sg_hub_state.hip keeps its keys in one)
 static_assert(offsetof(sg_sigset, count) == 8, "tests/test_prog_hashes.py plants a count in a readable block");
 
 namespace sg {
@@ -182,6 +176,40 @@ __global__ __launch_bounds__(kST) void k_ss_gather(const uint32_t* __restrict__ 
   if (t >= n || !flag[t] || pos[t] >= cap) return;
 #pragma unroll
   for (uint32_t w = 0; w < kKeyDw; w++) out[pos[t] * kKeyDw + w] = keys[t * kKeyDw + w];
+}
+
+// acc[t] |= key t of `keys` is in the set v (one launch per set of the hub corpus' purge)
+__global__ __launch_bounds__(kST) void k_ss_lookup_or(View v, const uint32_t* __restrict__ keys, uint64_t n,
+                                                       uint32_t* __restrict__ acc) {
+  const uint64_t t = (uint64_t)blockIdx.x * kST + threadIdx.x;
+  if (t >= n || acc[t]) return;
+  uint32_t k[kKeyDw];
+  key_load(keys + t * kKeyDw, k);
+  if (find_slot(v, view_count(v), k) != kEmpty) acc[t] = 1;
+}
+
+// remove, first launch: batch key t names store index hit[t] (kEmpty: not in the set); first[i] becomes the
+// least t that names i.  first[] starts all kEmpty, so afterwards first[i] == kEmpty marks a survivor.
+__global__ __launch_bounds__(kST) void k_ss_remove_mark(View v, const uint32_t* __restrict__ keys, uint64_t n,
+                                                         uint32_t* __restrict__ hit, uint32_t* __restrict__ first) {
+  const uint64_t t = (uint64_t)blockIdx.x * kST + threadIdx.x;
+  if (t >= n) return;
+  uint32_t k[kKeyDw];
+  key_load(keys + t * kKeyDw, k);
+  const uint32_t s = find_slot(v, v.count, k);
+  uint32_t i = s == kEmpty ? kEmpty : v.table[s];
+  if (i >= v.count) i = kEmpty;
+  hit[t] = i;
+  if (i != kEmpty) atomicMin(&first[i], (uint32_t)t);
+}
+
+// remove, second launch: removed[t] and, for the store, keep[i]
+__global__ __launch_bounds__(kST) void k_ss_remove_flags(const uint32_t* __restrict__ hit, uint64_t n,
+                                                          const uint32_t* __restrict__ first, uint64_t count,
+                                                          uint8_t* __restrict__ removed, uint32_t* __restrict__ keep) {
+  const uint64_t t = (uint64_t)blockIdx.x * kST + threadIdx.x;
+  if (t < n) removed[t] = hit[t] < count && first[hit[t]] == (uint32_t)t;
+  if (t < count) keep[t] = first[t] == kEmpty;
 }
 
 uint64_t slots_for(uint64_t keys) {
@@ -361,6 +389,90 @@ int add_common(sg_sigset* s, const uint8_t* keys, const uint8_t* bytes, const ui
 }
 
 }  // namespace
+
+// ---- what sg_hub_state.hip takes from this file (sg_internal.h) ----
+int sigset_new(sg_ctx* ctx, uint64_t hint, sg_sigset** out) {
+  sg_sigset* s = new sg_sigset();
+  s->ctx = ctx;
+  const int rc = grow_for(s, std::max<uint64_t>(hint, 1));
+  if (rc) {
+    set_free(s);
+    return rc;
+  }
+  *out = s;
+  return SG_OK;
+}
+
+void sigset_delete(sg_sigset* s) {
+  if (s) set_free(s);
+}
+
+size_t sigset_add_ws(uint64_t n) { return AddPlan(0, n).total; }
+
+int sigset_add_dev(sg_sigset* s, const uint32_t* d_keys, uint64_t n, uint8_t* d_is_new, size_t ws_base, size_t* o_pos) {
+  sg_ctx* ctx = s->ctx;
+  const AddPlan ap(ws_base, n);
+  *o_pos = ap.o_pos;
+  int rc = room_ok("sigset_add_dev", s, n);
+  if (rc) return rc;
+  if ((rc = grow_for(s, n))) return rc;
+  if ((rc = add_scratch(ctx, s->store, s->store_cap, s->table, s->nslots, s->count, d_keys, n, ap, d_is_new))) return rc;
+  uint64_t added = 0;
+  SG_HIP(hipMemcpyAsync(&added, (uint64_t*)ws_at(ctx, ap.o_pos) + n, 8, hipMemcpyDeviceToHost, ctx->stream));
+  SG_HIP(hipStreamSynchronize(ctx->stream));
+  s->count += std::min<uint64_t>(added, n);
+  return SG_OK;
+}
+
+int sigset_lookup_dev(sg_sigset* s, const uint32_t* d_keys, uint64_t n, uint32_t want, uint32_t* out32) {
+  if (!n) return SG_OK;
+  sg_ctx* ctx = s->ctx;
+  const View v{s->store, (uint32_t)s->count, nullptr, nullptr, 0, s->table, (uint32_t)(s->nslots - 1)};
+  ScopedTimer tm(ctx, "sigset_lookup");
+  hipLaunchKernelGGL(k_ss_lookup, dim3(div_up(n, kST)), dim3(kST), 0, ctx->stream, v, d_keys, n, (const uint32_t*)nullptr,
+                     want, (uint8_t*)nullptr, out32);
+  SG_HIP(hipGetLastError());
+  return SG_OK;
+}
+
+int sigset_lookup_or_dev(sg_sigset* s, const uint32_t* d_keys, uint64_t n, uint32_t* acc) {
+  if (!n) return SG_OK;
+  sg_ctx* ctx = s->ctx;
+  const View v{s->store, (uint32_t)s->count, nullptr, nullptr, 0, s->table, (uint32_t)(s->nslots - 1)};
+  ScopedTimer tm(ctx, "sigset_lookup");
+  hipLaunchKernelGGL(k_ss_lookup_or, dim3(div_up(n, kST)), dim3(kST), 0, ctx->stream, v, d_keys, n, acc);
+  SG_HIP(hipGetLastError());
+  return SG_OK;
+}
+
+int sigset_gather_dev(sg_ctx* ctx, const uint32_t* d_keys, uint64_t n, const uint32_t* d_flag, const uint64_t* d_pos,
+                      uint32_t* d_out, uint64_t cap) {
+  if (!n) return SG_OK;
+  ScopedTimer tm(ctx, "sigset_gather");
+  hipLaunchKernelGGL(k_ss_gather, dim3(div_up(n, kST)), dim3(kST), 0, ctx->stream, d_keys, n, d_flag, d_pos, d_out, cap);
+  SG_HIP(hipGetLastError());
+  return SG_OK;
+}
+
+int sigset_rebuild_dev(sg_sigset* s, const uint32_t* d_keep, const uint64_t* d_pos, uint64_t newcount) {
+  sg_ctx* ctx = s->ctx;
+  const uint64_t c = s->count;
+  if (newcount > c) newcount = c;
+  int rc = store_reserve(ctx, &s->store2, &s->store2_cap, std::max<uint64_t>(newcount, 1), 0);
+  if (rc) return rc;
+  if ((rc = table_fresh(ctx, &s->table2, &s->nslots2, slots_for(newcount)))) return rc;
+  if ((rc = sigset_gather_dev(ctx, s->store, c, d_keep, d_pos, s->store2, newcount))) return rc;
+  const View v{s->store2, (uint32_t)newcount, nullptr, nullptr, 0, s->table2, (uint32_t)(s->nslots2 - 1)};
+  if ((rc = launch_insert(ctx, v, 0, (uint32_t)newcount))) return rc;
+  SG_HIP(hipStreamSynchronize(ctx->stream));
+  std::swap(s->store, s->store2);
+  std::swap(s->store_cap, s->store2_cap);
+  std::swap(s->table, s->table2);
+  std::swap(s->nslots, s->nslots2);
+  s->count = newcount;
+  return SG_OK;
+}
+
 }  // namespace sg
 
 using namespace sg;
@@ -582,6 +694,48 @@ int sg_hub_sync(sg_sigset* hub, const uint8_t* bytes, const uint64_t* off, size_
   std::swap(hub->nslots, hub->nslots2);
   hub->count = std::min(got[0], n);
   return SG_OK;
+}
+
+int sg_sigset_remove(sg_sigset* s, const uint8_t* sigs, size_t n, uint8_t* removed) {
+  int rc = sigs_ok("sg_sigset_remove", s, sigs, n, removed);
+  if (rc) return rc;
+  sg_ctx* ctx = s->ctx;
+  std::lock_guard<std::mutex> g(ctx->mu);
+  rc = ensure_device(ctx);
+  if (rc) return rc;
+  if (n == 0) return SG_OK;
+  const uint64_t c = s->count;
+  WsPlan plan;
+  const size_t o_keys = plan.add(n * SG_SIG_BYTES), o_rem = plan.add(n);
+  if ((rc = dstage_reserve(ctx, plan))) return rc;
+  WsPlan wp;
+  const size_t o_hit = wp.add(n * 4), o_first = wp.add(c * 4 + 4), o_keep = wp.add(c * 4 + 4), o_pos = wp.add((c + 1) * 8),
+               o_scan = wp.add(scan_ws_bytes(c));
+  if ((rc = ws_reserve(ctx, wp))) return rc;
+  uint32_t* dkeys = dstage_at<uint32_t>(ctx, o_keys);
+  uint8_t* drem = dstage_at<uint8_t>(ctx, o_rem);
+  uint32_t* hit = (uint32_t*)ws_at(ctx, o_hit);
+  uint32_t* first = (uint32_t*)ws_at(ctx, o_first);
+  uint32_t* keep = (uint32_t*)ws_at(ctx, o_keep);
+  uint64_t* pos = (uint64_t*)ws_at(ctx, o_pos);
+  if ((rc = upload(ctx, dkeys, sigs, n * SG_SIG_BYTES))) return rc;
+  SG_HIP(hipMemsetAsync(first, 0xFF, c * 4 + 4, ctx->stream));
+  const View v{s->store, (uint32_t)c, nullptr, nullptr, 0, s->table, (uint32_t)(s->nslots - 1)};
+  {
+    ScopedTimer tm(ctx, "sigset_remove");
+    hipLaunchKernelGGL(k_ss_remove_mark, dim3(div_up(n, kST)), dim3(kST), 0, ctx->stream, v, (const uint32_t*)dkeys,
+                       (uint64_t)n, hit, first);
+    hipLaunchKernelGGL(k_ss_remove_flags, dim3(div_up(std::max<uint64_t>(n, c), kST)), dim3(kST), 0, ctx->stream,
+                       (const uint32_t*)hit, (uint64_t)n, (const uint32_t*)first, c, drem, keep);
+  }
+  SG_HIP(hipGetLastError());
+  if ((rc = scan_counts(ctx, keep, pos, c, o_scan))) return rc;
+  uint64_t left = 0;
+  SG_HIP(hipMemcpyAsync(removed, drem, n, hipMemcpyDeviceToHost, ctx->stream));
+  SG_HIP(hipMemcpyAsync(&left, pos + c, 8, hipMemcpyDeviceToHost, ctx->stream));
+  SG_HIP(hipStreamSynchronize(ctx->stream));
+  if (left >= c) return SG_OK;  // nothing was in the set
+  return sigset_rebuild_dev(s, keep, pos, left);
 }
 
 }  // extern "C"

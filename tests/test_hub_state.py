@@ -1,0 +1,805 @@
+"""The hub's corpus (prog/encoding.go:559-592; syz-hub/state/state.go:83-110, :175-195, :265-308, :310-336,
+:338-354): sg_call_sets*, sg_nametab_*, sg_sigset_remove, sg_hubcorpus_*.  On the CPU the boundary, every
+rejected argument, the no-device result, the oracle against the reference's table and the pinned scanner rules,
+and the conditions the cases rely on.  On the GPU every status, span, id, key, seq and count exactly as the
+oracle's (tests/hub_state_oracle.py: pure Python over dicts); no tolerance anywhere."""
+import os
+import re
+import subprocess
+
+import numpy as np
+import pytest
+
+from tests import hub_state_cases as K
+from tests import hub_state_oracle as OR
+from tests import prog_hashes_cases as PK
+from tests.conftest import ROOT
+
+U8, U32, U64 = np.uint8, np.uint32, np.uint64
+NAMES = ("sg_nametab_create", "sg_nametab_destroy", "sg_nametab_count", "sg_nametab_add", "sg_call_sets",
+         "sg_call_sets_dev", "sg_sigset_remove", "sg_hubcorpus_create", "sg_hubcorpus_destroy", "sg_hubcorpus_count",
+         "sg_hubcorpus_export", "sg_hubcorpus_add", "sg_hubcorpus_pending", "sg_hubcorpus_purge")
+FILL = 0xA5
+UNK = 0xFFFFFFFF
+
+
+def _has_gpu():
+    try:
+        import torch
+
+        return torch.cuda.device_count() > 0
+    except Exception:
+        return False
+
+
+# ---- CPU: the boundary ---------------------------------------------------------
+def test_header_binding_and_library():
+    import syzkaller_amd
+    from syzkaller_amd import _lib
+    from syzkaller_amd import hub as H
+    from syzkaller_amd.corpus import SigSet
+
+    text = open(os.path.join(ROOT, "include", "syzsig.h")).read()
+    for cite in ("encoding.go:559-592", "state.go:175-195", "state.go:265-308", "310-336", "state.go:338-354", "83-110",
+                 "state.go:181-183", ":286-300", "encoding.go:\n * 382"):
+        assert cite in text, cite
+    assert "parity unpinned at this edge" in text and "no tombstones" in text
+    assert "number\n * of '(' bytes in the batch always suffices" in text
+    assert "no cached SG_NAME_UNKNOWN can go stale" in text
+    assert re.search(r"#define SG_CALLSET_MAX_LINE %d\b" % K.MAX_LINE, text)
+    assert "#define SG_FNV64_OFFSET 0x%xull" % OR.FNV_OFFSET in text and "#define SG_FNV64_PRIME 0x%xull" % OR.FNV_PRIME in text
+    assert "#define SG_NAME_UNKNOWN 0xffffffffu" in text
+    src = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
+    out = subprocess.run(["nm", "-D", "--defined-only", _lib.LIB_PATH], capture_output=True, text=True, check=True).stdout
+    exported = set(re.findall(r" T (sg_[a-z0-9_]+)$", out, flags=re.M))
+    for name in NAMES:
+        assert re.search(r"\b(int|void) %s\s*\(" % name, src), name
+        assert name in _lib.SIGNATURES and name in exported, name
+    for name in ("NameTable", "call_sets", "CallSet", "HubCorpus", "HubState"):
+        assert callable(getattr(H, name)) and getattr(syzkaller_amd, name) is getattr(H, name)
+    for m in ("add", "id", "name", "__len__", "mask"):
+        assert callable(getattr(H.NameTable, m)), m
+    for m in ("Connect", "Sync", "addInputs", "purgeCorpus", "pendingInputs"):
+        assert callable(getattr(H.HubState, m)), m
+    assert callable(SigSet.remove)
+    assert H.CALLSET_MAX_LINE == K.MAX_LINE == OR.MAX_LINE and H.CALLSET_ERRORS == OR.ERRORS and H.NAME_UNKNOWN == UNK
+    for f in ("sg_call_set.hip", "sg_hub_state.hip"):
+        unit = open(os.path.join(ROOT, "syzkaller_amd", "csrc", f)).read()
+        assert "getenv" not in unit, f
+
+
+def _fake(count=0, ctx=0):
+    """A readable block that passes for a set, a corpus or a name table up to the checks: its context pointer
+    and, second field, a count."""
+    block = np.zeros(1 << 12, U64)
+    block[0], block[1] = ctx, count
+    return block
+
+
+def test_invalid_arguments_are_einval():
+    """Every check made before the context is touched: handles that are only readable blocks are enough."""
+    from syzkaller_amd import _lib
+    from syzkaller_amd.cover import _p8, _p32, _p64
+
+    lib, E, ref = _lib.lib, _lib.SG_EINVAL, _lib.ctypes.byref
+    vp = _lib.c_void_p
+    blk = _fake()
+    fake = blk.ctypes.data_as(vp)
+    other_ctx = np.zeros(1 << 13, U64)
+    foreign_blk = _fake(ctx=other_ctx.ctypes.data)  # a handle whose context is not the null one `fake` names
+    foreign = foreign_blk.ctypes.data_as(vp)
+    data = np.frombuffer(b"a()\nb()\nc()\n", U8).copy()
+    off = np.array([0, 4, 4, 12], U64)
+    bad0, dec = off.copy(), off.copy()
+    bad0[0], dec[2] = 1, 3
+    st, lo = np.full(3, FILL, U8), np.full(4, FILL, U64)
+    pos, ln, ids = np.full(8, FILL, U64), np.full(8, FILL, U32), np.full(8, FILL, U32)
+    nl = _lib.c_size_t(77)
+    out = vp()
+    # the dictionary
+    assert lib.sg_nametab_create(None, ref(out)) == E and lib.sg_nametab_create(fake, None) == E
+    assert lib.sg_nametab_count(None, _p64(lo)) == E and lib.sg_nametab_count(fake, None) == E
+    assert lib.sg_nametab_add(None, _p8(data), _p64(off), 3, _p32(ids)) == E
+    assert lib.sg_nametab_add(fake, _p8(data), _p64(off), 3, None) == E
+    assert lib.sg_nametab_add(fake, _p8(data), None, 3, _p32(ids)) == E
+    assert lib.sg_nametab_add(fake, None, _p64(off), 3, _p32(ids)) == E
+    assert lib.sg_nametab_add(fake, _p8(data), _p64(bad0), 3, _p32(ids)) == E
+    assert lib.sg_nametab_add(fake, _p8(data), _p64(dec), 3, _p32(ids)) == E
+    assert lib.sg_nametab_add(fake, _p8(data), _p64(off), 3, _p32(ids)) == E          # name 1 is empty
+    assert b"empty" in lib.sg_last_error()
+    lib.sg_nametab_destroy(None)
+    # the scan
+    args = (_p8(data), _p64(off), 3, _p8(st), _p64(lo), _p64(pos), _p32(ln), _p32(ids), 8, ref(nl))
+    assert lib.sg_call_sets(None, None, *args) == E
+    assert lib.sg_call_sets(fake, foreign, *args) == E and b"another context" in lib.sg_last_error()
+    assert lib.sg_call_sets(fake, None, None, *args[1:]) == E
+    assert lib.sg_call_sets(fake, None, args[0], None, *args[2:]) == E
+    assert lib.sg_call_sets(fake, None, args[0], _p64(bad0), *args[2:]) == E
+    assert lib.sg_call_sets(fake, None, args[0], _p64(dec), *args[2:]) == E
+    assert lib.sg_call_sets(fake, None, *args[:3], None, *args[4:]) == E                # status
+    assert lib.sg_call_sets(fake, None, *args[:4], None, *args[5:]) == E                # line_off
+    assert lib.sg_call_sets(fake, None, *args[:5], None, *args[6:]) == E                # name_pos with cap > 0
+    assert lib.sg_call_sets(fake, None, *args[:6], None, *args[7:]) == E                # name_len with cap > 0
+    assert lib.sg_call_sets(fake, None, *args[:9], None) == E                           # nlines
+    dev = (fake, fake, 3, 12, fake, fake, fake, fake, fake, 8)
+    assert lib.sg_call_sets_dev(None, None, *dev) == E
+    assert lib.sg_call_sets_dev(fake, foreign, *dev) == E
+    assert lib.sg_call_sets_dev(fake, None, None, *dev[1:]) == E
+    assert lib.sg_call_sets_dev(fake, None, fake, None, *dev[2:]) == E
+    assert lib.sg_call_sets_dev(fake, None, *dev[:4], None, *dev[5:]) == E              # d_status
+    assert lib.sg_call_sets_dev(fake, None, *dev[:5], None, *dev[6:]) == E              # d_line_off
+    assert lib.sg_call_sets_dev(fake, None, *dev[:6], None, *dev[7:]) == E              # d_name_pos with cap > 0
+    assert lib.sg_call_sets_dev(fake, None, fake, fake, 1 << 32, *dev[3:]) == E
+    assert lib.sg_call_sets_dev(fake, None, fake, fake, 3, 1 << 33, *dev[4:]) == E
+    # remove
+    sigs, flags = np.full(60, FILL, U8), np.full(3, FILL, U8)
+    assert lib.sg_sigset_remove(None, _p8(sigs), 3, _p8(flags)) == E
+    assert lib.sg_sigset_remove(fake, None, 3, _p8(flags)) == E
+    assert lib.sg_sigset_remove(fake, _p8(sigs), 3, None) == E
+    assert lib.sg_sigset_remove(fake, _p8(sigs), 1 << 31, _p8(flags)) == E
+    # the corpus
+    assert lib.sg_hubcorpus_create(None, fake, ref(out)) == E and lib.sg_hubcorpus_create(fake, None, ref(out)) == E
+    assert lib.sg_hubcorpus_create(fake, fake, None) == E
+    assert lib.sg_hubcorpus_create(fake, foreign, ref(out)) == E and not out.value
+    assert lib.sg_hubcorpus_count(None, _p64(lo)) == E and lib.sg_hubcorpus_count(fake, None) == E
+    nr, ni = _lib.c_size_t(77), _lib.c_size_t(77)
+    ex = (_p8(sigs), _p64(pos), _p64(lo), _p32(ids), 3, 8, ref(nr), ref(ni))
+    assert lib.sg_hubcorpus_export(None, *ex) == E
+    assert lib.sg_hubcorpus_export(fake, None, *ex[1:]) == E and lib.sg_hubcorpus_export(fake, ex[0], None, *ex[2:]) == E
+    assert lib.sg_hubcorpus_export(fake, *ex[:2], None, *ex[3:]) == E and lib.sg_hubcorpus_export(fake, *ex[:3], None, *ex[4:]) == E
+    assert lib.sg_hubcorpus_export(fake, *ex[:6], None, ex[7]) == E and lib.sg_hubcorpus_export(fake, *ex[:7], None) == E
+    seqs = np.array([1, 2, 3], U64)
+    isn = np.full(3, FILL, U8)
+    add = (_p8(data), _p64(off), 3, _p64(seqs), _p8(st), _p8(isn), _p8(sigs), _p64(pos), _p32(ln), 8, ref(nl))
+    assert lib.sg_hubcorpus_add(None, None, *add) == E
+    assert lib.sg_hubcorpus_add(fake, foreign, *add) == E and b"another context" in lib.sg_last_error()
+    assert lib.sg_hubcorpus_add(fake, None, None, *add[1:]) == E
+    assert lib.sg_hubcorpus_add(fake, None, add[0], None, *add[2:]) == E
+    assert lib.sg_hubcorpus_add(fake, None, add[0], _p64(bad0), *add[2:]) == E
+    assert lib.sg_hubcorpus_add(fake, None, add[0], _p64(dec), *add[2:]) == E
+    for k in (3, 4, 5, 7, 8, 10):  # seqs, status, is_new, unk_pos, unk_len, nunk
+        assert lib.sg_hubcorpus_add(fake, None, *add[:k], None, *add[k + 1:]) == E, k
+    big = seqs.copy()
+    big[1] = 1 << 33
+    assert lib.sg_hubcorpus_add(fake, None, *add[:3], _p64(big), *add[4:]) == E and b"seq" in lib.sg_last_error()
+    full = _fake((1 << 31) - 2).ctypes.data_as(vp)
+    assert lib.sg_hubcorpus_add(full, None, *add) == E and b"2^31" in lib.sg_last_error()   # the corpus
+    assert lib.sg_hubcorpus_add(fake, full, *add) == E                                      # the manager's set
+    ms, mo = _lib.c_uint64(77), _lib.c_uint64(77)
+    mask = np.ones(1, U64)
+    pe = (1, 2, _p64(mask), 1, 5, _p8(sigs), _p64(pos), 3, ref(nl), ref(ms), ref(mo))
+    assert lib.sg_hubcorpus_pending(None, fake, *pe) == E and lib.sg_hubcorpus_pending(fake, None, *pe) == E
+    assert lib.sg_hubcorpus_pending(fake, foreign, *pe) == E
+    for k in (2, 5, 6, 8, 9, 10):  # mask with nwords > 0, sigs, seqs with cap > 0, n, max_seq, more
+        assert lib.sg_hubcorpus_pending(fake, fake, *pe[:k], None, *pe[k + 1:]) == E, k
+    handles = (vp * 2)(blk.ctypes.data, foreign_blk.ctypes.data)
+    nulls = (vp * 2)(blk.ctypes.data, None)
+    good = (vp * 2)(blk.ctypes.data, blk.ctypes.data)
+    dels = np.full(100, FILL, U8)
+    assert lib.sg_hubcorpus_purge(None, good, 2, _p8(dels), 5, ref(nl)) == E
+    assert lib.sg_hubcorpus_purge(fake, None, 2, _p8(dels), 5, ref(nl)) == E
+    assert lib.sg_hubcorpus_purge(fake, handles, 2, _p8(dels), 5, ref(nl)) == E
+    assert lib.sg_hubcorpus_purge(fake, nulls, 2, _p8(dels), 5, ref(nl)) == E
+    assert lib.sg_hubcorpus_purge(fake, good, 2, None, 5, ref(nl)) == E
+    assert lib.sg_hubcorpus_purge(fake, good, 2, _p8(dels), 5, None) == E
+    held = _fake(6).ctypes.data_as(vp)
+    assert lib.sg_hubcorpus_purge(held, good, 2, _p8(dels), 5, ref(nl)) == E and b"del_cap" in lib.sg_last_error()
+    lib.sg_hubcorpus_destroy(None)
+    for a in (st, lo, pos, ln, ids, sigs, flags, isn, dels):
+        assert (a == FILL).all()
+    assert nl.value == 77 and nr.value == 77 and ni.value == 77 and ms.value == 77 and mo.value == 77
+
+
+@pytest.mark.skipif(_has_gpu(), reason="checks the no-GPU failure path")
+def test_no_device_is_enodev():
+    """Valid arguments and no device: the first thing each call asks of the context fails."""
+    from syzkaller_amd import _lib
+    from syzkaller_amd.cover import _p8, _p32, _p64
+
+    lib, N, ref, vp = _lib.lib, _lib.SG_ENODEV, _lib.ctypes.byref, _lib.c_void_p
+    cblock = np.zeros(1 << 16, U8)  # a zeroed sg_ctx: device 0, an unlocked mutex
+    fctx = cblock.ctypes.data_as(vp)
+    hblock = _fake(ctx=cblock.ctypes.data)  # a set, a table or a corpus of that context
+    fh = hblock.ctypes.data_as(vp)
+    data, off = np.frombuffer(b"a()\nb()\n", U8).copy(), np.array([0, 4, 8], U64)
+    st, lo = np.zeros(2, U8), np.zeros(3, U64)
+    pos, ln, ids, sigs = np.zeros(4, U64), np.zeros(4, U32), np.zeros(4, U32), np.zeros(40, U8)
+    nl, out = _lib.c_size_t(), vp()
+    assert lib.sg_nametab_create(fctx, ref(out)) == N and not out.value
+    assert lib.sg_call_sets(fctx, None, _p8(data), _p64(off), 2, _p8(st), _p64(lo), _p64(pos), _p32(ln), _p32(ids), 4,
+                            ref(nl)) == N
+    assert lib.sg_call_sets_dev(fctx, None, fctx, fctx, 2, 8, fctx, fctx, fctx, fctx, fctx, 4) == N
+    assert lib.sg_sigset_remove(fh, _p8(sigs), 2, _p8(st)) == N
+    assert lib.sg_hubcorpus_create(fctx, fh, ref(out)) == N and not out.value
+    seqs, ms, mo = np.ones(2, U64), _lib.c_uint64(), _lib.c_uint64()
+    assert lib.sg_hubcorpus_add(fh, None, _p8(data), _p64(off), 2, _p64(seqs), _p8(st), _p8(st), None, _p64(pos), _p32(ln),
+                                4, ref(nl)) == N
+    assert lib.sg_hubcorpus_pending(fh, fh, 0, 1, None, 0, 5, _p8(sigs), _p64(pos), 2, ref(nl), ref(ms), ref(mo)) == N
+    assert lib.sg_hubcorpus_purge(fh, None, 0, _p8(sigs), 2, ref(nl)) == N
+
+
+# ---- CPU: the oracle and the cases ---------------------------------------------
+def test_oracle_reference_table_and_edges():
+    for text, ok, names in K.kats():
+        if ok:
+            assert OR.CallSet(text) == set(names)
+        else:
+            with pytest.raises(ValueError):
+                OR.CallSet(text)
+    assert [ok for _, ok, _ in K.kats()] == [False, False, True, True, True]
+    with pytest.raises(ValueError, match="does not contain any calls"):
+        OR.CallSet(b"")
+    with pytest.raises(ValueError, match="call name is empty"):
+        OR.CallSet(b"r0 =  (foo)")
+    for text, status, names in K.EDGES:
+        st, lines = OR.call_lines(text)
+        assert st == status and [text[p:p + n] for p, n in lines] == names, text
+    assert {st for _, st, _ in K.EDGES} == {0, 1, 2, 4}
+
+
+def test_oracle_long_line_rule():
+    body = b"a(" + b"x" * (K.MAX_LINE - 3)
+    assert len(body) == K.MAX_LINE - 1
+    for tail in (b"", b"\n"):
+        assert OR.call_lines(body + tail)[0] == 0                      # 262,143 bytes of content
+        assert OR.call_lines(body + b"x" + tail)[0] == 3               # 262,144
+        assert OR.call_lines(b"b()\n" + body + tail)[0] == 0
+        assert OR.call_lines(b"b()\n" + body + b"x" + tail)[0] == 3
+    with pytest.raises(ValueError, match="token too long"):
+        OR.CallSet(body + b"x")
+    for text, status in K.long_cases():
+        assert OR.call_lines(text)[0] == status
+    assert [s for _, s in K.long_cases()].count(3) >= 4
+
+
+def test_case_conditions():
+    progs, marks = K.offset_batch()
+    starts = np.concatenate([[0], np.cumsum([len(p) for p in progs])])
+    assert sorted({(a, o) for _, a, o, _ in marks}) == [(a, o) for a in range(4) for o in K.OFFSETS]
+    seen = {c: set() for c in b"=(\n"}
+    for i, a, o, name in marks:
+        line = b"r%d = " % (o % 10) + name + b"("
+        assert starts[i] % 4 == a and progs[i][o:o + len(line)] == line and (o == 0 or progs[i][o - 1] == 10)
+        assert OR.call_lines(progs[i]) == (0, [(o + 5, len(name)), (o + len(line) + 5, 1)])
+        for c in b"=(\n":
+            seen[c].add((int(starts[i]) + progs[i].index(bytes([c]), o)) % K.STEP)
+    assert all(v == set(range(K.STEP)) for v in seen.values())  # each class at every place of a 64-byte step
+    assert max(K.OFFSETS) + 20 > 2 * K.STEP
+    for n in K.BATCH_SIZES:
+        ps = K.mixed(n, n)
+        assert len(ps) == n
+        if n >= 63:
+            st = OR.call_sets(ps)[0]
+            assert any(ps[k:k + 3] == [b"", b"", b""] for k in range(n)) and {0, 4} <= set(st.tolist())
+    big, at = K.big_among_short()
+    assert len(big[at]) >= 1 << 20 and len(big) == 201 and max(len(p) for p in big[:at] + big[at + 1:]) < 2000
+    assert OR.call_lines(big[at])[0] == 0 and len(big[at]) > 4000 * K.TILE
+    # the dictionary's cases
+    a, b = K.colliding_pair()
+    assert a != b and OR.fnv1a(a) != OR.fnv1a(b)
+    for bits in range(6, K.TABLE_MASK_BITS + 1):
+        assert K.low_bits(a, bits) == K.low_bits(b, bits)
+    names = K.many_names()
+    assert len(set(names)) == 5000 and {len(x) for x in names} == set(range(1, 201))
+    assert 2 * 5000 <= 1 << 14 <= 1 << K.TABLE_MASK_BITS  # the largest table these tests build: 2^14 slots
+    sharers = K.slot_sharers(names[:200], 50)
+    assert len(set(sharers)) == 50 and not set(sharers) & set(names)
+    assert all(any(K.low_bits(s) == K.low_bits(p) for p in names[:200]) for s in sharers)
+    assert K.NAMES[1].startswith(K.NAMES[0]) and K.NAMES[2].startswith(K.NAMES[0])  # prefixes of one another
+    assert len(set(K.POOL)) == len(K.POOL) == 400 and all(OR.call_lines(p)[0] == 0 for p in K.POOL)
+    # pending's cut: more than max_records selected, and a seq tie across index max_records
+    steps, maxrec = K.pending_steps()
+    c = OR.OHubCorpus(OR.ONameTable())
+    for seq, ps in steps:
+        assert c.add(ps, seq)[1].all()
+    mask = c.table.mask([b"read", b"write"])
+    keys, seqs, max_seq, more = c.pending(OR.OSet(), 0, 3, mask, maxrec)
+    assert len(c.recs) == 10 > maxrec and seqs == [1, 1, 1, 2, 2, 2, 2] and (max_seq, more) == (2, 3)
+    assert seqs[maxrec - 1] == seqs[maxrec] == seqs[maxrec + 1]
+
+
+def test_oracle_state_mirrors_the_go_lines():
+    s = OR.OHubState()
+    s.Connect("a", True, [b"read", b"write"], [b"read(0x1)", b"write(0x2)", b"broken"])
+    s.Connect("b", True, [b"read"], [b"read(0x3)"])
+    assert len(s.Corpus.recs) == 3 and s.corpusSeq == 2
+    progs, more = s.Sync("b", [], [])
+    assert progs == [b"read(0x1)"] and more == 0 and s.Managers["b"].New == 2 and s.Managers["b"].corpusSeq == 2
+    progs, more = s.Sync("a", [b"read(0x9)"], [OR.Hash(b"write(0x2)").hex()])
+    assert progs == [b"read(0x3)"] and len(s.Corpus.recs) == 3 and OR.Hash(b"write(0x2)") not in s.texts
+    with pytest.raises(ValueError):
+        s.Sync("nobody", [], [])
+
+
+# ---- GPU: CallSet ---------------------------------------------------------------
+def _check_sets(ctx, progs, table=None, otable=None):
+    from syzkaller_amd import hub as H
+
+    st, lo, pos, ln, ids = H.call_sets(progs, table=table, ctx=ctx)
+    est, elo, epos, eln, names = OR.call_sets(progs)
+    assert np.array_equal(st, est) and np.array_equal(lo, elo)
+    assert np.array_equal(pos, epos) and np.array_equal(ln, eln)
+    eids = [UNK if otable is None else otable.get(x, UNK) for x in names]
+    assert ids.tolist() == eids
+    return st, lo, pos, ln, ids
+
+
+@pytest.mark.gpu
+def test_callset_reference_table_and_rules(ctx):
+    from syzkaller_amd import hub as H
+
+    for text, ok, names in K.kats():
+        if ok:
+            assert H.CallSet(text, ctx=ctx) == set(names)
+        else:
+            with pytest.raises(ValueError):
+                H.CallSet(text, ctx=ctx)
+    for status, msg in OR.ERRORS.items():
+        text = {1: b"x", 2: b"r0 = (", 3: b"a(" + b"x" * K.MAX_LINE, 4: b"#"}[status]
+        with pytest.raises(ValueError, match=re.escape(msg)):
+            H.CallSet(text, ctx=ctx)
+    progs = [t for t, _, _ in K.EDGES]
+    st, lo, pos, ln, _ = _check_sets(ctx, progs)
+    view = b"".join(progs)
+    for k, (text, status, names) in enumerate(K.EDGES):
+        assert st[k] == status, text
+        assert [view[p:p + n] for p, n in zip(pos[lo[k]:lo[k + 1]].tolist(), ln[lo[k]:lo[k + 1]].tolist())] == names
+    for text, _, _ in K.EDGES:  # and each alone
+        _check_sets(ctx, [text])
+
+
+@pytest.mark.gpu
+def test_callset_every_offset_and_misalignment(ctx):
+    progs, marks = K.offset_batch()
+    st, lo, pos, ln, _ = _check_sets(ctx, progs)
+    view = b"".join(progs)
+    for i, a, o, name in marks:
+        assert st[i] == 0 and lo[i + 1] - lo[i] == 2, (a, o)
+        p, n = int(pos[lo[i]]), int(ln[lo[i]])
+        assert view[p:p + n] == name, (a, o)
+
+
+@pytest.mark.gpu
+def test_callset_long_lines(ctx):
+    cases = K.long_cases()
+    st = _check_sets(ctx, [t for t, _ in cases])[0]
+    assert st.tolist() == [s for _, s in cases]
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("nprogs", K.BATCH_SIZES)
+def test_callset_batch_sizes(ctx, nprogs):
+    _check_sets(ctx, K.mixed(nprogs, nprogs))
+
+
+@pytest.mark.gpu
+def test_callset_big_program_among_short_ones(ctx):
+    progs, at = K.big_among_short()
+    st, lo = _check_sets(ctx, progs)[:2]
+    assert st[at] == 0 and lo[at + 1] - lo[at] > 40000
+
+
+@pytest.mark.gpu
+def test_callset_cap_one_too_small_and_null_table(ctx):
+    from syzkaller_amd import _lib
+    from syzkaller_amd.corpus import texts_csr
+    from syzkaller_amd.cover import _p8, _p32, _p64
+
+    progs = K.mixed(300, 3)
+    b, off = texts_csr(progs)
+    n = len(progs)
+    est, elo, epos, eln, _ = OR.call_sets(progs)
+    total = int(elo[-1])
+    for cap in (total - 1, total):
+        st, lo = np.full(n + 8, FILL, U8), np.full(n + 9, FILL, U64)
+        pos, ln, ids = np.full(total + 8, FILL, U64), np.full(total + 8, FILL, U32), np.full(total + 8, FILL, U32)
+        nl = _lib.c_size_t(77)
+        _lib.call("sg_call_sets", ctx.h, None, _p8(b), _p64(off), n, _p8(st), _p64(lo), _p64(pos), _p32(ln), _p32(ids), cap,
+                  _lib.ctypes.byref(nl))
+        assert nl.value == total and np.array_equal(st[:n], est) and np.array_equal(lo[:n + 1], elo)
+        assert (st[n:] == FILL).all() and (lo[n + 1:] == FILL).all()
+        w = total if cap >= total else 0
+        assert np.array_equal(pos[:w], epos[:w]) and np.array_equal(ln[:w], eln[:w]) and (ids[:w] == UNK).all()
+        assert (pos[w:] == FILL).all() and (ln[w:] == FILL).all() and (ids[w:] == FILL).all()
+    # name_id NULL, and nprogs == 0
+    pos, ln = np.zeros(total, U64), np.zeros(total, U32)
+    st, lo = np.zeros(n, U8), np.zeros(n + 1, U64)
+    _lib.call("sg_call_sets", ctx.h, None, _p8(b), _p64(off), n, _p8(st), _p64(lo), _p64(pos), _p32(ln), None, total,
+              _lib.ctypes.byref(nl))
+    assert np.array_equal(pos, epos) and np.array_equal(ln, eln)
+    lo[0] = 5
+    _lib.call("sg_call_sets", ctx.h, None, None, _p64(np.zeros(1, U64)), 0, None, _p64(lo), None, None, None, 0,
+              _lib.ctypes.byref(nl))
+    assert nl.value == 0 and lo[0] == 0
+
+
+def _to_dev(a):
+    import torch
+
+    return torch.from_numpy(np.ascontiguousarray(a).view(np.uint8).copy()).to("cuda")
+
+
+@pytest.mark.gpu
+def test_callset_device_form_clamps_garbage_offsets(ctx):
+    import torch
+
+    from syzkaller_amd import hub as H
+    from syzkaller_amd._lib import call
+    from syzkaller_amd.corpus import texts_csr
+
+    table = H.NameTable(ctx)
+    table.add(K.NAMES[:5])
+    otab = {x: i for i, x in enumerate(K.NAMES[:5])}
+
+    def run(tab, d_bytes_ptr, nbytes, offs, count, cap):
+        """The five outputs, each with 16 guard bytes behind it that must stay as they were."""
+        sizes = (count, 8 * (count + 1), 8 * cap, 4 * cap, 4 * cap)
+        bufs = [torch.full((m + 16,), FILL, dtype=torch.uint8, device="cuda") for m in sizes]
+        torch.cuda.synchronize()
+        call("sg_call_sets_dev", ctx.h, tab.h if tab else None, d_bytes_ptr, _to_dev(offs).data_ptr(), count, nbytes,
+             *[t.data_ptr() for t in bufs], cap)
+        ctx.sync()
+        outs = [t.cpu().numpy() for t in bufs]
+        for o, m in zip(outs, sizes):
+            assert (o[m:] == FILL).all()
+        lo = outs[1][:sizes[1]].view(U64)
+        nl = int(lo[-1])
+        written = nl if nl <= cap else 0
+        for o, w in zip(outs[2:], (8, 4, 4)):
+            assert (o[w * written:] == FILL).all()
+        return (outs[0][:count].tolist(), lo.tolist(), outs[2][:8 * written].view(U64).tolist(),
+                outs[3][:4 * written].view(U32).tolist(), outs[4][:4 * written].view(U32).tolist())
+
+    def expect(view, ranges, tab=otab):
+        st, lo, pos, ln, ids = [], [0], [], [], []
+        for a0, a1 in ranges:
+            s, lines = OR.call_lines(view[a0:a1])
+            st.append(s)
+            for p, m in lines:
+                pos.append(a0 + p)
+                ln.append(m)
+                ids.append(tab.get(view[a0 + p:a0 + p + m], UNK))
+            lo.append(len(pos))
+        return st, lo, pos, ln, ids
+
+    progs = K.mixed(130, 31)
+    b, off = texts_csr(progs)
+    n, nbytes = len(progs), int(off[-1])
+    d_b = _to_dev(b)
+    good = expect(bytes(b), [(int(off[k]), int(off[k + 1])) for k in range(n)])
+    total = good[1][-1]
+    for shift in (0, 1, 3):  # the byte buffer at a misaligned device address too
+        d_bs = torch.empty(nbytes + 8, dtype=torch.uint8, device="cuda")
+        d_bs[shift:shift + nbytes] = d_b
+        assert run(table, d_bs.data_ptr() + shift, nbytes, off, n, total + 3) == good, shift
+    # a cap one too small: the statuses and the offsets only; and no table
+    got = run(table, d_b.data_ptr(), nbytes, off, n, total - 1)
+    assert got[:2] == good[:2] and got[2:] == ([], [], [])
+    assert run(None, d_b.data_ptr(), nbytes, off, n, total) == good[:4] + ([UNK] * total,)
+    # offsets past nbytes, an end below its start, a start inside a line: clamped to [start, nbytes].  The
+    # programs overlap, so the batch has more call lines than '(' bytes and more tiles than bytes / 256
+    valid = K.POOL[:130]
+    b2, off2 = texts_csr(valid)
+    nb2 = int(off2[-1])
+    d_b2 = _to_dev(b2)
+    bad = np.array([0, off2[3], off2[1], nb2 + 1000, 1 << 63, off2[2], nb2 - 1, off2[1] + 2, off2[4]], U64)
+    ranges = []
+    for k in range(bad.size - 1):
+        a0 = min(int(bad[k]), nb2)
+        ranges.append((a0, min(max(int(bad[k + 1]), a0), nb2)))
+    assert ranges[1] == (int(off2[3]),) * 2 and ranges[2] == (int(off2[1]), nb2) and ranges[3] == ranges[4] == (nb2, nb2)
+    assert ranges[5] == (int(off2[2]), nb2 - 1)
+    exp = expect(bytes(b2), ranges)
+    assert exp[0][:6] == [0, 4, 0, 4, 4, 0] and exp[1][-1] > int(np.count_nonzero(b2 == 0x28))
+    assert sum((a1 - a0 + 255) // 256 for a0, a1 in ranges) > nb2 // 256 + 1 + len(ranges)  # the tiles are widened
+    assert run(table, d_b2.data_ptr(), nb2, bad, len(ranges), exp[1][-1]) == exp
+    # and later calls still give right answers
+    _check_sets(ctx, progs, table, otab)
+    table.close()
+
+
+# ---- GPU: the dictionary ----------------------------------------------------------
+@pytest.mark.gpu
+def test_dictionary_ids_prefixes_collisions_and_absent_names(ctx):
+    from syzkaller_amd import hub as H
+
+    t = H.NameTable(ctx)
+    assert len(t) == 0
+    first = [b"open", b"openat", b"open$x", b"o", b"open"]
+    assert t.add(first).tolist() == [0, 1, 2, 3, 0] and len(t) == 4
+    a, b = K.colliding_pair()
+    assert t.add([a, b, a]).tolist() == [4, 5, 4]
+    names = K.many_names()
+    ids = t.add(names[:2500])
+    assert ids.tolist() == list(range(6, 2506))
+    assert t.add(first).tolist() == [0, 1, 2, 3, 0]                      # ids are stable across adds and growth
+    assert t.add(names).tolist() == list(range(6, 5006)) and len(t) == 5006
+    assert t.id(b"openat") == 1 and t.id(b"opena") is None and t.name(5) == b and t.id(names[77]) == 83
+    with pytest.raises(Exception):
+        t.add([b"new name", b""])
+    assert len(t) == 5006 and t.id(b"new name") is None                         # nothing added
+    otab = {x: i for i, x in enumerate([b"open", b"openat", b"open$x", b"o", a, b] + names)}
+    sharers = K.slot_sharers(names[:200], 50)
+    look = first + [a, b, b"opena", b"ope", b"open$", b"open$xy"] + names[::7] + sharers + [names[0] + b"\x01"]
+    progs = [x + b"(0x0)\nr1 = " + y + b"()\n" for x, y in zip(look, look[::-1])]
+    st, lo, pos, ln, ids = _check_sets(ctx, progs, t, otab)
+    assert (st == 0).all() and (ids == UNK).sum() == 2 * (4 + 50 + 1)
+    m = t.mask([b"open", names[0], b"nothing"])
+    assert m.size == (5006 + 63) // 64 and int(m[0]) == 1 | 1 << 6 and not m[1:].any()
+    t.close()
+
+
+# ---- GPU: sg_sigset_remove ----------------------------------------------------------
+def _same_set(s, o):
+    assert s.count() == len(o.m) and np.array_equal(s.export(), o.export())
+
+
+@pytest.mark.gpu
+def test_sigset_remove(ctx):
+    from syzkaller_amd.corpus import SigSet
+
+    s, o = SigSet(ctx=ctx), OR.OSet()
+    have, absent = PK.random_sigs(500, 61), PK.random_sigs(100, 62)
+    for x in have:
+        o.m[x.tobytes()] = True
+    assert s.add_new(have).all()
+    assert s.remove(np.zeros((0, 20), U8)).size == 0
+    batch = np.concatenate([have[10:20], absent[:5], have[10:15], have[400:401], absent[:2], have[499:500]])
+    exp = o.remove(batch)
+    assert exp.sum() == 12 and np.array_equal(s.remove(batch), exp)
+    _same_set(s, o)
+    assert not s.contains(have[10:20]).any() and s.contains(have[20:400]).all()
+    assert not s.remove(absent).any()                                    # absent keys only: nothing changes
+    _same_set(s, o)
+    exp = []
+    for x in batch:                                                      # add after remove
+        exp.append(bytes(x) not in o.m)
+        o.m[bytes(x)] = True
+    assert s.add_new(batch).tolist() == exp
+    _same_set(s, o)
+    everything = s.export()[::-1].copy()
+    assert s.remove(everything).all() and o.remove(everything).all()     # removing all
+    _same_set(s, o)
+    assert s.count() == 0 and not s.contains(have).any()
+    # 300 identities with one home slot, every second one removed: the survivors' chain is rebuilt
+    chain = PK.one_home(300, 5)
+    assert s.add_new(chain).all()
+    for x in chain:
+        o.m[x.tobytes()] = True
+    assert s.remove(chain[::2]).all() and o.remove(chain[::2]).all()
+    _same_set(s, o)
+    assert s.contains(chain).tolist() == [k % 2 == 1 for k in range(300)]
+    assert s.add_new(chain[:4]).tolist() == [True, False, True, False]
+    s.close()
+
+
+# ---- GPU: the corpus ----------------------------------------------------------------
+def _same_corpus(c, o):
+    for g, e in zip(c.export(), o.export()):
+        assert np.array_equal(g, e)
+    assert c.count() == len(o.recs)
+
+
+@pytest.mark.gpu
+def test_hubcorpus_add(ctx):
+    from syzkaller_amd import hub as H
+    from syzkaller_amd.corpus import SigSet, texts_csr
+
+    t = H.NameTable(ctx)
+    c, o = H.HubCorpus(t), OR.OHubCorpus(OR.ONameTable())
+    mgr, omgr = SigSet(ctx=ctx), OR.OSet()
+    _same_corpus(c, o)
+    # an unknown name: nothing changes, the spans are exact; after interning the same call succeeds
+    t.add([b"read"])
+    o.table.add([b"read"])
+    batch = [b"read(0x1)\nwrite(0x2)\n", b"broken", b"r0 = mmap(0x0)\nread(0x3)\nwrite(0x4)", b"brk(\nno bracket"]
+    b, off = texts_csr(batch)
+    st, new, sigs, (upos, ulen), nunk = c.add_raw(b, off, 7, mgr)
+    espans = o.unknown(batch)
+    assert nunk == 3 == len(espans) and list(zip(upos.tolist(), ulen.tolist())) == espans
+    assert st.tolist() == [0, 1, 0, 1] and not new.any() and c.count() == 0 and mgr.count() == 0 and len(t) == 1
+    st, new, sigs, (upos, ulen), nunk = c.add_raw(b, off, 7, mgr, unk_cap=2)  # fewer slots than spans
+    assert nunk == 3 and list(zip(upos.tolist(), ulen.tolist())) == espans[:2] and c.count() == 0
+    st, new, sigs = c.add(batch, 7, mgr)
+    est, enew, ekeys = o.add(batch, 7, omgr)
+    assert np.array_equal(st, est) and np.array_equal(new, enew) and np.array_equal(sigs, ekeys)
+    assert new.tolist() == [True, False, True, False] and [t.name(i) for i in range(len(t))] == [b"read", b"write", b"mmap"]
+    _same_corpus(c, o)
+    _same_set(mgr, omgr)
+    # repeats inside a batch and against the store; bad programs skipped; with and without mgr
+    rng = np.random.default_rng(8)
+    for step in range(6):
+        pick = rng.integers(0, 120, size=40 + 10 * step)
+        batch = [K.POOL[i] for i in pick] + [b"", b"x", batch[0]]
+        m, om = (mgr, omgr) if step % 2 == 0 else (None, None)
+        st, new, sigs = c.add(batch, 10 + step, m)
+        est, enew, ekeys = o.add(batch, 10 + step, om)
+        assert np.array_equal(st, est) and np.array_equal(new, enew) and np.array_equal(sigs, ekeys), step
+        _same_corpus(c, o)
+        _same_set(mgr, omgr)
+    assert len(t) == len(o.table.ids) and all(t.id(x) == i for x, i in o.table.ids.items())
+    # per-program seqs; one at the limit is rejected and nothing changes
+    batch = K.POOL[200:230]
+    seqs = np.arange(100, 130, dtype=U64)[::-1].copy()
+    st, new, _ = c.add(batch, seqs)
+    o.add(batch, seqs.tolist())
+    _same_corpus(c, o)
+    seqs[3] = H.SEQ_LIMIT
+    with pytest.raises(Exception):
+        c.add(K.POOL[300:330], seqs)
+    _same_corpus(c, o)
+    assert c.add([], 1)[0].size == 0
+    for x in (c, mgr, t):
+        x.close()
+
+
+def _filled(ctx, steps):
+    from syzkaller_amd import hub as H
+
+    t = H.NameTable(ctx)
+    c, o = H.HubCorpus(t), OR.OHubCorpus(OR.ONameTable())
+    for seq, ps in steps:
+        c.add(ps, seq)
+        o.add(ps, seq)
+    _same_corpus(c, o)
+    return t, c, o
+
+
+def _pending(c, o, mgr, omgr, mgr_seq, hub_seq, names, maxrec, nwords=None):
+    mask, emask = c.table.mask(names), o.table.mask(names)
+    assert np.array_equal(mask, emask)
+    if nwords is not None:
+        mask = emask = mask[:nwords]
+    sigs, seqs, max_seq, more = c.pending(mgr, mgr_seq, hub_seq, mask, maxrec)
+    ekeys, eseqs, emax, emore = o.pending(omgr, mgr_seq, hub_seq, emask, maxrec)
+    assert [s.tobytes() for s in sigs] == ekeys and seqs.tolist() == eseqs and (max_seq, more) == (emax, emore)
+    return ekeys, eseqs, emax, emore
+
+
+@pytest.mark.gpu
+def test_hubcorpus_pending(ctx):
+    from syzkaller_amd.corpus import SigSet
+
+    steps, maxrec = K.pending_steps()
+    t, c, o = _filled(ctx, steps)
+    mgr, omgr = SigSet(ctx=ctx), OR.OSet()
+    both = [b"read", b"write"]
+    assert _pending(c, o, mgr, omgr, 3, 3, both, 1000) == ([], [], 3, 0)              # a caught-up manager
+    assert len(_pending(c, o, mgr, omgr, 0, 3, both, 1000)[0]) == 10                  # everything
+    assert _pending(c, o, mgr, omgr, 1, 3, both, 1000)[1] == [2] * 4 + [3] * 3        # the seq filter alone
+    assert _pending(c, o, mgr, omgr, 0, 3, [b"read"], 1000)[1] == [1] * 3 + [2] * 4   # the mask alone
+    held = [OR.Hash(p) for p in steps[1][1][1:3]]
+    mgr.add_new(held)
+    for h in held:
+        omgr.m[h] = True
+    assert _pending(c, o, mgr, omgr, 0, 3, both, 1000)[1] == [1] * 3 + [2] * 2 + [3] * 3   # the manager's set alone
+    mgr.remove(held)
+    omgr.remove(held)
+    assert _pending(c, o, mgr, omgr, 0, 3, both, 1000, nwords=0)[0] == []             # an id beyond the mask
+    # the cut: exactly max_records selected, one more, and the tie across index max_records
+    assert _pending(c, o, mgr, omgr, 0, 3, both, 10)[2:] == (3, 0)
+    assert _pending(c, o, mgr, omgr, 0, 3, both, 9)[2:] == (3, 0)                     # index 9 is the last: all kept
+    assert _pending(c, o, mgr, omgr, 0, 3, both, 7)[2:] == (3, 0)
+    assert _pending(c, o, mgr, omgr, 0, 3, both, 6)[1:] == ([1] * 3 + [2] * 4, 2, 3)
+    assert _pending(c, o, mgr, omgr, 0, 3, both, maxrec)[1:] == ([1] * 3 + [2] * 4, 2, 3)
+    assert _pending(c, o, mgr, omgr, 0, 3, both, 2)[1:] == ([1] * 3, 1, 7)
+    assert _pending(c, o, mgr, omgr, 0, 3, both, 0)[1:] == ([1] * 3, 1, 7)
+    # seqs out of record order: the output is by (seq, record index)
+    c.add(K.one_name_progs(3, b"read", b"late"), 2)
+    o.add(K.one_name_progs(3, b"read", b"late"), 2)
+    got = _pending(c, o, mgr, omgr, 0, 3, both, 1000)
+    assert got[1] == [1] * 3 + [2] * 7 + [3] * 3
+    # more ids than one mask word, and a larger corpus against a manager holding half of it
+    names = [b"n%d" % k for k in range(200)]
+    progs = [b"\n".join(names[(7 * k + j) % 200] + b"(0x%x)" % k for j in range(1 + k % 5)) for k in range(3000)]
+    for seq in range(4, 10):
+        c.add(progs[(seq - 4) * 500:(seq - 3) * 500], seq)
+        o.add(progs[(seq - 4) * 500:(seq - 3) * 500], seq)
+    _same_corpus(c, o)
+    half = [OR.Hash(p) for p in progs[::2]]
+    mgr.add_new(half)
+    for h in half:
+        omgr.m[h] = True
+    sup = both + names[:150]
+    assert t.mask(sup).size == 4
+    for maxrec_ in (1000, 100, 499, 500, 5000):
+        for seq0 in (0, 5):
+            got = _pending(c, o, mgr, omgr, seq0, 9, sup, maxrec_)
+            assert len(got[0]) > 0
+    assert _pending(c, o, mgr, omgr, 0, 9, sup, 1000, nwords=2)[3] >= 0
+    _same_corpus(c, o)  # reads only
+    for x in (c, mgr, t):
+        x.close()
+
+
+@pytest.mark.gpu
+def test_hubcorpus_purge(ctx):
+    from syzkaller_amd import _lib
+    from syzkaller_amd.corpus import SigSet
+    from syzkaller_amd.cover import _p8
+
+    steps = [(s + 1, K.POOL[60 * s:60 * s + 60]) for s in range(5)]
+    t, c, o = _filled(ctx, steps)
+    keys = [OR.Hash(p) for p in K.POOL[:300]]
+    sets, osets = [SigSet(ctx=ctx) for _ in range(3)], [OR.OSet() for _ in range(3)]
+    for k, (s, os_) in enumerate(zip(sets, osets)):
+        mine = keys[k::5] + [OR.Hash(b"not in the corpus %d" % k)]
+        s.add_new(mine)
+        for h in mine:
+            os_.m[h] = True
+    # del_cap one too small: SG_EINVAL before any work
+    dels, nd = np.full(20 * 300, FILL, U8), _lib.c_size_t(77)
+    arr = (_lib.c_void_p * 3)(*[s.h.value for s in sets])
+    assert _lib.lib.sg_hubcorpus_purge(c.h, arr, 3, _p8(dels), 299, _lib.ctypes.byref(nd)) == _lib.SG_EINVAL
+    assert nd.value == 77 and (dels == FILL).all()
+    _same_corpus(c, o)
+    got, exp = c.purge(sets), o.purge(osets)
+    assert [g.tobytes() for g in got] == exp and len(exp) == 120
+    _same_corpus(c, o)
+    assert len(c.purge(sets)) == 0 == len(o.purge(osets))               # nothing left to delete
+    _same_corpus(c, o)
+    # the corpus goes on: adds after a purge, a manager's deletions, another purge
+    for x in (c, o):
+        x.add(K.POOL[300:340] + K.POOL[:10], 9)
+    _same_corpus(c, o)
+    sets[0].remove(keys[0::5][:20])
+    osets[0].remove(keys[0::5][:20])
+    got, exp = c.purge(sets[:2]), o.purge(osets[:2])
+    assert [g.tobytes() for g in got] == exp and len(exp) > 60
+    _same_corpus(c, o)
+    got, exp = c.purge([]), o.purge([])                                  # no manager: everything goes
+    assert [g.tobytes() for g in got] == exp and c.count() == 0
+    _same_corpus(c, o)
+    assert c.purge([]).shape == (0, 20)
+    for x in (c, o):
+        x.add(K.POOL[:20], 11)
+    _same_corpus(c, o)
+    for x in sets + [c, t]:
+        x.close()
+
+
+@pytest.mark.gpu
+def test_hub_state_against_the_oracle(ctx):
+    from syzkaller_amd import hub as H
+
+    s, o = H.HubState(ctx), OR.OHubState()
+    rng = np.random.default_rng(17)
+    calls = {"a": K.NAMES, "b": K.NAMES[:4], "c": K.NAMES[3:], "d": [b"unknown$call"]}
+
+    def same():
+        _same_corpus(s.Corpus, o.Corpus)
+        assert s.corpusSeq == o.corpusSeq and s.texts == o.texts and list(s.Managers) == list(o.Managers)
+        for name, m in s.Managers.items():
+            om = o.Managers[name]
+            _same_set(m.Corpus, om.Corpus)
+            assert (m.corpusSeq, m.Added, m.Deleted, m.New) == (om.corpusSeq, om.Added, om.Deleted, om.New), name
+
+    for name, lo in (("a", 0), ("b", 80), ("c", 160)):
+        corpus = K.POOL[lo:lo + 120] + [b"broken", b""]
+        for x in (s, o):
+            x.Connect(name, True, calls[name], corpus)
+        same()
+    with pytest.raises(ValueError, match="unconnected manager nobody"):
+        s.Sync("nobody", [], [])
+    for x in (s, o):
+        x.Connect("d", True, calls["d"], [])
+    same()
+    held = {n: list(K.POOL[lo:lo + 120]) for n, lo in (("a", 0), ("b", 80), ("c", 160))}
+    held["d"] = []
+    for step in range(12):
+        name = "abcd"[step % 4]
+        add = [K.POOL[i] for i in rng.integers(0, 400, size=int(rng.integers(0, 30)))]
+        ndel = int(rng.integers(0, 10)) if step % 3 else 0
+        dels = [OR.Hash(held[name].pop()).hex() for _ in range(min(ndel, len(held[name])))]
+        got, exp = s.Sync(name, add, dels), o.Sync(name, add, dels)
+        assert got == exp, step
+        held[name] += add
+        same()
+    got, exp = s.pendingInputs("a", 3), o.pendingInputs("a", 3)
+    assert got == exp
+    for x in (s, o):
+        x.Connect("b", False, calls["a"], K.POOL[:5])                    # a reconnect: its corpus starts over
+    same()
+    assert s.Sync("b", [], []) == o.Sync("b", [], [])
+    same()
+    s.close()
