@@ -50,8 +50,7 @@ struct sg_nametab {
   std::vector<uint64_t> hash;
   std::vector<uint32_t> slots;
   // the device mirror, one allocation: [bytes | off | hash | slots], uploaded after every add
-  uint8_t* d_mirror = nullptr;
-  size_t d_cap = 0;
+  sg::DevBuf<uint8_t> d_mirror;  // (64 KiB, then doubling)
   size_t o_off = 0, o_hash = 0, o_slots = 0;
 };
 
@@ -394,11 +393,12 @@ CsArgs cs_args(sg_ctx* ctx, const CsPlan& pl, const uint8_t* d_bytes, const uint
 
 NtView nt_view(const sg_nametab* t) {
   NtView v{};
-  if (!t || !t->d_mirror || t->hash.empty()) return v;
-  v.bytes = t->d_mirror;
-  v.off = (const uint64_t*)(t->d_mirror + t->o_off);
-  v.hash = (const uint64_t*)(t->d_mirror + t->o_hash);
-  v.slots = (const uint32_t*)(t->d_mirror + t->o_slots);
+  if (!t || !t->d_mirror.p || t->hash.empty()) return v;
+  const uint8_t* m = t->d_mirror.p;
+  v.bytes = m;
+  v.off = (const uint64_t*)(m + t->o_off);
+  v.hash = (const uint64_t*)(m + t->o_hash);
+  v.slots = (const uint32_t*)(m + t->o_slots);
   v.mask = (uint32_t)t->slots.size() - 1;
   v.n = (uint32_t)t->hash.size();
   v.nbytes = t->bytes.size();
@@ -431,24 +431,18 @@ int nt_upload(sg_nametab* t) {
   const size_t nb = align256(t->bytes.size() + 1), no = align256(t->off.size() * 8), nh = align256(t->hash.size() * 8 + 8),
                ns = align256(t->slots.size() * 4 + 4);
   SG_HIP(hipStreamSynchronize(ctx->stream));  // (no lookup in flight reads the old mirror)
-  if (nb + no + nh + ns > t->d_cap) {
-    size_t cap = std::max<size_t>(t->d_cap * 2, 1 << 16);
-    while (cap < nb + no + nh + ns) cap *= 2;
-    if (t->d_mirror) SG_HIP(hipFree(t->d_mirror));
-    t->d_mirror = nullptr;
-    t->d_cap = 0;
-    SG_HIP(hipMalloc(&t->d_mirror, cap));
-    t->d_cap = cap;
-  }
+  const int rc = t->d_mirror.grow_drop(grow_cap(t->d_mirror.cap, nb + no + nh + ns, 1 << 16), ctx->stream);
+  if (rc) return rc;
+  uint8_t* m = t->d_mirror.p;
   t->o_off = nb;
   t->o_hash = nb + no;
   t->o_slots = nb + no + nh;
-  if (!t->bytes.empty()) SG_HIP(hipMemcpy(t->d_mirror, t->bytes.data(), t->bytes.size(), hipMemcpyHostToDevice));
-  SG_HIP(hipMemcpy(t->d_mirror + t->o_off, t->off.data(), t->off.size() * 8, hipMemcpyHostToDevice));
+  if (!t->bytes.empty()) SG_HIP(hipMemcpy(m, t->bytes.data(), t->bytes.size(), hipMemcpyHostToDevice));
+  SG_HIP(hipMemcpy(m + t->o_off, t->off.data(), t->off.size() * 8, hipMemcpyHostToDevice));
   if (!t->hash.empty())
-    SG_HIP(hipMemcpy(t->d_mirror + t->o_hash, t->hash.data(), t->hash.size() * 8, hipMemcpyHostToDevice));
+    SG_HIP(hipMemcpy(m + t->o_hash, t->hash.data(), t->hash.size() * 8, hipMemcpyHostToDevice));
   if (!t->slots.empty())
-    SG_HIP(hipMemcpy(t->d_mirror + t->o_slots, t->slots.data(), t->slots.size() * 4, hipMemcpyHostToDevice));
+    SG_HIP(hipMemcpy(m + t->o_slots, t->slots.data(), t->slots.size() * 4, hipMemcpyHostToDevice));
   return SG_OK;
 }
 
@@ -558,7 +552,6 @@ int sg_nametab_create(sg_ctx* ctx, sg_nametab** out) {
   t->ctx = ctx;
   t->slots.assign(64, kNoId);
   if ((rc = nt_upload(t))) {
-    if (t->d_mirror) hipFree(t->d_mirror);
     delete t;
     return rc;
   }
@@ -573,7 +566,6 @@ void sg_nametab_destroy(sg_nametab* t) {
     hipSetDevice(t->ctx->device);
     hipStreamSynchronize(t->ctx->stream);
   }
-  if (t->d_mirror) hipFree(t->d_mirror);
   delete t;
 }
 

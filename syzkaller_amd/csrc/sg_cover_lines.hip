@@ -628,9 +628,9 @@ int sg_cover_lines_set(sg_cover_table* t, sg_set* cov, uint32_t base, uint64_t* 
   if (rc) return rc;
   uint64_t total = 0;
   for (int pass = 0; pass < 2; pass++) {
-    rc = set_export_dev(cov, dstage_at<uint32_t>(ctx, 0), ctx->dstage_cap / 4, &total);
+    rc = set_export_dev(cov, dstage_at<uint32_t>(ctx, 0), ctx->dstage.cap / 4, &total);
     if (rc) return rc;
-    if (total * 4 <= ctx->dstage_cap) break;
+    if (total * 4 <= ctx->dstage.cap) break;
     rc = dstage_reserve(ctx, total * 4);
     if (rc) return rc;
   }

@@ -48,51 +48,19 @@ int ensure_device(sg_ctx* ctx) {
 }
 
 int ws_reserve(sg_ctx* ctx, size_t bytes) {
-  if (bytes <= ctx->ws_cap) return SG_OK;
-  size_t cap = ctx->ws_cap ? ctx->ws_cap : (64u << 20);
-  while (cap < bytes) cap *= 2;
-  if (ctx->ws) {
-    SG_HIP(hipStreamSynchronize(ctx->stream));
-    SG_HIP(hipFree(ctx->ws));
-    ctx->ws = nullptr;
-    ctx->ws_cap = 0;
-  }
-  SG_HIP(hipMalloc(&ctx->ws, cap));
-  ctx->ws_cap = cap;
-  return SG_OK;
+  return ctx->ws.grow_drop(grow_cap(ctx->ws.cap, bytes, 64u << 20), ctx->stream);
 }
 
+// (the staging buffers also wait for the host pipeline's DMAs on copy_stream)
 int pin_reserve(sg_ctx* ctx, size_t bytes) {
-  if (bytes <= ctx->pin_cap) return SG_OK;
-  size_t cap = ctx->pin_cap ? ctx->pin_cap : (16u << 20);
-  while (cap < bytes) cap *= 2;
-  if (ctx->pin) {
-    SG_HIP(hipStreamSynchronize(ctx->stream));
-    if (ctx->copy_stream) SG_HIP(hipStreamSynchronize(ctx->copy_stream));  // (the host pipeline's DMAs)
-    SG_HIP(hipHostFree(ctx->pin));
-    ctx->pin = nullptr;
-    ctx->pin_cap = 0;
-  }
-  SG_HIP(hipHostMalloc(&ctx->pin, cap, hipHostMallocDefault));
-  ctx->pin_cap = cap;
-  return SG_OK;
+  return ctx->pin.grow_drop(grow_cap(ctx->pin.cap, bytes, 16u << 20), ctx->stream, ctx->copy_stream);
 }
 
 int dstage_reserve(sg_ctx* ctx, size_t bytes) {
-  if (bytes <= ctx->dstage_cap) return SG_OK;
-  size_t cap = ctx->dstage_cap ? ctx->dstage_cap : (16u << 20);
-  while (cap < bytes) cap *= 2;
-  if (ctx->dstage) {
-    SG_HIP(hipStreamSynchronize(ctx->stream));
-    if (ctx->copy_stream) SG_HIP(hipStreamSynchronize(ctx->copy_stream));  // (the host pipeline's DMAs)
-    SG_HIP(hipFree(ctx->dstage));
-    ctx->dstage = nullptr;
-    ctx->dstage_cap = 0;
-  }
-  SG_HIP(hipMalloc(&ctx->dstage, cap));
-  ctx->dstage_cap = cap;
-  return SG_OK;
+  return ctx->dstage.grow_drop(grow_cap(ctx->dstage.cap, bytes, 16u << 20), ctx->stream, ctx->copy_stream);
 }
+
+int slice_off_reserve(sg_ctx* ctx, size_t n) { return ctx->slice_off.grow_drop(n, ctx->stream); }
 
 static int plan_ok(const WsPlan& plan) {
   if (!plan.overflow) return SG_OK;
@@ -298,7 +266,7 @@ static int scan_u64_inplace(sg_ctx* ctx, uint64_t* data, uint64_t n, char* scrat
 
 int scan_counts(sg_ctx* ctx, const uint32_t* d_in, uint64_t* d_out, uint64_t n, size_t ws_used) {
   ScopedTimer tm(ctx, "scan");
-  char* scratch = (char*)ctx->ws + ws_used;
+  char* scratch = ctx->ws.p + ws_used;
   uint64_t nt = n ? (n + kScanTile - 1) / kScanTile : 0;
   uint64_t* sums = (uint64_t*)scratch;
   uint64_t* bases = (uint64_t*)(scratch + ((nt * 8 + 255) & ~255ull));
@@ -572,17 +540,11 @@ void sg_ctx_destroy(sg_ctx* ctx) {
     hipEventDestroy(r.b);
   }
   for (auto ev : ctx->timer.pool) hipEventDestroy(ev);
-  if (ctx->ws) hipFree(ctx->ws);
-  for (auto& s : ctx->prefix)
-    if (s.ws) hipFree(s.ws);
-  if (ctx->pin) hipHostFree(ctx->pin);
-  if (ctx->dstage) hipFree(ctx->dstage);
   if (ctx->owner) hipFree(ctx->owner);
   if (ctx->m0f) hipFree(ctx->m0f);
   if (ctx->m0f_host) hipHostFree(ctx->m0f_host);
   if (ctx->m0f_ev) hipEventDestroy(ctx->m0f_ev);
   if (ctx->fs_ev) hipEventDestroy(ctx->fs_ev);
-  if (ctx->slice_off) hipFree(ctx->slice_off);
   if (ctx->slice_cuts) hipFree(ctx->slice_cuts);
   if (ctx->dscal) hipFree(ctx->dscal);
   if (ctx->own_big) hipFree(ctx->own_big);
@@ -596,7 +558,7 @@ void sg_ctx_destroy(sg_ctx* ctx) {
     hipStreamDestroy(ctx->copy_stream);
   }
   if (ctx->own_stream) hipStreamDestroy(ctx->own_stream);
-  delete ctx;
+  delete ctx;  // (the workspaces, the staging buffers and slice_off free themselves)
 }
 
 int sg_ctx_sync(sg_ctx* ctx) {
@@ -1088,7 +1050,7 @@ int sg_set_add(sg_set* set, const uint32_t* sig, size_t n) {
   if (rc) return rc;
   rc = ws_reserve(ctx, n * 4);
   if (rc) return rc;
-  uint32_t* d = (uint32_t*)ctx->ws;
+  uint32_t* d = (uint32_t*)ctx->ws.p;
   SG_HIP(hipMemcpyAsync(d, sig, n * 4, hipMemcpyHostToDevice, ctx->stream));
   {
     ScopedTimer tm(ctx, "set_add");
@@ -1110,7 +1072,7 @@ int sg_set_new(sg_set* set, const uint32_t* sig, size_t n, int* out) {
   if (rc) return rc;
   rc = ws_reserve(ctx, n * 4);
   if (rc) return rc;
-  uint32_t* d = (uint32_t*)ctx->ws;
+  uint32_t* d = (uint32_t*)ctx->ws.p;
   SG_HIP(hipMemcpyAsync(d, sig, n * 4, hipMemcpyHostToDevice, ctx->stream));
   SG_HIP(hipMemsetAsync(ctx->dscal, 0, 8, ctx->stream));
   hipLaunchKernelGGL(k_set_new, dim3(std::min<uint64_t>(div_up(n, 256), 8192)), dim3(256), 0, ctx->stream,

@@ -583,10 +583,10 @@ int exec_comps(sg_ctx* ctx, const uint64_t* d_recs, const uint64_t* d_call_off, 
     ctx->exec_comps_general = got[0];
     ng = got[1] <= nrecs ? got[1] : nrecs;
     if (ng) {
-      const void* ws_before = ctx->ws;
+      const void* ws_before = ctx->ws.p;
       rc = ws_reserve(ctx, need_a + ec_general_bytes(ng, ncalls));
       if (rc) return rc;
-      if (ctx->ws != ws_before) {  // the workspace moved: the first pass went with it
+      if (ctx->ws.p != ws_before) {  // the workspace moved: the first pass went with it
         rc = first_pass();
         if (rc) return rc;
       }

@@ -399,10 +399,10 @@ int exec_cover(sg_ctx* ctx, const uint64_t* d_pcs, const uint64_t* d_call_off, u
     ctx->exec_cover_general = got[0];
     ng = got[1] <= npcs ? got[1] : npcs;
     if (ng) {
-      const void* ws_before = ctx->ws;
+      const void* ws_before = ctx->ws.p;
       rc = ws_reserve(ctx, need_a + xc_general_bytes(ng, ncalls));
       if (rc) return rc;
-      if (ctx->ws != ws_before) {  // the workspace moved: the first pass went with it
+      if (ctx->ws.p != ws_before) {  // the workspace moved: the first pass went with it
         rc = first_pass();
         if (rc) return rc;
       }

@@ -631,10 +631,10 @@ int hints_replacers(sg_ctx* ctx, const uint64_t* d_pair_off, const uint64_t* d_p
                o_reps = p.add(wcap * 8);
   const size_t tail = p.total;
   const size_t scan_n = nc > nvals ? nc : nvals;
-  const void* ws_before = ctx->ws;
+  const void* ws_before = ctx->ws.p;
   rc = ws_reserve(ctx, tail + radix_sort_ws(nc) + scan_ws_bytes(scan_n) + need_a);
   if (rc) return rc;
-  if (ctx->ws != ws_before) {  // the workspace moved: the counts went with it
+  if (ctx->ws.p != ws_before) {  // the workspace moved: the counts went with it
     rc = count();
     if (rc) return rc;
   }

@@ -127,8 +127,8 @@ int host_pipeline(sg_ctx* ctx, uint32_t* mwords, uint32_t* nwords, const uint32_
   }
   ctx->host_copy_bytes = ctx->host_copy_ns = ctx->host_wait_ns = 0;
   ctx->host_threads = (uint64_t)threads;
-  char* pin = (char*)ctx->pin;
-  char* dst = (char*)ctx->dstage;
+  char* pin = ctx->pin.p;
+  char* dst = ctx->dstage.p;
   uint8_t* dflag = (uint8_t*)(dst + 2 * b_slot);
   hipEvent_t* ev_dma = ctx->pipe_ev;      // slot k's DMA done (pinned k free, device k filled)
   hipEvent_t* ev_tri = ctx->pipe_ev + 2;  // slot k's triage done (device k free)

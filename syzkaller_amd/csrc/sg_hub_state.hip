@@ -18,7 +18,10 @@
 //    and its ids against the mask; the selected (seq << 31 | index) keys are
 //    sorted (radix_sort_u64) and one thread finds the cut of :286-300.
 //  * purge: used[r] ORed over the managers' sets, then keys, seqs and ids are
-//    gathered into second buffers and a fresh table is built: nothing is ever
+//    gathered into the second halves (the key set's and the records': each
+//    buffer owns its block and capacity, DevBuf of sg_buf.h, and grows from 1024
+//    elements by doubling, rec_reserve), a fresh table is built and the halves
+//    are swapped: nothing is ever
 //    deleted from a table, so there are no tombstones and a probe never has to
 //    step over a dead slot; the price is a rebuild per deleting call.
 // Every index is checked against its buffer's capacity before it is used as
@@ -27,7 +30,6 @@
 
 #include <algorithm>
 #include <cstddef>
-#include <initializer_list>
 
 struct sg_hubcorpus {
   sg_ctx* ctx = nullptr;
@@ -35,22 +37,19 @@ struct sg_hubcorpus {
   sg_nametab* tab = nullptr;
   sg_sigset* keys = nullptr;
   uint64_t nids = 0;
-  uint64_t* seq = nullptr;
-  uint64_t seq_cap = 0;
-  uint64_t* call_off = nullptr;  // [count + 1]
-  uint64_t off_cap = 0;
-  uint32_t* ids = nullptr;
-  uint64_t ids_cap = 0;
-  // purge's second buffers, swapped in
-  uint64_t* seq2 = nullptr;
-  uint64_t seq2_cap = 0;
-  uint64_t* call_off2 = nullptr;
-  uint64_t off2_cap = 0;
-  uint32_t* ids2 = nullptr;
-  uint64_t ids2_cap = 0;
-  // add's call lines: name_pos, name_len, name_id
-  uint8_t* lines = nullptr;
-  uint64_t lines_cap = 0;  // bytes
+  // the records beside the keys; purge gathers the kept ones into `next`, then swaps the halves
+  struct Half {
+    sg::DevBuf<uint64_t> seq;
+    sg::DevBuf<uint64_t> call_off;  // [count + 1]
+    sg::DevBuf<uint32_t> ids;
+    void swap(Half& o) {
+      seq.swap(o.seq);
+      call_off.swap(o.call_off);
+      ids.swap(o.ids);
+    }
+  } cur, next;
+  // add's call lines: name_pos, name_len, name_id (bytes)
+  sg::DevBuf<uint8_t> lines;
 };
 static_assert(offsetof(sg_hubcorpus, count) == 8, "tests/test_hub_state.py plants a count in a readable block");
 
@@ -230,32 +229,8 @@ __global__ __launch_bounds__(kHT) void k_hs_purge_ids(const uint32_t* __restrict
   if (dst < ids2_cap && dst < idpos[r + 1]) ids2[dst] = ids[i];
 }
 
-// a device buffer of at least `need` elements, the first `keep` kept
-template <typename T>
-int buf_reserve(sg_ctx* ctx, T** p, uint64_t* cap, uint64_t need, uint64_t keep) {
-  if (need <= *cap) return SG_OK;
-  uint64_t nc = std::max<uint64_t>(*cap * 2, 1024);
-  while (nc < need) nc *= 2;
-  T* np = nullptr;
-  SG_HIP(hipMalloc(&np, nc * sizeof(T)));
-  hipError_t e = hipSuccess;
-  if (*p && keep) e = hipMemcpyAsync(np, *p, keep * sizeof(T), hipMemcpyDeviceToDevice, ctx->stream);
-  if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-  if (e != hipSuccess) {
-    hipFree(np);
-    return hip_fail(e, "buf_reserve");
-  }
-  if (*p) SG_HIP(hipFree(*p));
-  *p = np;
-  *cap = nc;
-  return SG_OK;
-}
-
 void hub_free(sg_hubcorpus* h) {
   sigset_delete(h->keys);
-  for (void* p : {(void*)h->seq, (void*)h->call_off, (void*)h->ids, (void*)h->seq2, (void*)h->call_off2, (void*)h->ids2,
-                  (void*)h->lines})
-    if (p) hipFree(p);
   delete h;
 }
 
@@ -288,11 +263,11 @@ int sg_hubcorpus_create(sg_ctx* ctx, sg_nametab* tab, sg_hubcorpus** out) {
   h->ctx = ctx;
   h->tab = tab;
   rc = sigset_new(ctx, 1, &h->keys);
-  if (!rc) rc = buf_reserve(ctx, &h->seq, &h->seq_cap, 1024, 0);
-  if (!rc) rc = buf_reserve(ctx, &h->call_off, &h->off_cap, 1025, 0);
-  if (!rc) rc = buf_reserve(ctx, &h->ids, &h->ids_cap, 1024, 0);
+  if (!rc) rc = rec_reserve(ctx, h->cur.seq, 1024, 0);
+  if (!rc) rc = rec_reserve(ctx, h->cur.call_off, 1025, 0);
+  if (!rc) rc = rec_reserve(ctx, h->cur.ids, 1024, 0);
   if (!rc) {
-    hipError_t e = hipMemsetAsync(h->call_off, 0, 8, ctx->stream);
+    hipError_t e = hipMemsetAsync(h->cur.call_off.p, 0, 8, ctx->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
     if (e != hipSuccess) rc = hip_fail(e, fn);
   }
@@ -339,11 +314,11 @@ int sg_hubcorpus_export(sg_hubcorpus* h, uint8_t* sigs, uint64_t* seqs, uint64_t
   *nids = h->nids;
   if (c > cap_recs || h->nids > cap_ids) return SG_OK;
   if (c) {
-    SG_HIP(hipMemcpyAsync(sigs, h->keys->store, c * SG_SIG_BYTES, hipMemcpyDeviceToHost, ctx->stream));
-    SG_HIP(hipMemcpyAsync(seqs, h->seq, c * 8, hipMemcpyDeviceToHost, ctx->stream));
+    SG_HIP(hipMemcpyAsync(sigs, h->keys->cur.keys(), c * SG_SIG_BYTES, hipMemcpyDeviceToHost, ctx->stream));
+    SG_HIP(hipMemcpyAsync(seqs, h->cur.seq.p, c * 8, hipMemcpyDeviceToHost, ctx->stream));
   }
-  SG_HIP(hipMemcpyAsync(call_off, h->call_off, (c + 1) * 8, hipMemcpyDeviceToHost, ctx->stream));
-  if (h->nids) SG_HIP(hipMemcpyAsync(call_ids, h->ids, h->nids * 4, hipMemcpyDeviceToHost, ctx->stream));
+  SG_HIP(hipMemcpyAsync(call_off, h->cur.call_off.p, (c + 1) * 8, hipMemcpyDeviceToHost, ctx->stream));
+  if (h->nids) SG_HIP(hipMemcpyAsync(call_ids, h->cur.ids.p, h->nids * 4, hipMemcpyDeviceToHost, ctx->stream));
   SG_HIP(hipStreamSynchronize(ctx->stream));
   return SG_OK;
 }
@@ -405,10 +380,10 @@ int sg_hubcorpus_add(sg_hubcorpus* h, sg_sigset* mgr, const uint8_t* bytes, cons
   SG_HIP(hipMemcpyAsync(status, dstatus, n, hipMemcpyDeviceToHost, ctx->stream));
   SG_HIP(hipStreamSynchronize(ctx->stream));
   const uint64_t lcap = std::max<uint64_t>(nl, 1);
-  if ((rc = buf_reserve(ctx, &h->lines, &h->lines_cap, align256(lcap * 8) + 2 * align256(lcap * 4), 0))) return rc;
-  uint64_t* lpos = (uint64_t*)h->lines;
-  uint32_t* llen = (uint32_t*)(h->lines + align256(lcap * 8));
-  uint32_t* lid = (uint32_t*)(h->lines + align256(lcap * 8) + align256(lcap * 4));
+  if ((rc = rec_reserve(ctx, h->lines, align256(lcap * 8) + 2 * align256(lcap * 4), 0))) return rc;
+  uint64_t* lpos = (uint64_t*)h->lines.p;
+  uint32_t* llen = (uint32_t*)(h->lines.p + align256(lcap * 8));
+  uint32_t* lid = (uint32_t*)(h->lines.p + align256(lcap * 8) + align256(lcap * 4));
   if (nl && (rc = call_sets_emit(ctx, h->tab, dbytes, doff, n, nbytes, dstatus, dline, lpos, llen, lid, nl, 0))) return rc;
   // (the scan's workspace is no longer needed: the plan below may move it)
   WsPlan wp;
@@ -477,18 +452,19 @@ int sg_hubcorpus_add(sg_hubcorpus* h, sg_sigset* mgr, const uint8_t* bytes, cons
     SG_HIP(hipMemcpyAsync(&addids, idpos + m, 8, hipMemcpyDeviceToHost, ctx->stream));
     SG_HIP(hipStreamSynchronize(ctx->stream));
     const uint64_t c = h->count;
-    if ((rc = buf_reserve(ctx, &h->seq, &h->seq_cap, c, old))) return rc;
-    if ((rc = buf_reserve(ctx, &h->call_off, &h->off_cap, c + 1, old + 1))) return rc;
-    if ((rc = buf_reserve(ctx, &h->ids, &h->ids_cap, h->nids + addids, h->nids))) return rc;
+    sg_hubcorpus::Half& cur = h->cur;
+    if ((rc = rec_reserve(ctx, cur.seq, c, old))) return rc;
+    if ((rc = rec_reserve(ctx, cur.call_off, c + 1, old + 1))) return rc;
+    if ((rc = rec_reserve(ctx, cur.ids, h->nids + addids, h->nids))) return rc;
     {
       ScopedTimer tm(ctx, "hub_add_append");
       hipLaunchKernelGGL(k_hs_append_recs, grid_of(n), dim3(kHT), 0, ctx->stream, (const uint32_t*)okflag,
                          (const uint64_t*)okpos, n, m, entered, newpos, (const uint64_t*)idpos, (const uint64_t*)dseqs, old,
-                         h->nids, h->seq, h->seq_cap, h->call_off, h->off_cap);
+                         h->nids, cur.seq.p, (uint64_t)cur.seq.cap, cur.call_off.p, (uint64_t)cur.call_off.cap);
       if (nl)
         hipLaunchKernelGGL(k_hs_append_ids, grid_of(nl), dim3(kHT), 0, ctx->stream, (const uint32_t*)okflag,
                            (const uint64_t*)okpos, n, m, entered, (const uint64_t*)idpos, (const uint64_t*)dline, nl,
-                           (const uint32_t*)lid, h->nids, h->ids, h->ids_cap);
+                           (const uint32_t*)lid, h->nids, cur.ids.p, (uint64_t)cur.ids.cap);
     }
     SG_HIP(hipGetLastError());
     h->nids += addids;
@@ -535,17 +511,17 @@ int sg_hubcorpus_pending(sg_hubcorpus* h, sg_sigset* mgr, uint64_t mgr_seq, uint
   uint64_t* kb = (uint64_t*)ws_at(ctx, o_kb);
   uint64_t* cut = (uint64_t*)ws_at(ctx, o_cut);
   if ((rc = upload(ctx, dmask, mask, nwords * 8))) return rc;
-  if ((rc = sigset_lookup_dev(mgr, h->keys->store, c, 0u, sel))) return rc;
+  if ((rc = sigset_lookup_dev(mgr, h->keys->cur.keys(), c, 0u, sel))) return rc;
   {
     ScopedTimer tm(ctx, "hub_pending_select");
-    hipLaunchKernelGGL(k_hs_pending_sel, grid_of(c), dim3(kHT), 0, ctx->stream, sel, c, (const uint64_t*)h->seq, mgr_seq,
-                       (const uint64_t*)h->call_off, (const uint32_t*)h->ids, h->nids, (const uint64_t*)dmask,
-                       (uint64_t)nwords);
+    hipLaunchKernelGGL(k_hs_pending_sel, grid_of(c), dim3(kHT), 0, ctx->stream, sel, c, (const uint64_t*)h->cur.seq.p,
+                       mgr_seq, (const uint64_t*)h->cur.call_off.p, (const uint32_t*)h->cur.ids.p, h->nids,
+                       (const uint64_t*)dmask, (uint64_t)nwords);
   }
   SG_HIP(hipGetLastError());
   if ((rc = scan_counts(ctx, sel, pos, c, o_scan))) return rc;
   hipLaunchKernelGGL(k_hs_pending_keys, grid_of(c), dim3(kHT), 0, ctx->stream, (const uint32_t*)sel, (const uint64_t*)pos, c,
-                     (const uint64_t*)h->seq, ka);
+                     (const uint64_t*)h->cur.seq.p, ka);
   SG_HIP(hipGetLastError());
   uint64_t nsel = 0;
   SG_HIP(hipMemcpyAsync(&nsel, pos + c, 8, hipMemcpyDeviceToHost, ctx->stream));
@@ -574,7 +550,7 @@ int sg_hubcorpus_pending(sg_hubcorpus* h, sg_sigset* mgr, uint64_t mgr_seq, uint
   {
     ScopedTimer tm(ctx, "hub_pending_out");
     hipLaunchKernelGGL(k_hs_pending_out, grid_of(keep), dim3(kHT), 0, ctx->stream, (const uint64_t*)sorted, keep,
-                       (const uint32_t*)h->keys->store, c, dsigs, dseqs);
+                       (const uint32_t*)h->keys->cur.keys(), c, dsigs, dseqs);
   }
   SG_HIP(hipGetLastError());
   SG_HIP(hipMemcpyAsync(sigs, dsigs, keep * SG_SIG_BYTES, hipMemcpyDeviceToHost, ctx->stream));
@@ -624,11 +600,11 @@ int sg_hubcorpus_purge(sg_hubcorpus* h, sg_sigset* const* mgrs, size_t nmgrs, ui
   uint64_t* idpos = (uint64_t*)ws_at(ctx, o_idpos);
   SG_HIP(hipMemsetAsync(used, 0, c * 4 + 4, ctx->stream));
   for (size_t i = 0; i < nmgrs; i++)
-    if ((rc = sigset_lookup_or_dev(mgrs[i], h->keys->store, c, used))) return rc;
+    if ((rc = sigset_lookup_or_dev(mgrs[i], h->keys->cur.keys(), c, used))) return rc;
   {
     ScopedTimer tm(ctx, "hub_purge_flags");
     hipLaunchKernelGGL(k_hs_purge_flags, grid_of(c), dim3(kHT), 0, ctx->stream, (const uint32_t*)used, c,
-                       (const uint64_t*)h->call_off, dead, newcnt);
+                       (const uint64_t*)h->cur.call_off.p, dead, newcnt);
   }
   SG_HIP(hipGetLastError());
   if ((rc = scan_counts(ctx, used, keeppos, c, o_scan))) return rc;
@@ -641,29 +617,25 @@ int sg_hubcorpus_purge(sg_hubcorpus* h, sg_sigset* const* mgrs, size_t nmgrs, ui
   SG_HIP(hipStreamSynchronize(ctx->stream));
   const uint64_t newc = std::min(got[0], c), nd = std::min(got[1], c), newids = std::min(got[2], h->nids);
   if (nd == 0) return SG_OK;
-  if ((rc = sigset_gather_dev(ctx, h->keys->store, c, dead, deadpos, ddel, c))) return rc;
+  if ((rc = sigset_gather_dev(ctx, h->keys->cur.keys(), c, dead, deadpos, ddel, c))) return rc;
   SG_HIP(hipMemcpyAsync(del_sigs, ddel, nd * SG_SIG_BYTES, hipMemcpyDeviceToHost, ctx->stream));
-  if ((rc = buf_reserve(ctx, &h->seq2, &h->seq2_cap, std::max<uint64_t>(newc, 1), 0))) return rc;
-  if ((rc = buf_reserve(ctx, &h->call_off2, &h->off2_cap, newc + 1, 0))) return rc;
-  if ((rc = buf_reserve(ctx, &h->ids2, &h->ids2_cap, std::max<uint64_t>(newids, 1), 0))) return rc;
+  sg_hubcorpus::Half &cur = h->cur, &nx = h->next;
+  if ((rc = rec_reserve(ctx, nx.seq, std::max<uint64_t>(newc, 1), 0))) return rc;
+  if ((rc = rec_reserve(ctx, nx.call_off, newc + 1, 0))) return rc;
+  if ((rc = rec_reserve(ctx, nx.ids, std::max<uint64_t>(newids, 1), 0))) return rc;
   {
     ScopedTimer tm(ctx, "hub_purge_gather");
     hipLaunchKernelGGL(k_hs_purge_recs, grid_of(c), dim3(kHT), 0, ctx->stream, (const uint32_t*)used,
-                       (const uint64_t*)keeppos, (const uint64_t*)idpos, c, (const uint64_t*)h->seq, h->seq2, h->seq2_cap,
-                       h->call_off2, h->off2_cap);
+                       (const uint64_t*)keeppos, (const uint64_t*)idpos, c, (const uint64_t*)cur.seq.p, nx.seq.p,
+                       (uint64_t)nx.seq.cap, nx.call_off.p, (uint64_t)nx.call_off.cap);
     if (h->nids)
       hipLaunchKernelGGL(k_hs_purge_ids, grid_of(h->nids), dim3(kHT), 0, ctx->stream, (const uint32_t*)used,
-                         (const uint64_t*)idpos, c, (const uint64_t*)h->call_off, (const uint32_t*)h->ids, h->nids, h->ids2,
-                         h->ids2_cap);
+                         (const uint64_t*)idpos, c, (const uint64_t*)cur.call_off.p, (const uint32_t*)cur.ids.p, h->nids,
+                         nx.ids.p, (uint64_t)nx.ids.cap);
   }
   SG_HIP(hipGetLastError());
   if ((rc = sigset_rebuild_dev(h->keys, used, keeppos, newc))) return rc;  // (waits)
-  std::swap(h->seq, h->seq2);
-  std::swap(h->seq_cap, h->seq2_cap);
-  std::swap(h->call_off, h->call_off2);
-  std::swap(h->off_cap, h->off2_cap);
-  std::swap(h->ids, h->ids2);
-  std::swap(h->ids_cap, h->ids2_cap);
+  cur.swap(nx);
   h->count = h->keys->count;
   h->nids = newids;
   *ndel = nd;

@@ -12,6 +12,7 @@
 #include <vector>
 
 #include "../../include/syzsig.h"
+#include "sg_buf.h"
 #include "sg_plan.h"
 
 namespace sg {
@@ -72,8 +73,7 @@ struct PrefixSlot {
   uint32_t* marks = nullptr;   // begin's marks (end's set updates)
   bool keep = false;           // partitions kept instead of pairs
   bool open = false;
-  void* ws = nullptr;
-  size_t ws_cap = 0;
+  sg::DevBuf<char> ws;  // swapped with the context's during the slot's calls (sg_prefix.hip SlotWs)
 };
 constexpr uint32_t kPrefixSlots = 2;
 
@@ -149,14 +149,12 @@ struct sg_ctx {
   uint64_t canon_stats[4] = {0, 0, 0, 0};
   hipStream_t own_stream = nullptr;
   hipStream_t stream = nullptr;
-  // grow-only device workspace and pinned host staging
-  void* ws = nullptr;
-  size_t ws_cap = 0;
-  void* pin = nullptr;
-  size_t pin_cap = 0;
-  // grow-only device staging for the host entry points' inputs / outputs
-  void* dstage = nullptr;
-  size_t dstage_cap = 0;
+  // grow-only device workspace and pinned host staging (capacities in bytes;
+  // grown by ws_reserve / pin_reserve, contents dropped)
+  sg::DevBuf<char> ws;
+  sg::PinBuf pin;
+  // grow-only device staging for the host entry points' inputs / outputs (dstage_reserve)
+  sg::DevBuf<char> dstage;
   // the host ingest pipeline (sg_host.hip): its copy stream and the events
   // between the two staging slots' DMA and triage
   hipStream_t copy_stream = nullptr;
@@ -173,9 +171,8 @@ struct sg_ctx {
   // two-phase triage state (prefix_begin / prefix_end, sg_prefix.hip)
   PrefixSlot prefix[kPrefixSlots];
   bool debug_part = false;
-  // rebased record offsets of record slices (grow-only, owned)
-  uint64_t* slice_off = nullptr;
-  size_t slice_off_cap = 0;
+  // rebased record offsets of record slices (grow-only, to the exact size: slice_off_reserve)
+  sg::DevBuf<uint64_t> slice_off;
   // a batch's record-slice cuts, found on the device (sg_part_triage.hip k_slice_cuts)
   uint64_t* slice_cuts = nullptr;
   // small device scalars (counters / flags)
@@ -202,36 +199,43 @@ struct sg_set {
 };
 
 // map[hash.Sig]bool on the device (sg_sigset.hip)
+struct SigKey {
+  uint32_t w[SG_SIG_BYTES / 4];
+};
+// One {store, table} pair of a set.  The store's capacity is in keys; the
+// table's is its slot count, always the power of two that was asked for (the
+// probes mask with it).
+struct SigHalf {
+  sg::DevBuf<SigKey> store;
+  sg::DevBuf<uint32_t> table;
+  uint32_t* keys() const { return (uint32_t*)store.p; }
+  uint32_t mask() const { return (uint32_t)(table.cap - 1); }
+  void swap(SigHalf& o) {
+    store.swap(o.store);
+    table.swap(o.table);
+  }
+};
 struct sg_sigset {
   sg_ctx* ctx = nullptr;
   uint64_t count = 0;  // identities held (kept on the host: every call that changes it waits)
-  uint32_t* store = nullptr;
-  uint64_t store_cap = 0;  // keys
-  uint32_t* table = nullptr;
-  uint64_t nslots = 0;
-  // the second pair: hub_sync, remove and the hub corpus' purge build the new set in it, then swap
-  uint32_t* store2 = nullptr;
-  uint64_t store2_cap = 0;
-  uint32_t* table2 = nullptr;
-  uint64_t nslots2 = 0;
+  SigHalf cur;
+  // hub_sync, remove and the hub corpus' purge build the new set here, then swap the halves
+  SigHalf next;
 };
 
 namespace sg {
 
 // ---- host helpers (sg_ctx.hip) ----
-int hip_fail(hipError_t e, const char* what);
-#define SG_HIP(call)                                     \
-  do {                                                   \
-    hipError_t e_ = (call);                              \
-    if (e_ != hipSuccess) return ::sg::hip_fail(e_, #call); \
-  } while (0)
-
+// (hip_fail and SG_HIP: sg_buf.h)
 int ensure_device(sg_ctx* ctx);
-// Grow-only buffers.  The plan forms (WsPlan, sg_plan.h) reserve plan.total
-// and refuse a plan with more regions than it records.
+// Grow-only buffers, each by grow_cap (sg_plan.h) from its floor: 64 MiB of
+// workspace, 16 MiB of pinned and of device staging.  Growing drops the
+// contents and waits for ctx->stream first (the staging buffers: for
+// ctx->copy_stream too).  The plan forms (WsPlan) reserve plan.total and
+// refuse a plan with more regions than it records.
 int ws_reserve(sg_ctx* ctx, size_t bytes);
 int ws_reserve(sg_ctx* ctx, const WsPlan& plan);
-inline void* ws_at(sg_ctx* ctx, size_t off) { return (char*)ctx->ws + off; }
+inline void* ws_at(sg_ctx* ctx, size_t off) { return ctx->ws.p + off; }
 int pin_reserve(sg_ctx* ctx, size_t bytes);
 // The host forms' staging: plan the regions, reserve once, then bind each
 // pointer from the offset WsPlan::add returned (the buffer may move in the
@@ -240,8 +244,18 @@ int dstage_reserve(sg_ctx* ctx, size_t bytes);
 int dstage_reserve(sg_ctx* ctx, const WsPlan& plan);
 template <typename T>
 inline T* dstage_at(sg_ctx* ctx, size_t off) {
-  return (T*)((char*)ctx->dstage + off);
+  return (T*)(ctx->dstage.p + off);
 }
+// Room for `need` elements in a buffer that runs parallel to a set's keys (the
+// key store itself, the hub corpus' records): 1024 elements, then doubling,
+// the first `keep` kept (copied on ctx->stream, waited for).
+constexpr size_t kRecFloor = 1024;
+template <typename T>
+int rec_reserve(sg_ctx* ctx, DevBuf<T>& b, size_t need, size_t keep) {
+  return b.grow_keep(grow_cap(b.cap, need, kRecFloor), keep, ctx->stream);
+}
+// ctx->slice_off of exactly `n` offsets when it holds fewer (waits for ctx->stream).
+int slice_off_reserve(sg_ctx* ctx, size_t n);
 // Host -> device on ctx->stream; nothing for zero bytes.
 int upload(sg_ctx* ctx, void* d_dst, const void* h_src, size_t bytes);
 // CSR download on ctx->stream: the n + 1 offsets, a wait, then the off[n] *

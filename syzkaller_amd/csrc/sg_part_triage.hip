@@ -179,22 +179,14 @@ int bucket_triage(sg_ctx* ctx, uint32_t* mwords, uint32_t* nwords, const uint32_
   int rc = record_slices(ctx, d_off, nrec, sl);
   if (rc) return rc;
   // every slice's rebased offsets at once (no wait between two slices)
-  const size_t need = nrec + sl.size();
-  if (ctx->slice_off_cap < need) {
-    SG_HIP(hipStreamSynchronize(ctx->stream));
-    if (ctx->slice_off) SG_HIP(hipFree(ctx->slice_off));
-    ctx->slice_off = nullptr;
-    ctx->slice_off_cap = 0;
-    SG_HIP(hipMalloc(&ctx->slice_off, need * 8));
-    ctx->slice_off_cap = need;
-  }
+  if ((rc = slice_off_reserve(ctx, nrec + sl.size()))) return rc;
   size_t at = 0;
   for (const RecSlice& x : sl) {
     // the sequential loop (fuzzer.go:665) cut between two records sees the
     // same maxSignal at every record; a slice starts at a record boundary (a
     // trace slice's first entry is a call start)
     const uint64_t nr = x.r1 - x.r0;
-    uint64_t* roff = ctx->slice_off + at;
+    uint64_t* roff = ctx->slice_off.p + at;
     at += nr + 1;
     if (x.e1 == x.e0) continue;  // records without entries (flags cleared above)
     rc = rebase_offsets(ctx, d_off + x.r0, nr + 1, x.e0, roff);

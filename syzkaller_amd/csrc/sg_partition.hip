@@ -1030,7 +1030,7 @@ int partition_pass1(sg_ctx* ctx, const uint32_t* d_vals, const uint64_t* d_off, 
   }
   int rc = reserved ? SG_OK : ws_reserve(ctx, ws_base + bp.p.total);
   if (rc) return rc;
-  if (ctx->ws_cap < ws_base + bp.p.total) {
+  if (ctx->ws.cap < ws_base + bp.p.total) {
     set_error("bucket triage: workspace not reserved");
     return SG_EINVAL;
   }

@@ -32,6 +32,18 @@ struct WsPlan {
   }
 };
 
+// The capacity a grow-only buffer of `cap` elements takes to hold `need`:
+// unchanged while it fits, else max(2 * cap, floor) doubled until it does.
+// ("cap, or the floor when cap is 0, doubled while too small" is the same
+// function: growth is only entered with need > cap, where the first doubling
+// of cap always happens, and a buffer that exists is never below its floor.)
+inline size_t grow_cap(size_t cap, size_t need, size_t floor) {
+  if (need <= cap) return cap;
+  size_t nc = 2 * cap > floor ? 2 * cap : floor;
+  while (nc < need) nc *= 2;
+  return nc;
+}
+
 // CSR offsets of n lists: off[0] == 0 and non-decreasing up to off[n].
 inline bool offsets_ok(const uint64_t* off, size_t n) {
   if (off[0] != 0) return false;

@@ -132,38 +132,18 @@ __global__ __launch_bounds__(1024) void k_sum_counts(const uint32_t* __restrict_
 }
 
 // The slot's workspace stands in for the context's during one call (the
-// partition code addresses the workspace through ctx->ws); grown to the exact
-// size, since it is kept.
+// partition code addresses the workspace through ctx->ws): swapped in, and
+// out again with whatever the call made of it.
 struct SlotWs {
   sg_ctx* c;
   PrefixSlot& s;
-  void* ws;
-  size_t cap;
-  SlotWs(sg_ctx* c_, PrefixSlot& s_) : c(c_), s(s_), ws(c_->ws), cap(c_->ws_cap) {
-    c->ws = s.ws;
-    c->ws_cap = s.ws_cap;
-  }
-  ~SlotWs() {
-    s.ws = c->ws;
-    s.ws_cap = c->ws_cap;
-    c->ws = ws;
-    c->ws_cap = cap;
-  }
+  SlotWs(sg_ctx* c_, PrefixSlot& s_) : c(c_), s(s_) { c->ws.swap(s.ws); }
+  ~SlotWs() { c->ws.swap(s.ws); }
 };
 
-static int slot_reserve(sg_ctx* ctx, PrefixSlot& s, size_t bytes) {
-  if (bytes <= s.ws_cap) return SG_OK;
-  const size_t cap = (bytes + (64u << 20) - 1) & ~size_t((64u << 20) - 1);
-  if (s.ws) {
-    SG_HIP(hipStreamSynchronize(ctx->stream));
-    SG_HIP(hipFree(s.ws));
-    s.ws = nullptr;
-    s.ws_cap = 0;
-  }
-  SG_HIP(hipMalloc(&s.ws, cap));
-  s.ws_cap = cap;
-  return SG_OK;
-}
+// The slot's workspace grows to the size asked for rounded up to 64 MiB, not
+// by doubling, since it is kept.
+static size_t slot_cap(size_t bytes) { return (bytes + (64u << 20) - 1) & ~size_t((64u << 20) - 1); }
 
 // flags of the kept pairs {s, record}: kFixU pairs per thread in flight (one
 // pair per thread and step: 7.2 ms per C3 slice, eight: 3.9 ms).  Bound by
@@ -253,10 +233,10 @@ int prefix_begin(sg_ctx* ctx, uint32_t slot, const uint32_t* base_words, uint32_
   if (rc) return rc;
   if (!S.keep) {
     // the pairs: a counter, then <= n pairs
-    rc = slot_reserve(ctx, S, 256 + n * 8);
+    rc = S.ws.grow_drop(slot_cap(256 + n * 8), ctx->stream);
     if (rc) return rc;
-    unsigned long long* np = (unsigned long long*)S.ws;
-    uint2* pairs = (uint2*)((char*)S.ws + 256);
+    unsigned long long* np = (unsigned long long*)S.ws.p;
+    uint2* pairs = (uint2*)(S.ws.p + 256);
     SG_HIP(hipMemsetAsync(np, 0, 8, ctx->stream));
     SG_HIP(hipMemsetAsync(marks_words, 0, kSetBytes, ctx->stream));  // (the later slices' filter)
     size_t need = 0;
@@ -288,7 +268,7 @@ int prefix_begin(sg_ctx* ctx, uint32_t slot, const uint32_t* base_words, uint32_
   size_t total = 0;
   for (const RecSlice& x : sl)
     if (x.e1 > x.e0) total += align256(bucket_plan_bytes(x.e1 - x.e0, x.r1 - x.r0)) + align256((x.r1 - x.r0 + 1) * 8);
-  rc = slot_reserve(ctx, S, total ? total : 256);
+  rc = S.ws.grow_drop(slot_cap(total ? total : 256), ctx->stream);
   if (rc) return rc;
   SlotWs guard(ctx, S);
   size_t base = 0;
@@ -342,12 +322,12 @@ int prefix_end(sg_ctx* ctx, uint32_t slot, uint32_t* mwords, const uint32_t* owo
       ScopedTimer tm(ctx, "prefix_flags");
       hipLaunchKernelGGL(k_prefix_flags, dim3((uint32_t)std::min<uint64_t>(div_up(S.n, kFixT * kFixU), 2048)),
                          dim3(kFixT), 0,
-                         ctx->stream, (const uint2*)((char*)S.ws + 256), (const unsigned long long*)S.ws, mwords,
+                         ctx->stream, (const uint2*)(S.ws.p + 256), (const unsigned long long*)S.ws.p, mwords,
                          owords, d_rec_new);
     }
     if (ctx->debug_part && S.n) {  // diagnostics (syncs): the kept pairs
       unsigned long long np = 0;
-      SG_HIP(hipMemcpyAsync(&np, S.ws, 8, hipMemcpyDeviceToHost, ctx->stream));
+      SG_HIP(hipMemcpyAsync(&np, S.ws.p, 8, hipMemcpyDeviceToHost, ctx->stream));
       SG_HIP(hipStreamSynchronize(ctx->stream));
       fprintf(stderr, "sg prefix: %llu entries, %llu pairs\n", (unsigned long long)S.n, np);
     }

@@ -417,7 +417,7 @@ int sg_prog_hashes(sg_ctx* ctx, const uint8_t* bytes, const uint64_t* off, size_
   if ((rc = upload(ctx, dbytes, bytes, nbytes))) return rc;
   if ((rc = upload(ctx, doff, off, (nprogs + 1) * 8))) return rc;
   if ((rc = prog_hashes(ctx, dbytes, doff, nprogs, nbytes, dsig, 0))) return rc;
-  uint8_t* hs = sigs ? sigs : (uint8_t*)ctx->pin;
+  uint8_t* hs = sigs ? sigs : (uint8_t*)ctx->pin.p;
   SG_HIP(hipMemcpyAsync(hs, dsig, nprogs * SG_SIG_BYTES, hipMemcpyDeviceToHost, ctx->stream));
   SG_HIP(hipStreamSynchronize(ctx->stream));
   if (hex) {  // hex.EncodeToString

@@ -1039,7 +1039,7 @@ int sg_cover_uncovered(sg_ctx* ctx, const uint32_t* cov, size_t ncov, uint32_t b
   const size_t scan_off = p.total;
   rc = ws_reserve(ctx, p.total + std::max(scan_ws_bytes(nchunks), report_query_scan_bytes(t, ncov, chunked)));
   if (rc) return rc;
-  report_tables_bind(ctx->ws, to, t);
+  report_tables_bind(ctx->ws.p, to, t);
   uint32_t* dcov = (uint32_t*)ws_at(ctx, o_cov);
   uint64_t* mask = (uint64_t*)ws_at(ctx, o_m);
   uint32_t* cnt = (uint32_t*)ws_at(ctx, o_c);

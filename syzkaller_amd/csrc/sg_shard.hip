@@ -373,18 +373,11 @@ int sg_shard_candidates_dev(sg_ctx* ctx, sg_set* snapshot, const uint32_t* d_val
         set_error("sg_shard_candidates_dev: a record holds >= 2^30 signal entries");
         return SG_EINVAL;
       }
-    if (ctx->slice_off_cap < need) {
-      SG_HIP(hipStreamSynchronize(ctx->stream));
-      if (ctx->slice_off) SG_HIP(hipFree(ctx->slice_off));
-      ctx->slice_off = nullptr;
-      ctx->slice_off_cap = 0;
-      SG_HIP(hipMalloc(&ctx->slice_off, need * 8));
-      ctx->slice_off_cap = need;
-    }
+    if ((rc = slice_off_reserve(ctx, need))) return rc;
     size_t at = 0;
     for (size_t j = 0; j < ns; j++) {
       const uint64_t r0 = cuts[4 * j], r1 = cuts[4 * j + 1], e0 = cuts[4 * j + 2], e1 = cuts[4 * j + 3];
-      uint64_t* roff = ctx->slice_off + at;
+      uint64_t* roff = ctx->slice_off.p + at;
       at += r1 - r0 + 1;
       if (e1 == e0) continue;
       rc = rebase_offsets(ctx, d_rec_off + r0, r1 - r0 + 1, e0, roff);
@@ -629,7 +622,7 @@ int sg_prefix_cands_dev(sg_ctx* ctx, uint32_t slot, uint32_t* d_out, uint64_t ca
   }
   if (!cap || !S.n) return SG_OK;
   hipLaunchKernelGGL(k_pair_sigs, dim3(std::min<uint64_t>(div_up(cap, 256), 8192)), dim3(256), 0, ctx->stream,
-                     (const uint2*)((char*)S.ws + 256), (const unsigned long long*)S.ws, cap, d_out);
+                     (const uint2*)(S.ws.p + 256), (const unsigned long long*)S.ws.p, cap, d_out);
   SG_HIP(hipGetLastError());
   return SG_OK;
 }

@@ -30,10 +30,16 @@
 //    k_ss_remove_mark finds each batch key's store index and atomicMin's the
 //    batch position into first[index]; a later launch flags the removed keys
 //    (first[index] is their own position) and the survivors (first[] still
-//    empty); the survivors are gathered into the second store and a fresh
-//    table is built from it, as sg_hub_sync does: no tombstones.
+//    empty); the survivors are gathered into the second half's store and a
+//    fresh table is built from it, as sg_hub_sync does: no tombstones.
+// A set has two halves of {store, table}, each buffer owning its block and
+// capacity (SigHalf, sg_internal.h; DevBuf, sg_buf.h).  The set is `cur`;
+// hub_sync, remove and the hub corpus' purge build the new set in `next` and
+// swap the halves once, so either half may be the one that grows next.
 // Growth rebuilds a larger table from the store by the same insert kernel
-// before the batch is inserted; the store is reallocated with a device copy.
+// before the batch is inserted (the table's capacity is its slot count, a
+// power of two, never rounded); the store grows from 1024 keys by doubling
+// with a device copy of its keys (rec_reserve).
 // Every index is checked against count + n before it is used as an address,
 // and every probe loop is bounded by the number of slots.
 #include "sg_internal.h"
@@ -226,63 +232,41 @@ int launch_insert(sg_ctx* ctx, const View& v, uint32_t i0, uint32_t m) {
   return SG_OK;
 }
 
-// a table of at least `slots` slots, all empty
-int table_fresh(sg_ctx* ctx, uint32_t** table, uint64_t* nslots, uint64_t slots) {
-  if (*nslots < slots) {
-    if (*table) {
-      SG_HIP(hipStreamSynchronize(ctx->stream));
-      SG_HIP(hipFree(*table));
-      *table = nullptr;
-      *nslots = 0;
-    }
-    SG_HIP(hipMalloc(table, slots * 4));
-    *nslots = slots;
-  }
-  SG_HIP(hipMemsetAsync(*table, 0xFF, *nslots * 4, ctx->stream));
+// the set of h's first `count` keys, for a batch of n scratch keys at `scratch`
+View view_of(const SigHalf& h, uint64_t count, const uint32_t* scratch = nullptr, uint64_t n = 0) {
+  return View{h.keys(), (uint32_t)count, nullptr, scratch, (uint32_t)n, h.table.p, h.mask()};
+}
+
+// a table of at least `slots` slots (exactly `slots` when it has to grow), all empty
+int table_fresh(sg_ctx* ctx, DevBuf<uint32_t>& table, uint64_t slots) {
+  const int rc = table.grow_drop(slots, ctx->stream);
+  if (rc) return rc;
+  SG_HIP(hipMemsetAsync(table.p, 0xFF, table.cap * 4, ctx->stream));
   return SG_OK;
 }
 
-// room for `keys` keys in a store, the first `keep` kept
-int store_reserve(sg_ctx* ctx, uint32_t** store, uint64_t* cap, uint64_t keys, uint64_t keep) {
-  if (keys <= *cap) return SG_OK;
-  uint64_t nc = std::max<uint64_t>(*cap * 2, 1024);
-  while (nc < keys) nc *= 2;
-  uint32_t* ns = nullptr;
-  SG_HIP(hipMalloc(&ns, nc * SG_SIG_BYTES));
-  hipError_t e = hipSuccess;
-  if (*store && keep) e = hipMemcpyAsync(ns, *store, keep * SG_SIG_BYTES, hipMemcpyDeviceToDevice, ctx->stream);
-  if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-  if (e != hipSuccess) {
-    hipFree(ns);
-    return hip_fail(e, "store_reserve");
-  }
-  if (*store) SG_HIP(hipFree(*store));
-  *store = ns;
-  *cap = nc;
-  return SG_OK;
+// a half for a fresh set of up to `keys` keys: room in the store (nothing kept), an empty table
+int half_fresh(sg_ctx* ctx, SigHalf& h, uint64_t keys) {
+  const int rc = rec_reserve(ctx, h.store, std::max<uint64_t>(keys, 1), 0);
+  return rc ? rc : table_fresh(ctx, h.table, slots_for(keys));
 }
 
 // the table sized for count + n keys: a larger one is rebuilt from the store
 int grow_for(sg_sigset* s, uint64_t n) {
   sg_ctx* ctx = s->ctx;
-  int rc = store_reserve(ctx, &s->store, &s->store_cap, s->count + n, s->count);
+  SigHalf& h = s->cur;
+  int rc = rec_reserve(ctx, h.store, s->count + n, s->count);
   if (rc) return rc;
   const uint64_t need = slots_for(s->count + n);
-  if (need <= s->nslots) return SG_OK;
-  uint32_t* nt = nullptr;
-  uint64_t ns = 0;
-  if ((rc = table_fresh(ctx, &nt, &ns, need))) return rc;
-  const View v{s->store, (uint32_t)s->count, nullptr, nullptr, 0, nt, (uint32_t)(ns - 1)};
+  if (need <= h.table.cap) return SG_OK;
+  DevBuf<uint32_t> nt;  // (freed here unless it is swapped in)
+  if ((rc = table_fresh(ctx, nt, need))) return rc;
+  const View v{h.keys(), (uint32_t)s->count, nullptr, nullptr, 0, nt.p, (uint32_t)(nt.cap - 1)};
   rc = launch_insert(ctx, v, 0, (uint32_t)s->count);
-  hipError_t e = hipStreamSynchronize(ctx->stream);
-  if (rc || e != hipSuccess) {
-    hipFree(nt);
-    return rc ? rc : hip_fail(e, "grow_for");
-  }
-  if (s->table) SG_HIP(hipFree(s->table));
-  s->table = nt;
-  s->nslots = ns;
-  return SG_OK;
+  const hipError_t e = hipStreamSynchronize(ctx->stream);
+  if (rc || e != hipSuccess) return rc ? rc : hip_fail(e, "grow_for");
+  h.table.swap(nt);
+  return nt.release();
 }
 
 // workspace of an add of n scratch keys: flags, slots, positions, the scan
@@ -297,11 +281,11 @@ struct AddPlan {
   }
 };
 
-// insert, flags, scan, compact of n scratch keys (device) into {store, table} holding `count`; is_new nullable.
+// insert, flags, scan, compact of n scratch keys (device) into the half h holding `count`; is_new nullable.
 // The new count is count + pos[n] (device, at ws o_pos + 8 * n).
-int add_scratch(sg_ctx* ctx, uint32_t* store, uint64_t store_cap, uint32_t* table, uint64_t nslots, uint64_t count,
-                const uint32_t* d_keys, uint64_t n, const AddPlan& ap, uint8_t* d_is_new) {
-  const View v{store, (uint32_t)count, nullptr, d_keys, (uint32_t)n, table, (uint32_t)(nslots - 1)};
+int add_scratch(sg_ctx* ctx, const SigHalf& h, uint64_t count, const uint32_t* d_keys, uint64_t n, const AddPlan& ap,
+                uint8_t* d_is_new) {
+  const View v = view_of(h, count, d_keys, n);
   uint32_t* flag = (uint32_t*)ws_at(ctx, ap.o_flag);
   uint32_t* slot = (uint32_t*)ws_at(ctx, ap.o_slot);
   uint64_t* pos = (uint64_t*)ws_at(ctx, ap.o_pos);
@@ -316,7 +300,7 @@ int add_scratch(sg_ctx* ctx, uint32_t* store, uint64_t store_cap, uint32_t* tabl
   if (n) {
     ScopedTimer tm(ctx, "sigset_compact");
     hipLaunchKernelGGL(k_ss_compact, dim3(div_up(n, kST)), dim3(kST), 0, ctx->stream, v, (const uint32_t*)flag,
-                       (const uint32_t*)slot, (const uint64_t*)pos, store, store_cap);
+                       (const uint32_t*)slot, (const uint64_t*)pos, h.keys(), (uint64_t)h.store.cap);
   }
   SG_HIP(hipGetLastError());
   return SG_OK;
@@ -340,14 +324,6 @@ int room_ok(const char* fn, const sg_sigset* s, uint64_t n) {
     return SG_EINVAL;
   }
   return SG_OK;
-}
-
-void set_free(sg_sigset* s) {
-  if (s->store) hipFree(s->store);
-  if (s->table) hipFree(s->table);
-  if (s->store2) hipFree(s->store2);
-  if (s->table2) hipFree(s->table2);
-  delete s;
 }
 
 // sg_sigset_add_new / _add_progs after the checks; keys: host identities, or null to hash the programs
@@ -379,7 +355,7 @@ int add_common(sg_sigset* s, const uint8_t* keys, const uint8_t* bytes, const ui
     if ((rc = prog_hashes(ctx, dbytes, doff, n, nbytes, (uint8_t*)dkeys, 0))) return rc;
     if (sigs) SG_HIP(hipMemcpyAsync(sigs, dkeys, n * SG_SIG_BYTES, hipMemcpyDeviceToHost, ctx->stream));
   }
-  if ((rc = add_scratch(ctx, s->store, s->store_cap, s->table, s->nslots, s->count, dkeys, n, ap, dnew))) return rc;
+  if ((rc = add_scratch(ctx, s->cur, s->count, dkeys, n, ap, dnew))) return rc;
   uint64_t added = 0;
   SG_HIP(hipMemcpyAsync(is_new, dnew, n, hipMemcpyDeviceToHost, ctx->stream));
   SG_HIP(hipMemcpyAsync(&added, (uint64_t*)ws_at(ctx, ap.o_pos) + n, 8, hipMemcpyDeviceToHost, ctx->stream));
@@ -396,16 +372,14 @@ int sigset_new(sg_ctx* ctx, uint64_t hint, sg_sigset** out) {
   s->ctx = ctx;
   const int rc = grow_for(s, std::max<uint64_t>(hint, 1));
   if (rc) {
-    set_free(s);
+    delete s;
     return rc;
   }
   *out = s;
   return SG_OK;
 }
 
-void sigset_delete(sg_sigset* s) {
-  if (s) set_free(s);
-}
+void sigset_delete(sg_sigset* s) { delete s; }
 
 size_t sigset_add_ws(uint64_t n) { return AddPlan(0, n).total; }
 
@@ -416,7 +390,7 @@ int sigset_add_dev(sg_sigset* s, const uint32_t* d_keys, uint64_t n, uint8_t* d_
   int rc = room_ok("sigset_add_dev", s, n);
   if (rc) return rc;
   if ((rc = grow_for(s, n))) return rc;
-  if ((rc = add_scratch(ctx, s->store, s->store_cap, s->table, s->nslots, s->count, d_keys, n, ap, d_is_new))) return rc;
+  if ((rc = add_scratch(ctx, s->cur, s->count, d_keys, n, ap, d_is_new))) return rc;
   uint64_t added = 0;
   SG_HIP(hipMemcpyAsync(&added, (uint64_t*)ws_at(ctx, ap.o_pos) + n, 8, hipMemcpyDeviceToHost, ctx->stream));
   SG_HIP(hipStreamSynchronize(ctx->stream));
@@ -427,7 +401,7 @@ int sigset_add_dev(sg_sigset* s, const uint32_t* d_keys, uint64_t n, uint8_t* d_
 int sigset_lookup_dev(sg_sigset* s, const uint32_t* d_keys, uint64_t n, uint32_t want, uint32_t* out32) {
   if (!n) return SG_OK;
   sg_ctx* ctx = s->ctx;
-  const View v{s->store, (uint32_t)s->count, nullptr, nullptr, 0, s->table, (uint32_t)(s->nslots - 1)};
+  const View v = view_of(s->cur, s->count);
   ScopedTimer tm(ctx, "sigset_lookup");
   hipLaunchKernelGGL(k_ss_lookup, dim3(div_up(n, kST)), dim3(kST), 0, ctx->stream, v, d_keys, n, (const uint32_t*)nullptr,
                      want, (uint8_t*)nullptr, out32);
@@ -438,7 +412,7 @@ int sigset_lookup_dev(sg_sigset* s, const uint32_t* d_keys, uint64_t n, uint32_t
 int sigset_lookup_or_dev(sg_sigset* s, const uint32_t* d_keys, uint64_t n, uint32_t* acc) {
   if (!n) return SG_OK;
   sg_ctx* ctx = s->ctx;
-  const View v{s->store, (uint32_t)s->count, nullptr, nullptr, 0, s->table, (uint32_t)(s->nslots - 1)};
+  const View v = view_of(s->cur, s->count);
   ScopedTimer tm(ctx, "sigset_lookup");
   hipLaunchKernelGGL(k_ss_lookup_or, dim3(div_up(n, kST)), dim3(kST), 0, ctx->stream, v, d_keys, n, acc);
   SG_HIP(hipGetLastError());
@@ -458,17 +432,12 @@ int sigset_rebuild_dev(sg_sigset* s, const uint32_t* d_keep, const uint64_t* d_p
   sg_ctx* ctx = s->ctx;
   const uint64_t c = s->count;
   if (newcount > c) newcount = c;
-  int rc = store_reserve(ctx, &s->store2, &s->store2_cap, std::max<uint64_t>(newcount, 1), 0);
+  int rc = half_fresh(ctx, s->next, newcount);
   if (rc) return rc;
-  if ((rc = table_fresh(ctx, &s->table2, &s->nslots2, slots_for(newcount)))) return rc;
-  if ((rc = sigset_gather_dev(ctx, s->store, c, d_keep, d_pos, s->store2, newcount))) return rc;
-  const View v{s->store2, (uint32_t)newcount, nullptr, nullptr, 0, s->table2, (uint32_t)(s->nslots2 - 1)};
-  if ((rc = launch_insert(ctx, v, 0, (uint32_t)newcount))) return rc;
+  if ((rc = sigset_gather_dev(ctx, s->cur.keys(), c, d_keep, d_pos, s->next.keys(), newcount))) return rc;
+  if ((rc = launch_insert(ctx, view_of(s->next, newcount), 0, (uint32_t)newcount))) return rc;
   SG_HIP(hipStreamSynchronize(ctx->stream));
-  std::swap(s->store, s->store2);
-  std::swap(s->store_cap, s->store2_cap);
-  std::swap(s->table, s->table2);
-  std::swap(s->nslots, s->nslots2);
+  s->cur.swap(s->next);
   s->count = newcount;
   return SG_OK;
 }
@@ -491,17 +460,8 @@ int sg_sigset_create(sg_ctx* ctx, uint64_t capacity_hint, sg_sigset** out) {
     return SG_EINVAL;
   }
   std::lock_guard<std::mutex> g(ctx->mu);
-  int rc = ensure_device(ctx);
-  if (rc) return rc;
-  sg_sigset* s = new sg_sigset();
-  s->ctx = ctx;
-  rc = grow_for(s, std::max<uint64_t>(capacity_hint, 1));
-  if (rc) {
-    set_free(s);
-    return rc;
-  }
-  *out = s;
-  return SG_OK;
+  const int rc = ensure_device(ctx);
+  return rc ? rc : sigset_new(ctx, capacity_hint, out);
 }
 
 void sg_sigset_destroy(sg_sigset* s) {
@@ -511,7 +471,7 @@ void sg_sigset_destroy(sg_sigset* s) {
     hipSetDevice(s->ctx->device);
     hipStreamSynchronize(s->ctx->stream);
   }
-  set_free(s);
+  delete s;
 }
 
 int sg_sigset_clear(sg_sigset* s) {
@@ -523,7 +483,7 @@ int sg_sigset_clear(sg_sigset* s) {
   std::lock_guard<std::mutex> g(ctx->mu);
   int rc = ensure_device(ctx);
   if (rc) return rc;
-  SG_HIP(hipMemsetAsync(s->table, 0xFF, s->nslots * 4, ctx->stream));
+  SG_HIP(hipMemsetAsync(s->cur.table.p, 0xFF, s->cur.table.cap * 4, ctx->stream));
   s->count = 0;
   return SG_OK;
 }
@@ -549,7 +509,7 @@ int sg_sigset_export(sg_sigset* s, uint8_t* sigs, size_t cap, size_t* n) {
   if (rc) return rc;
   *n = s->count;
   if (s->count && s->count <= cap) {
-    SG_HIP(hipMemcpyAsync(sigs, s->store, s->count * SG_SIG_BYTES, hipMemcpyDeviceToHost, ctx->stream));
+    SG_HIP(hipMemcpyAsync(sigs, s->cur.keys(), s->count * SG_SIG_BYTES, hipMemcpyDeviceToHost, ctx->stream));
     SG_HIP(hipStreamSynchronize(ctx->stream));
   }
   return SG_OK;
@@ -569,7 +529,7 @@ int sg_sigset_contains(sg_sigset* s, const uint8_t* sigs, size_t n, uint8_t* pre
   uint32_t* dkeys = dstage_at<uint32_t>(ctx, o_keys);
   uint8_t* dout = dstage_at<uint8_t>(ctx, o_out);
   if ((rc = upload(ctx, dkeys, sigs, n * SG_SIG_BYTES))) return rc;
-  const View v{s->store, (uint32_t)s->count, nullptr, nullptr, 0, s->table, (uint32_t)(s->nslots - 1)};
+  const View v = view_of(s->cur, s->count);
   {
     ScopedTimer tm(ctx, "sigset_lookup");
     hipLaunchKernelGGL(k_ss_lookup, dim3(div_up(n, kST)), dim3(kST), 0, ctx->stream, v, (const uint32_t*)dkeys, (uint64_t)n,
@@ -637,8 +597,7 @@ int sg_hub_sync(sg_sigset* hub, const uint8_t* bytes, const uint64_t* off, size_
   const AddPlan ap(align256(prog_hashes_ws(n)), n);
   const size_t o_dflag = ap.total, o_dpos = o_dflag + align256(c * 4 + 4), o_dscan = o_dpos + align256((c + 1) * 8);
   if ((rc = ws_reserve(ctx, o_dscan + scan_ws_bytes(c)))) return rc;
-  if ((rc = store_reserve(ctx, &hub->store2, &hub->store2_cap, std::max<uint64_t>(n, 1), 0))) return rc;
-  if ((rc = table_fresh(ctx, &hub->table2, &hub->nslots2, slots_for(n)))) return rc;
+  if ((rc = half_fresh(ctx, hub->next, n))) return rc;
   uint32_t* dkeys = dstage_at<uint32_t>(ctx, o_keys);
   uint8_t* dadd = dstage_at<uint8_t>(ctx, o_add);
   uint32_t* ddel = dstage_at<uint32_t>(ctx, o_del);
@@ -651,11 +610,12 @@ int sg_hub_sync(sg_sigset* hub, const uint8_t* bytes, const uint64_t* off, size_
     if (sigs) SG_HIP(hipMemcpyAsync(sigs, dkeys, n * SG_SIG_BYTES, hipMemcpyDeviceToHost, ctx->stream));
   }
   // the fresh set: the corpus' identities in first-occurrence order
-  if ((rc = add_scratch(ctx, hub->store2, hub->store2_cap, hub->table2, hub->nslots2, 0, dkeys, n, ap, nullptr))) return rc;
+  if ((rc = add_scratch(ctx, hub->next, 0, dkeys, n, ap, nullptr))) return rc;
   const uint32_t* flag = (const uint32_t*)ws_at(ctx, ap.o_flag);
   const uint64_t* count2 = (const uint64_t*)ws_at(ctx, ap.o_pos) + n;
-  const View vold{hub->store, (uint32_t)c, nullptr, nullptr, 0, hub->table, (uint32_t)(hub->nslots - 1)};
-  const View vnew{hub->store2, 0, count2, nullptr, 0, hub->table2, (uint32_t)(hub->nslots2 - 1)};
+  const View vold = view_of(hub->cur, c);
+  View vnew = view_of(hub->next, 0);
+  vnew.count_dev = count2;
   uint32_t* dflag = (uint32_t*)ws_at(ctx, o_dflag);
   uint64_t* dpos = (uint64_t*)ws_at(ctx, o_dpos);
   {
@@ -666,14 +626,14 @@ int sg_hub_sync(sg_sigset* hub, const uint8_t* bytes, const uint64_t* off, size_
                          0u, dadd, (uint32_t*)nullptr);
     // Del: the old identities the fresh set does not hold
     if (c)
-      hipLaunchKernelGGL(k_ss_lookup, dim3(div_up(c, kST)), dim3(kST), 0, ctx->stream, vnew, (const uint32_t*)hub->store, c,
-                         (const uint32_t*)nullptr, 0u, (uint8_t*)nullptr, dflag);
+      hipLaunchKernelGGL(k_ss_lookup, dim3(div_up(c, kST)), dim3(kST), 0, ctx->stream, vnew,
+                         (const uint32_t*)hub->cur.keys(), c, (const uint32_t*)nullptr, 0u, (uint8_t*)nullptr, dflag);
   }
   SG_HIP(hipGetLastError());
   if ((rc = scan_counts(ctx, dflag, dpos, c, o_dscan))) return rc;
   if (c) {
     ScopedTimer tm(ctx, "hub_sync_gather");
-    hipLaunchKernelGGL(k_ss_gather, dim3(div_up(c, kST)), dim3(kST), 0, ctx->stream, (const uint32_t*)hub->store, c,
+    hipLaunchKernelGGL(k_ss_gather, dim3(div_up(c, kST)), dim3(kST), 0, ctx->stream, (const uint32_t*)hub->cur.keys(), c,
                        (const uint32_t*)dflag, (const uint64_t*)dpos, ddel, c);
   }
   SG_HIP(hipGetLastError());
@@ -688,10 +648,7 @@ int sg_hub_sync(sg_sigset* hub, const uint8_t* bytes, const uint64_t* off, size_
     SG_HIP(hipStreamSynchronize(ctx->stream));
   }
   *ndel = nd;
-  std::swap(hub->store, hub->store2);
-  std::swap(hub->store_cap, hub->store2_cap);
-  std::swap(hub->table, hub->table2);
-  std::swap(hub->nslots, hub->nslots2);
+  hub->cur.swap(hub->next);
   hub->count = std::min(got[0], n);
   return SG_OK;
 }
@@ -720,7 +677,7 @@ int sg_sigset_remove(sg_sigset* s, const uint8_t* sigs, size_t n, uint8_t* remov
   uint64_t* pos = (uint64_t*)ws_at(ctx, o_pos);
   if ((rc = upload(ctx, dkeys, sigs, n * SG_SIG_BYTES))) return rc;
   SG_HIP(hipMemsetAsync(first, 0xFF, c * 4 + 4, ctx->stream));
-  const View v{s->store, (uint32_t)c, nullptr, nullptr, 0, s->table, (uint32_t)(s->nslots - 1)};
+  const View v = view_of(s->cur, c);
   {
     ScopedTimer tm(ctx, "sigset_remove");
     hipLaunchKernelGGL(k_ss_remove_mark, dim3(div_up(n, kST)), dim3(kST), 0, ctx->stream, v, (const uint32_t*)dkeys,

@@ -1,7 +1,8 @@
 // The buffer planner and the offsets check of syzkaller_amd/csrc/sg_plan.h, on
 // the CPU: alignment, no overlap, the total, the region-count overflow, and
 // the three largest staging layouts against the byte counts their entry points
-// summed by hand before they used the planner.
+// summed by hand before they used the planner; and grow_cap, the capacity
+// policy of the grow-only buffers.
 #include <cstdio>
 #include <vector>
 
@@ -118,6 +119,42 @@ int main() {
            {nrecs * 32 + 32, (ncalls + 1) * 8, (ncalls + 1) * 8, nvals * 8 + 8, ncalls * 4 + 4, (nvals + 1) * 8,
             (ncalls + 1) * 8, (ncalls + 1) * 8, 2 * nrecs * 16 + 16},
            {768, 512, 512, 768, 256, 768, 512, 512, 768}, 5376);
+  }
+  {  // grow_cap: the capacity a grow-only buffer takes
+    const size_t MiB = size_t(1) << 20;
+    const struct {
+      size_t cap, need, floor, want;
+    } cases[] = {{0, 0, 1024, 0},
+                 {0, 1, 1024, 1024},
+                 {0, 1024, 1024, 1024},
+                 {0, 1025, 1024, 2048},
+                 {1024, 1024, 1024, 1024},
+                 {1024, 1025, 1024, 2048},
+                 {1024, 5000, 1024, 8192},
+                 {2048, 2049, 1024, 4096},
+                 {0, 1, 64 * MiB, 64 * MiB},
+                 {64 * MiB, 64 * MiB + 1, 64 * MiB, 128 * MiB},
+                 {0, 16 * MiB + 1, 16 * MiB, 32 * MiB}};
+    for (const auto& c : cases) {
+      const size_t got = sg::grow_cap(c.cap, c.need, c.floor);
+      if (got != c.want) {
+        printf("FAIL grow_cap(%zu, %zu, %zu) = %zu, expected %zu\n", c.cap, c.need, c.floor, got, c.want);
+        fails++;
+      }
+    }
+    for (size_t cap : {size_t(0), size_t(1024), size_t(3000)})
+      for (size_t need = 0; need <= 10000; need++) {
+        const size_t got = sg::grow_cap(cap, need, 1024);
+        CHECK(got >= need);
+        if (need <= cap) CHECK(got == cap);
+        // the loop the key store's reserve ran before the policy was shared
+        size_t nc = cap;
+        if (need > cap) {
+          nc = cap * 2 > 1024 ? cap * 2 : 1024;
+          while (nc < need) nc *= 2;
+        }
+        CHECK(got == nc);
+      }
   }
   if (fails) return 1;
   printf("PASS\n");

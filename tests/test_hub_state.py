@@ -759,6 +759,47 @@ def test_hubcorpus_purge(ctx):
 
 
 @pytest.mark.gpu
+def test_hubcorpus_growth_across_purges(ctx):
+    """purge gathers the kept records into second buffers and swaps them in: the buffers that grow next are the
+    swapped-in ones, at their own capacity, and they must keep the records they hold."""
+    from syzkaller_amd import hub as H
+    from syzkaller_amd.corpus import SigSet
+
+    progs = K.pool(3000, 23)
+    t = H.NameTable(ctx)
+    c, o = H.HubCorpus(t), OR.OHubCorpus(OR.ONameTable())
+    mgr, omgr = SigSet(ctx=ctx), OR.OSet()
+
+    def add(batch, seq):
+        got, exp = c.add(batch, seq), o.add(batch, seq)
+        for g, e in zip(got, exp):
+            assert np.array_equal(g, e), seq
+        _same_corpus(c, o)
+
+    def purge(left):
+        got, exp = c.purge([mgr]), o.purge([omgr])
+        assert [g.tobytes() for g in got] == exp and c.count() == left
+        _same_corpus(c, o)
+
+    add(progs[:1500], 1)                                 # records and call ids pass 1024: grown with their contents
+    assert c.export()[3].size > 1024
+    held = [OR.Hash(p) for p in progs[:1500:75]]
+    mgr.add_new(held)
+    for h in held:
+        omgr.m[h] = True
+    purge(20)                                            # the second buffers come in at their first capacity
+    add(progs[1500:], 2)                                 # ... and grow keeping the 20 records
+    assert c.count() == 1520
+    got = _pending(c, o, mgr, omgr, 0, 2, K.NAMES, 1000)
+    assert len(got[0]) == 1500                           # (one seq: the tie runs past max_records to the end)
+    purge(20)                                            # swapped back to the buffers that had grown
+    add(progs[1:11], 3)
+    assert c.count() == 30
+    for x in (c, mgr, t):
+        x.close()
+
+
+@pytest.mark.gpu
 def test_hub_state_against_the_oracle(ctx):
     from syzkaller_amd import hub as H
 

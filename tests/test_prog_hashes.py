@@ -397,6 +397,52 @@ def test_growth_from_a_hint_of_one(ctx):
 
 
 @pytest.mark.gpu
+def test_sigset_growth_across_swaps(ctx):
+    """remove and hub_sync build the new set in the second {store, table} pair and swap it in: the pair that
+    grows next is the one swapped in, at its own capacity, and it must keep the keys it holds."""
+    from syzkaller_amd.corpus import SigSet
+
+    s, o = SigSet(1, ctx=ctx), OR.OSigSet()
+    sigs = K.random_sigs(4505, 52)
+    ever = [sigs]
+
+    def same(what):
+        assert s.count() == o.count() == len(s), what
+        assert np.array_equal(s.export(), o.export()), what
+        for e in ever:
+            assert np.array_equal(s.contains(e), o.contains(e)), what
+
+    def remove(batch):
+        exp = np.array([o.m.pop(bytes(x), None) is not None for x in batch], dtype=bool)
+        assert np.array_equal(s.remove(batch), exp)
+
+    assert np.array_equal(s.add_new(sigs[:1500]), o.add_new(sigs[:1500]))  # the store passes 1024 keys, the table grows
+    same("1500 added")
+    remove(sigs[10:1500])                                                    # rebuilt in the second pair, swapped
+    assert s.count() == 10
+    same("all but 10 removed")
+    fresh = sigs[1500:4500]
+    assert np.array_equal(s.add_new(fresh), o.add_new(fresh))                # the swapped-in pair grows, keeping 10
+    same("3000 added")
+    corpus = K.POOL + [K.text(40 + k % 90, 8000 + k) for k in range(800)]
+    assert len(corpus) == 1200
+    ever.append(OR.hashes(corpus))
+    _sync(s, o, corpus, "a corpus of 1200")                                  # the second swap: back to the first pair
+    same("synced")
+    more = [K.text(30 + k % 120, 9000 + k) for k in range(2000)]
+    ever.append(OR.hashes(more))
+    assert np.array_equal(s.add_progs(more), o.add_new(ever[-1]))
+    same("2000 programs added")
+    remove(s.export())
+    assert s.count() == 0
+    same("everything removed")
+    assert np.array_equal(s.add_new(sigs[4500:]), o.add_new(sigs[4500:]))
+    assert s.count() == 5
+    same("5 added")
+    s.close()
+
+
+@pytest.mark.gpu
 def test_contains(ctx):
     from syzkaller_amd.corpus import SigSet
 
