@@ -74,7 +74,9 @@ int sg_ctx_kernel_time(sg_ctx* ctx, const char* name, double* ms, uint64_t* laun
  * sg_triage_traces without diff lists): "host_copy_bytes", "host_copy_ns"
  * (pageable -> pinned copies), "host_wait_ns" (waits for a staging slot's DMA),
  * "host_copy_threads"; "cpu_quota_milli" (the CPUs this process may use,
- * x1000); the M0 filter (the flags path's low-novelty regime): "m0_filter_used"
+ * x1000); "workspace_bytes" (the capacity of the context's grow-only device
+ * workspace: 0 before the first call that needs it, then 64 MiB, doubling);
+ * the M0 filter (the flags path's low-novelty regime): "m0_filter_used"
  * and "m0_filter_fallback" (record slices it finished / that went on to pass
  * 2), "m0_filter_survivors" (the last launch's), "m0_filter_queued_milli" (the
  * queued fraction of the last partitioned slice, x1000, that auto reads),

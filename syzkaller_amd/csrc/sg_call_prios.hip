@@ -89,17 +89,11 @@ struct AddArgs {
   unsigned long long* counts;
 };
 
-// program p's range of ids, clamped to the buffer
-__device__ __forceinline__ void prog_range(const AddArgs& a, uint64_t p, uint64_t& a0, uint64_t& a1) {
-  a0 = min(a.off[p], a.nids);
-  a1 = min(max(a.off[p + 1], a0), a.nids);
-}
-
 __global__ __launch_bounds__(kPT) void k_prio_merge(AddArgs a) {
   const uint64_t stride = (uint64_t)gridDim.x * kPT;
   for (uint64_t p = (uint64_t)blockIdx.x * kPT + threadIdx.x; p < a.nprogs; p += stride) {
     uint64_t a0, a1;
-    prog_range(a, p, a0, a1);
+    sgd::csr_range(a.off, p, a.nids, a0, a1);  // program p's ids, clamped to the buffer
     const uint64_t len = a1 - a0;
     if (len == 0) continue;
     if (len > kPrioShort) {
@@ -178,7 +172,7 @@ __global__ __launch_bounds__(kPT) void k_prio_long(AddArgs a) {
   for (uint64_t li = blockIdx.x; li < nl; li += gridDim.x) {
     const uint64_t p = min(a.longs[li], a.nprogs - 1);
     uint64_t a0, a1;
-    prog_range(a, p, a0, a1);
+    sgd::csr_range(a.off, p, a.nids, a0, a1);  // program p's ids, clamped to the buffer
     for (uint32_t i = threadIdx.x; i < a.ncalls; i += kPT) hist[i] = 0;
     if (threadIdx.x == 0) nd = 0;
     __syncthreads();

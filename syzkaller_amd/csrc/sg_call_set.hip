@@ -104,11 +104,6 @@ struct CsArgs {
   uint32_t* name_len;
 };
 
-__device__ __forceinline__ void prog_range(const uint64_t* off, uint64_t nbytes, uint64_t p, uint64_t& a0, uint64_t& a1) {
-  a0 = min(off[p], nbytes);
-  a1 = min(max(off[p + 1], a0), nbytes);
-}
-
 // sums[k]: the batch's tiles at shift k beyond one per non-empty program.  That is zero for every program of at
 // most kCsTile << k bytes, so a wave of short programs adds to a few shifts only (each add is an atomic on one
 // address: with all 33 sums added by every wave this kernel took 1.6 ms at 500k programs).  The tiles are at
@@ -119,7 +114,7 @@ __global__ __launch_bounds__(256) void k_cs_lens(const uint64_t* __restrict__ of
   uint64_t len = 0;
   if (p < nprogs) {
     uint64_t a0, a1;
-    prog_range(off, nbytes, p, a0, a1);
+    sgd::csr_range(off, p, nbytes, a0, a1);
     len = a1 - a0;
   }
   uint64_t longest = len;
@@ -149,7 +144,7 @@ __global__ __launch_bounds__(256) void k_cs_ntiles(const uint64_t* __restrict__ 
   if (p == 0) sums[kCsShift] = sh;  // (read by the later launches)
   if (p >= nprogs) return;
   uint64_t a0, a1;
-  prog_range(off, nbytes, p, a0, a1);
+  sgd::csr_range(off, p, nbytes, a0, a1);
   ntile[p] = (uint32_t)((a1 - a0 + ((1ull << sh) - 1)) >> sh);
 }
 
@@ -188,7 +183,7 @@ __global__ __launch_bounds__(kCsBlock) void k_cs_scan(CsArgs a) {
   for (; g < gend; g++) {
     while (p + 1 < a.nprogs && a.tile_off[p + 1] <= g) p++;
     uint64_t a0, a1;
-    prog_range(a.off, a.nbytes, p, a0, a1);
+    sgd::csr_range(a.off, p, a.nbytes, a0, a1);
     const uint64_t t = g - a.tile_off[p];
     const uint64_t tb = a0 + (t << sh);
     if (kEmit && a.status[p] != 0) continue;

@@ -35,6 +35,7 @@
 //
 // No kernel sorts: slot order is output order.  Header lines of inlined
 // helpers are hit from thousands of sites, so every OR tests the bit first.
+#include "sg_rank.h"
 #include "sg_report.h"
 
 #include <algorithm>
@@ -70,11 +71,6 @@ __global__ void k_ct_keys(const uint32_t* __restrict__ file, const uint32_t* __r
   if (i < n) key[i] = ((uint64_t)file[i] << 32) | line[i];
 }
 
-__global__ void k_ct_first(const uint64_t* __restrict__ sorted, uint64_t n, uint32_t* __restrict__ first) {
-  const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < n) first[i] = i == 0 || sorted[i] != sorted[i - 1];
-}
-
 // the distinct keys, ascending, and each slot's line
 __global__ void k_ct_distinct(const uint64_t* __restrict__ sorted, const uint32_t* __restrict__ first,
                               const uint64_t* __restrict__ pos, uint64_t n, uint64_t* __restrict__ dkeys,
@@ -91,14 +87,14 @@ __global__ void k_ct_frame_slot(const uint32_t* __restrict__ file, const uint32_
                                 const uint64_t* __restrict__ dkeys, const uint64_t* __restrict__ pos,
                                 uint32_t* __restrict__ frame_slot) {
   const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < n) frame_slot[i] = (uint32_t)lb64(dkeys, pos[n], ((uint64_t)file[i] << 32) | line[i]);
+  if (i < n) frame_slot[i] = (uint32_t)sgd::lb64(dkeys, pos[n], ((uint64_t)file[i] << 32) | line[i]);
 }
 
 // file f's slots start at the first key >= f << 32 (f == nfiles: all of them)
 __global__ void k_ct_file_off(const uint64_t* __restrict__ dkeys, const uint64_t* __restrict__ pos, uint64_t n,
                               uint32_t nfiles, uint32_t* __restrict__ file_slot_off) {
   const uint64_t f = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (f <= nfiles) file_slot_off[f] = (uint32_t)lb64(dkeys, pos[n], f << 32);
+  if (f <= nfiles) file_slot_off[f] = (uint32_t)sgd::lb64(dkeys, pos[n], f << 32);
 }
 
 // each call site's row of tab (every site is there: checked on the host)
@@ -531,8 +527,7 @@ int sg_cover_table_create(sg_ctx* ctx, const uint64_t* sym_start, const uint64_t
       } else {
         sorted = ka;
       }
-      hipLaunchKernelGGL(k_ct_first, fgrid, dim3(256), 0, ctx->stream, sorted, nfr, fl);
-      if ((rc = scan_counts(ctx, fl, pos, nfr, p.total))) return rc;
+      if ((rc = rank_runs(ctx, sorted, nfr, fl, pos, nullptr, p.total))) return rc;  // (k_ct_distinct writes the keys)
       hipLaunchKernelGGL(k_ct_distinct, fgrid, dim3(256), 0, ctx->stream, sorted, fl, pos, nfr, dk, t->slot_line);
       hipLaunchKernelGGL(k_ct_frame_slot, fgrid, dim3(256), 0, ctx->stream, t->frame_file, li, nfr, dk, pos,
                          t->frame_slot);

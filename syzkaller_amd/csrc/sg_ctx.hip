@@ -814,6 +814,8 @@ int sg_ctx_counter(sg_ctx* ctx, const char* name, uint64_t* out) {
     *out = SG_EXEC_COVER_FAST_CAP;
   else if (!strcmp(name, "cpu_quota_milli"))
     *out = (uint64_t)(ctx->cpu_quota * 1000.0 + 0.5);
+  else if (!strcmp(name, "workspace_bytes"))  // the workspace buffer's capacity (ws_reserve)
+    *out = ctx->ws.cap;
   else {
     set_error("sg_ctx_counter: unknown counter '%s'", name);
     return SG_EINVAL;

@@ -27,11 +27,13 @@
 //  kEcCap distinct records in a table of 2 kEcCap entries.  The first two hold
 //  any call of theirs.  A call with more distinct records than kEcCap (or
 //  whose probe walked the whole table) is flagged, not truncated, and takes the
-// General path (ec_general): order-preserving rank compression with the radix
-// sort, over the flagged calls' records only: distinct arg2 -> rank A;
-// rank(arg1) << 32 | A -> rank B; rank(type) << 32 | B -> rank C; a sort of
-// call << 32 | C, first occurrences; a survivor's triple is read back through
-// the tables of distinct values.  It writes the same workspace triples.
+// General path (ec_general), on the stages of sg_rank.hip: order-preserving
+// rank compression with the radix sort, over the flagged calls' records only:
+// distinct arg2 -> rank A; rank(arg1) << 32 | A -> rank B; rank(type) << 32 | B
+// -> rank C; a sort of call << 32 | C, first occurrences; a survivor's triple
+// is read back through the tables of distinct values.  It writes the same
+// workspace triples.  exec_comps() leaves the choice of the calls, the one read
+// of their count and the workspace's growth to two_path_first (sg_rank.h).
 // scan_counts over the calls' counts gives comp_off and word_off; k_ec_emit, a
 // wave per call, extends the operands (after sort and unique, as the
 // reference) and writes triples and words at those offsets.  The words are the
@@ -41,8 +43,8 @@
 // consumer of the triples is sg_hint_seed.hip; its fused call takes the raw
 // workspace keys (exec_comps with `raw`) and skips k_ec_emit.
 // Every loop is bounded by a count known on entry (records of the call, table
-// entries, sort size, 64 search steps).
-#include "sg_internal.h"
+// entries, sort size).
+#include "sg_rank.h"
 
 namespace sg {
 
@@ -64,13 +66,6 @@ struct EcArgs {
   uint64_t* gbase;           // [ncalls] a flagged call's place among the general path's records
   unsigned long long* scal;  // zeroed: {flagged calls, their records}
 };
-
-// a call's record range, clamped to the batch (the device form cannot check its offsets)
-__device__ __forceinline__ void ec_range(const uint64_t* __restrict__ call_off, uint64_t c, uint64_t nrecs, uint64_t& r0,
-                                         uint64_t& r1) {
-  r0 = min(call_off[c], nrecs);
-  r1 = min(max(call_off[c + 1], r0), nrecs);
-}
 
 __device__ __forceinline__ uint64_t ec_hash(uint64_t t, uint64_t a1, uint64_t a2) {
   uint64_t h = a1 * 0x9E3779B97F4A7C15ull;
@@ -98,7 +93,7 @@ __global__ __launch_bounds__(kThreads) void k_ec_call(EcArgs a) {
   const uint64_t c = blockIdx.x;
   const uint32_t tid = threadIdx.x, lane = tid & 63;
   uint64_t r0, r1;
-  ec_range(a.call_off, c, a.nrecs, r0, r1);
+  sgd::csr_range(a.call_off, c, a.nrecs, r0, r1);
   const uint64_t len = r1 - r0;
   if (len <= a.len_lo || len > a.len_hi) return;  // the other shape's call (or an empty one)
   const uint64_t* __restrict__ rec = a.recs + 4 * r0;
@@ -232,75 +227,11 @@ __global__ __launch_bounds__(kThreads) void k_ec_call(EcArgs a) {
   }
 }
 
-// option exec_comps_path = 0: every call is the general path's, in place
-__global__ void k_ec_flag_all(const uint64_t* __restrict__ call_off, uint64_t ncalls, uint64_t nrecs,
-                              uint8_t* __restrict__ flag, uint64_t* __restrict__ gbase) {
-  const uint64_t c = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (c >= ncalls) return;
-  uint64_t r0, r1;
-  ec_range(call_off, c, nrecs, r0, r1);
-  flag[c] = 1;
-  gbase[c] = r0;
-}
-
-// ---- the general path's kernels ---------------------------------------------
-// a workgroup per call: a flagged call's records get their places
-__global__ __launch_bounds__(256) void k_ec_fill(const uint64_t* __restrict__ call_off, uint64_t nrecs,
-                                                 const uint8_t* __restrict__ flag, const uint64_t* __restrict__ gbase,
-                                                 uint64_t ng, uint32_t* __restrict__ gidx, uint32_t* __restrict__ gcall) {
-  const uint64_t c = blockIdx.x;
-  if (!flag[c]) return;
-  uint64_t r0, r1;
-  ec_range(call_off, c, nrecs, r0, r1);
-  const uint64_t g0 = gbase[c];
-  for (uint64_t k = threadIdx.x; k < r1 - r0; k += 256)
-    if (g0 + k < ng) {
-      gidx[g0 + k] = (uint32_t)(r0 + k);
-      gcall[g0 + k] = (uint32_t)c;
-    }
-}
+// ---- the general path's kernels (the shared stages: sg_rank.hip) ----------------
 __global__ void k_ec_field(const uint64_t* __restrict__ recs, const uint32_t* __restrict__ gidx, uint64_t n,
                            uint32_t field, uint64_t* __restrict__ v, uint64_t* __restrict__ ka) {
   const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i < n) v[i] = ka[i] = recs[4 * (uint64_t)gidx[i] + field];
-}
-__global__ void k_ec_pack(const uint32_t* __restrict__ hi, const uint32_t* __restrict__ lo, uint64_t n,
-                          uint64_t* __restrict__ v, uint64_t* __restrict__ ka) {
-  const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < n) v[i] = ka[i] = ((uint64_t)hi[i] << 32) | lo[i];
-}
-__global__ void k_ec_mark(const uint64_t* __restrict__ a, uint64_t n, uint32_t* __restrict__ flags) {
-  const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < n) flags[i] = i == 0 || a[i] != a[i - 1];
-}
-__global__ void k_ec_unique(const uint64_t* __restrict__ a, const uint32_t* __restrict__ flags,
-                            const uint64_t* __restrict__ pos, uint64_t n, uint64_t* __restrict__ u) {
-  const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < n && flags[i]) u[pos[i]] = a[i];
-}
-// rank[i] = the place of v[i] among the nu distinct values u (ascending)
-__global__ void k_ec_rank(const uint64_t* __restrict__ v, uint64_t n, const uint64_t* __restrict__ u,
-                          const uint64_t* __restrict__ nu_at, uint32_t* __restrict__ rank) {
-  const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n) return;
-  const uint64_t x = v[i];
-  uint64_t lo = 0, hi = min(*nu_at, n);  // first j with u[j] >= x: x is there
-  for (int step = 0; step < 64 && lo < hi; step++) {
-    const uint64_t mid = lo + (hi - lo) / 2;
-    if (u[mid] < x)
-      lo = mid + 1;
-    else
-      hi = mid;
-  }
-  rank[i] = (uint32_t)lo;
-}
-// sorted keys call << 32 | C: the place, among the first occurrences, of each call's first
-__global__ void k_ec_first(const uint64_t* __restrict__ keys, const uint64_t* __restrict__ pos, uint64_t n,
-                           uint64_t ncalls, uint64_t* __restrict__ first) {
-  const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n) return;
-  const uint64_t c = keys[i] >> 32;
-  if (c < ncalls && (i == 0 || (keys[i - 1] >> 32) != c)) first[c] = pos[i];
 }
 struct EcTables {
   const uint64_t *ut, *u1, *u2, *ub, *uc;  // distinct types, arg1, arg2, rank(arg1) << 32 | A, rank(type) << 32 | B
@@ -321,7 +252,7 @@ __global__ void k_ec_gwrite(const uint64_t* __restrict__ keys, const uint32_t* _
   const uint64_t a1 = t.u1[min<uint64_t>(kb >> 32, n - 1)];
   const uint64_t a2 = t.u2[min<uint64_t>((uint32_t)kb, n - 1)];
   uint64_t r0, r1;
-  ec_range(call_off, c, nrecs, r0, r1);
+  sgd::csr_range(call_off, c, nrecs, r0, r1);
   const uint64_t li = pos[i] - first[c];  // < the call's distinct records <= its records
   if (li >= r1 - r0) return;
   uint64_t* dst = tmp + 3 * (r0 + li);
@@ -330,19 +261,6 @@ __global__ void k_ec_gwrite(const uint64_t* __restrict__ keys, const uint32_t* _
   dst[2] = a2;
   atomicAdd(&cnt[c], 1u);
   atomicAdd(&wcnt[c], (typ & 6) == 6 ? 5u : 3u);
-}
-
-// kcov_comparison_t::write's extension (executor.h:632-645)
-__device__ __forceinline__ uint64_t ec_extend(uint64_t typ, uint64_t x) {
-  switch (typ & 6) {
-    case 0:
-      return (uint64_t)(int64_t)(int8_t)x;
-    case 2:
-      return (uint64_t)(int64_t)(int16_t)x;
-    case 4:
-      return (uint64_t)(int64_t)(int32_t)x;
-  }
-  return x;
 }
 
 // a wave per call: the workspace triples, extended, to comps and words
@@ -358,7 +276,7 @@ __global__ __launch_bounds__(256) void k_ec_emit(const uint64_t* __restrict__ ca
   const bool do_words = words && word_off && word_off[ncalls] <= words_cap;
   if (!do_comps && !do_words) return;
   uint64_t r0, r1;
-  ec_range(call_off, c, nrecs, r0, r1);
+  sgd::csr_range(call_off, c, nrecs, r0, r1);
   const uint64_t o0 = comp_off[c], n = min(comp_off[c + 1] - o0, r1 - r0);
   const uint64_t* __restrict__ src = tmp + 3 * r0;
   uint64_t wrun = do_words ? word_off[c] : 0;
@@ -369,8 +287,8 @@ __global__ __launch_bounds__(256) void k_ec_emit(const uint64_t* __restrict__ ca
     uint64_t typ = 0, a1 = 0, a2 = 0;
     if (v) {
       typ = src[3 * i];
-      a1 = ec_extend(typ, src[3 * i + 1]);
-      a2 = ec_extend(typ, src[3 * i + 2]);
+      a1 = sgd::kcov_extend(typ, src[3 * i + 1]);
+      a2 = sgd::kcov_extend(typ, src[3 * i + 2]);
       if (do_comps) {
         comps[3 * (o0 + i)] = typ;
         comps[3 * (o0 + i) + 1] = a1;
@@ -399,64 +317,9 @@ __global__ __launch_bounds__(256) void k_ec_emit(const uint64_t* __restrict__ ca
   }
 }
 
-uint64_t ec_bits_below(uint64_t n) {  // a mask covering 0 .. n - 1
-  uint64_t m = 0;
-  while (n > 1 && m < n - 1) m = (m << 1) | 1;
-  return m;
-}
-
-// v (and its copy in ka) -> the distinct values u, ascending, and each value's rank
-int ec_rank(sg_ctx* ctx, const EcGen& g, uint64_t vary, uint64_t* u, uint32_t* rank) {
-  const dim3 grid(div_up(g.ng, 256)), b(256);
-  uint64_t* sorted = nullptr;
-  int rc = radix_sort_u64(ctx, g.ka, g.kb, g.ng, g.tail, &sorted, vary ? vary : 1);
-  if (rc) return rc;
-  hipLaunchKernelGGL(k_ec_mark, grid, b, 0, ctx->stream, (const uint64_t*)sorted, g.ng, g.flags);
-  rc = scan_counts(ctx, g.flags, g.pos, g.ng, g.tail);
-  if (rc) return rc;
-  hipLaunchKernelGGL(k_ec_unique, grid, b, 0, ctx->stream, (const uint64_t*)sorted, (const uint32_t*)g.flags,
-                     (const uint64_t*)g.pos, g.ng, u);
-  hipLaunchKernelGGL(k_ec_rank, grid, b, 0, ctx->stream, (const uint64_t*)g.v, g.ng, (const uint64_t*)u,
-                     (const uint64_t*)(g.pos + g.ng), rank);
-  SG_HIP(hipGetLastError());
-  return SG_OK;
-}
-
-// gidx / gcall: the record and the call of each of the ng places of the flagged calls (call c's at gbase[c])
-int ec_fill(sg_ctx* ctx, const uint64_t* call_off, uint64_t ncalls, uint64_t nrecs, const uint8_t* flag,
-            const uint64_t* gbase, uint64_t ng, uint32_t* gidx, uint32_t* gcall) {
-  // places never assigned (none, when the counts are consistent) read record 0 of call 0
-  SG_HIP(hipMemsetAsync(gidx, 0, ng * 4, ctx->stream));
-  SG_HIP(hipMemsetAsync(gcall, 0, ng * 4, ctx->stream));
-  hipLaunchKernelGGL(k_ec_fill, dim3((uint32_t)ncalls), dim3(256), 0, ctx->stream, call_off, nrecs, flag, gbase, ng, gidx,
-                     gcall);
-  SG_HIP(hipGetLastError());
-  return SG_OK;
-}
-
-// The sort of call << 32 | rank (*sorted), its first occurrences (g.flags) and their scan (g.pos), and each
-// call's first place among them (first, [ncalls])
-int ec_call_first(sg_ctx* ctx, const EcGen& g, const uint32_t* gcall, const uint32_t* rank, uint64_t ncalls,
-                  uint64_t* first, uint64_t** sorted) {
-  const dim3 grid(div_up(g.ng, 256)), b(256);
-  SG_HIP(hipMemsetAsync(first, 0, ncalls * 8, ctx->stream));
-  hipLaunchKernelGGL(k_ec_pack, grid, b, 0, ctx->stream, gcall, rank, g.ng, g.v, g.ka);
-  const uint64_t kvary = (ec_bits_below(ncalls) << 32) | ec_bits_below(g.ng);
-  int rc = radix_sort_u64(ctx, g.ka, g.kb, g.ng, g.tail, sorted, kvary ? kvary : 1);
-  if (rc) return rc;
-  hipLaunchKernelGGL(k_ec_mark, grid, b, 0, ctx->stream, (const uint64_t*)*sorted, g.ng, g.flags);
-  rc = scan_counts(ctx, g.flags, g.pos, g.ng, g.tail);
-  if (rc) return rc;
-  hipLaunchKernelGGL(k_ec_first, grid, b, 0, ctx->stream, (const uint64_t*)*sorted, (const uint64_t*)g.pos, g.ng, ncalls,
-                     first);
-  SG_HIP(hipGetLastError());
-  return SG_OK;
-}
-
-// ec_general's workspace: five u32 and eight u64 arrays of ng, the scan's ng + 1, a u64 per call
+// ec_general's workspace: four u32 and five u64 arrays of ng and a u64 per call of its own, then the shared stages'
 static size_t ec_general_bytes(uint64_t ng, uint64_t ncalls) {
-  return 5 * align256(ng * 4) + 8 * align256(ng * 8) + align256((ng + 1) * 8) + align256(ncalls * 8) +
-         radix_sort_ws(ng) + scan_ws_bytes(ng) + 4096;
+  return 4 * align256(ng * 4) + 5 * align256(ng * 8) + align256(ncalls * 8) + rank_ws_bytes(ng) + 4096;
 }
 
 // the flagged calls' ng records (places gbase) -> their workspace triples and counts
@@ -465,17 +328,9 @@ static int ec_general(sg_ctx* ctx, const EcArgs& a, uint64_t ng, size_t base) {
   WsPlan p;
   p.total = base;
   const size_t o_gidx = p.add(ng * 4), o_gcall = p.add(ng * 4), o_rlo = p.add(ng * 4), o_rhi = p.add(ng * 4),
-               o_v = p.add(ng * 8), o_ka = p.add(ng * 8), o_kb = p.add(ng * 8), o_pos = p.add((ng + 1) * 8),
                o_ut = p.add(ng * 8), o_u1 = p.add(ng * 8), o_u2 = p.add(ng * 8), o_ub = p.add(ng * 8),
-               o_uc = p.add(ng * 8), o_first = p.add(a.ncalls * 8), o_flags = p.add(ng * 4);
-  EcGen g{};
-  g.ng = ng;
-  g.v = (uint64_t*)ws_at(ctx, o_v);
-  g.ka = (uint64_t*)ws_at(ctx, o_ka);
-  g.kb = (uint64_t*)ws_at(ctx, o_kb);
-  g.pos = (uint64_t*)ws_at(ctx, o_pos);
-  g.flags = (uint32_t*)ws_at(ctx, o_flags);
-  g.tail = p.total;
+               o_uc = p.add(ng * 8), o_first = p.add(a.ncalls * 8);
+  const RankWs g = rank_ws(ctx, p, ng);
   uint32_t* gidx = (uint32_t*)ws_at(ctx, o_gidx);
   uint32_t* gcall = (uint32_t*)ws_at(ctx, o_gcall);
   uint32_t* rlo = (uint32_t*)ws_at(ctx, o_rlo);
@@ -484,25 +339,25 @@ static int ec_general(sg_ctx* ctx, const EcArgs& a, uint64_t ng, size_t base) {
   uint64_t *ut = (uint64_t*)ws_at(ctx, o_ut), *u1 = (uint64_t*)ws_at(ctx, o_u1), *u2 = (uint64_t*)ws_at(ctx, o_u2),
            *ub = (uint64_t*)ws_at(ctx, o_ub), *uc = (uint64_t*)ws_at(ctx, o_uc);
   const dim3 grid(div_up(ng, 256)), b(256);
-  int rc = ec_fill(ctx, a.call_off, a.ncalls, a.nrecs, a.flag, a.gbase, ng, gidx, gcall);
+  int rc = rank_fill(ctx, a.call_off, a.ncalls, a.nrecs, a.flag, a.gbase, ng, gidx, gcall);
   if (rc) return rc;
-  const uint64_t rk = ec_bits_below(ng), packed = (rk << 32) | rk;
+  const uint64_t rk = bits_below(ng), packed = (rk << 32) | rk;
   // 1. distinct arg2 -> A
   hipLaunchKernelGGL(k_ec_field, grid, b, 0, ctx->stream, a.recs, (const uint32_t*)gidx, ng, 2u, g.v, g.ka);
-  if ((rc = ec_rank(ctx, g, ~0ull, u2, rlo))) return rc;
+  if ((rc = rank_values(ctx, g, ~0ull, u2, rlo))) return rc;
   // 2. rank(arg1) << 32 | A -> B
   hipLaunchKernelGGL(k_ec_field, grid, b, 0, ctx->stream, a.recs, (const uint32_t*)gidx, ng, 1u, g.v, g.ka);
-  if ((rc = ec_rank(ctx, g, ~0ull, u1, rhi))) return rc;
-  hipLaunchKernelGGL(k_ec_pack, grid, b, 0, ctx->stream, (const uint32_t*)rhi, (const uint32_t*)rlo, ng, g.v, g.ka);
-  if ((rc = ec_rank(ctx, g, packed, ub, rlo))) return rc;
+  if ((rc = rank_values(ctx, g, ~0ull, u1, rhi))) return rc;
+  if ((rc = rank_pack(ctx, g, rhi, rlo))) return rc;
+  if ((rc = rank_values(ctx, g, packed, ub, rlo))) return rc;
   // 3. rank(type) << 32 | B -> C
   hipLaunchKernelGGL(k_ec_field, grid, b, 0, ctx->stream, a.recs, (const uint32_t*)gidx, ng, 0u, g.v, g.ka);
-  if ((rc = ec_rank(ctx, g, ~0ull, ut, rhi))) return rc;
-  hipLaunchKernelGGL(k_ec_pack, grid, b, 0, ctx->stream, (const uint32_t*)rhi, (const uint32_t*)rlo, ng, g.v, g.ka);
-  if ((rc = ec_rank(ctx, g, packed, uc, rlo))) return rc;
+  if ((rc = rank_values(ctx, g, ~0ull, ut, rhi))) return rc;
+  if ((rc = rank_pack(ctx, g, rhi, rlo))) return rc;
+  if ((rc = rank_values(ctx, g, packed, uc, rlo))) return rc;
   // 4. sort call << 32 | C; 5. first occurrences; 6. the survivors' triples through the tables
   uint64_t* sorted = nullptr;
-  if ((rc = ec_call_first(ctx, g, gcall, rlo, a.ncalls, first, &sorted))) return rc;
+  if ((rc = rank_group_first(ctx, g, gcall, rlo, a.ncalls, first, &sorted))) return rc;
   EcTables t{ut, u1, u2, ub, uc};
   hipLaunchKernelGGL(k_ec_gwrite, grid, b, 0, ctx->stream, (const uint64_t*)sorted, (const uint32_t*)g.flags,
                      (const uint64_t*)g.pos, ng, t, (const uint64_t*)first, a.call_off, a.ncalls, a.nrecs, a.tmp, a.cnt,
@@ -529,8 +384,6 @@ int exec_comps(sg_ctx* ctx, const uint64_t* d_recs, const uint64_t* d_call_off, 
   const size_t o_gbase = p.add(ncalls * 8), o_tmp = p.add(nrecs * 24);
   const size_t scan_a = p.total;
   const size_t need_a = p.total + scan_ws_bytes(ncalls);
-  int rc = ws_reserve(ctx, all_general ? need_a + ec_general_bytes(nrecs, ncalls) : need_a);
-  if (rc) return rc;
   EcArgs a{};
   a.recs = d_recs;
   a.call_off = d_call_off;
@@ -544,54 +397,30 @@ int exec_comps(sg_ctx* ctx, const uint64_t* d_recs, const uint64_t* d_call_off, 
     a.gbase = (uint64_t*)ws_at(ctx, o_gbase);
     a.tmp = (uint64_t*)ws_at(ctx, o_tmp);
     SG_HIP(hipMemsetAsync(ws_at(ctx, 0), 0, zeroed, ctx->stream));
-    if (all_general) {
-      hipLaunchKernelGGL(k_ec_flag_all, dim3(div_up(ncalls, 256)), dim3(256), 0, ctx->stream, d_call_off, ncalls, nrecs,
-                         a.flag, a.gbase);
-    } else {
-      ScopedTimer tm(ctx, "exec_comps_call");
-      a.len_lo = 0;
-      a.len_hi = kEcSmall;
-      hipLaunchKernelGGL((k_ec_call<256, kEcSmall>), dim3((uint32_t)ncalls), dim3(256), 0, ctx->stream, a);
-      if (nrecs > kEcSmall) {
-        a.len_lo = kEcSmall;
-        a.len_hi = kEcMid;
-        hipLaunchKernelGGL((k_ec_call<kEcMidThreads, kEcMid>), dim3((uint32_t)ncalls), dim3(kEcMidThreads), 0,
-                           ctx->stream, a);
-      }
-      if (nrecs > kEcMid) {
-        a.len_lo = kEcMid;
-        a.len_hi = ~0ull;
-        hipLaunchKernelGGL((k_ec_call<1024, kEcCap>), dim3((uint32_t)ncalls), dim3(1024), 0, ctx->stream, a);
-      }
+    if (all_general) return rank_flag_all(ctx, d_call_off, ncalls, nrecs, nullptr, a.flag, a.gbase, a.scal);
+    ScopedTimer tm(ctx, "exec_comps_call");
+    a.len_lo = 0;
+    a.len_hi = kEcSmall;
+    hipLaunchKernelGGL((k_ec_call<256, kEcSmall>), dim3((uint32_t)ncalls), dim3(256), 0, ctx->stream, a);
+    if (nrecs > kEcSmall) {
+      a.len_lo = kEcSmall;
+      a.len_hi = kEcMid;
+      hipLaunchKernelGGL((k_ec_call<kEcMidThreads, kEcMid>), dim3((uint32_t)ncalls), dim3(kEcMidThreads), 0, ctx->stream,
+                         a);
+    }
+    if (nrecs > kEcMid) {
+      a.len_lo = kEcMid;
+      a.len_hi = ~0ull;
+      hipLaunchKernelGGL((k_ec_call<1024, kEcCap>), dim3((uint32_t)ncalls), dim3(1024), 0, ctx->stream, a);
     }
     SG_HIP(hipGetLastError());
     return SG_OK;
   };
-  rc = first_pass();
-  if (rc) return rc;
+  const TwoPath tp{all_general, false, ncalls, nrecs, kEcCap, need_a, o_scal};
   uint64_t ng = 0;
-  if (all_general) {
-    ng = nrecs;
-    ctx->exec_comps_general = ncalls;
-  } else if (nrecs > kEcCap) {
-    // the one device-to-host read (16 B, one wait): the flagged calls' records
-    // size the general path's workspace.  No call of a batch of at most kEcCap
-    // records can be flagged: such a batch is read by nobody.
-    unsigned long long got[2] = {0, 0};
-    SG_HIP(hipMemcpyAsync(got, a.scal, sizeof(got), hipMemcpyDeviceToHost, ctx->stream));
-    SG_HIP(hipStreamSynchronize(ctx->stream));
-    ctx->exec_comps_general = got[0];
-    ng = got[1] <= nrecs ? got[1] : nrecs;
-    if (ng) {
-      const void* ws_before = ctx->ws.p;
-      rc = ws_reserve(ctx, need_a + ec_general_bytes(ng, ncalls));
-      if (rc) return rc;
-      if (ctx->ws.p != ws_before) {  // the workspace moved: the first pass went with it
-        rc = first_pass();
-        if (rc) return rc;
-      }
-    }
-  }
+  int rc = two_path_first(ctx, tp, first_pass, [&](uint64_t n) { return ec_general_bytes(n, ncalls); },
+                          &ctx->exec_comps_general, &ng);
+  if (rc) return rc;
   if (ng) {
     rc = ec_general(ctx, a, ng, need_a);
     if (rc) return rc;

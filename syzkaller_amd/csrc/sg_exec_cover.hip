@@ -29,16 +29,17 @@
 //  The first two hold any call of theirs.  A call with more distinct PCs than
 //  kXcCap (or whose probe walked the whole table) is flagged, not truncated,
 //  and takes the
-// General path (xc_general), over the flagged calls' PCs only, on the stages
-// sg_exec_comps.hip shares: the radix sort gives the distinct values U and a
-// binary search each PC's rank in U; a sort of call << 32 | rank, its first
-// occurrences and their scan give each survivor its place; (uint32_t)U[rank]
-// goes to the same workspace slots.
+// General path (xc_general), over the flagged calls' PCs only, on the stages of
+// sg_rank.hip: the radix sort gives the distinct values U and a binary search
+// each PC's rank in U; a sort of call << 32 | rank, its first occurrences and
+// their scan give each survivor its place; (uint32_t)U[rank] goes to the same
+// workspace slots.  exec_cover() leaves the choice of the calls, the one read of
+// their count and the workspace's growth to two_path_first (sg_rank.h).
 // scan_counts over the calls' counts gives cov_off; k_xc_emit, a wave per call,
 // packs the lists at those offsets and checks the capacity on the device.
 // Every loop is bounded by a count known on entry (PCs of the call, table
-// entries, sort size, 64 search steps).
-#include "sg_internal.h"
+// entries, sort size).
+#include "sg_rank.h"
 
 #include <algorithm>
 
@@ -64,13 +65,6 @@ struct XcArgs {
   unsigned long long* scal;  // zeroed: {flagged calls, their PCs}
 };
 
-// a call's PC range, clamped to the batch (the device form cannot check its offsets)
-__device__ __forceinline__ void xc_range(const uint64_t* __restrict__ call_off, uint64_t c, uint64_t npcs, uint64_t& r0,
-                                         uint64_t& r1) {
-  r0 = min(call_off[c], npcs);
-  r1 = min(max(call_off[c + 1], r0), npcs);
-}
-
 __device__ __forceinline__ uint32_t xc_hash(uint64_t pc) {
   uint64_t h = pc * 0x9E3779B97F4A7C15ull;
   h ^= h >> 29;
@@ -88,7 +82,7 @@ __global__ __launch_bounds__(kThreads) void k_xc_call(XcArgs a) {
   const uint64_t c = blockIdx.x;
   const uint32_t tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
   uint64_t r0, r1;
-  xc_range(a.call_off, c, a.npcs, r0, r1);
+  sgd::csr_range(a.call_off, c, a.npcs, r0, r1);
   const uint64_t len = r1 - r0;
   if (len <= a.len_lo || len > a.len_hi) return;  // the other shape's call (or an empty one)
   if (a.sel && !a.sel[c]) return;
@@ -200,26 +194,7 @@ __global__ __launch_bounds__(kThreads) void k_xc_call(XcArgs a) {
   }
 }
 
-// option exec_cover_path = 0: every call is the general path's, in place; with
-// sel, every selected call, at a place taken as the fast shape's flagged calls take theirs
-__global__ void k_xc_flag_all(const uint64_t* __restrict__ call_off, uint64_t ncalls, uint64_t npcs,
-                              const uint8_t* __restrict__ sel, uint8_t* __restrict__ flag, uint64_t* __restrict__ gbase,
-                              unsigned long long* __restrict__ scal) {
-  const uint64_t c = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (c >= ncalls) return;
-  uint64_t r0, r1;
-  xc_range(call_off, c, npcs, r0, r1);
-  if (!sel) {
-    flag[c] = 1;
-    gbase[c] = r0;
-  } else if (sel[c] && r1 > r0) {
-    flag[c] = 1;
-    gbase[c] = atomicAdd(&scal[1], (unsigned long long)(r1 - r0));
-    atomicAdd(&scal[0], 1ull);
-  }
-}
-
-// ---- the general path's kernels ---------------------------------------------
+// ---- the general path's kernels (the shared stages: sg_rank.hip) ----------------
 __global__ void k_xc_gather(const uint64_t* __restrict__ pcs, const uint32_t* __restrict__ gidx, uint64_t n,
                             uint64_t* __restrict__ v, uint64_t* __restrict__ ka) {
   const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -235,7 +210,7 @@ __global__ void k_xc_gwrite(const uint64_t* __restrict__ keys, const uint32_t* _
   const uint64_t c = keys[i] >> 32;
   if (c >= ncalls) return;
   uint64_t r0, r1;
-  xc_range(call_off, c, npcs, r0, r1);
+  sgd::csr_range(call_off, c, npcs, r0, r1);
   const uint64_t li = pos[i] - first[c];  // < the call's distinct PCs <= its PCs
   if (li >= r1 - r0) return;
   tmp[r0 + li] = (uint32_t)u[min<uint64_t>((uint32_t)keys[i], n - 1)];  // (a rank is below n: U holds n entries)
@@ -261,7 +236,7 @@ __global__ __launch_bounds__(256) void k_xc_emit(const uint64_t* __restrict__ ca
   if (c >= ncalls || cov_off[ncalls] > cov_cap) return;
   const uint32_t lane = threadIdx.x & 63;
   uint64_t r0, r1;
-  xc_range(call_off, c, npcs, r0, r1);
+  sgd::csr_range(call_off, c, npcs, r0, r1);
   const uint64_t o0 = cov_off[c], n = min(cov_off[c + 1] - o0, r1 - r0);
   // four loads per lane in flight before their stores
   for (uint64_t i0 = 0; i0 < n; i0 += 256) {
@@ -279,10 +254,9 @@ __global__ __launch_bounds__(256) void k_xc_emit(const uint64_t* __restrict__ ca
   }
 }
 
-// xc_general's workspace: four u32 and four u64 arrays of ng, the scan's ng + 1, a u64 per call
+// xc_general's workspace: three u32 arrays and one u64 array of ng and a u64 per call of its own, then the shared stages'
 static size_t xc_general_bytes(uint64_t ng, uint64_t ncalls) {
-  return 4 * align256(ng * 4) + 4 * align256(ng * 8) + align256((ng + 1) * 8) + align256(ncalls * 8) +
-         radix_sort_ws(ng) + scan_ws_bytes(ng) + 4096;
+  return 3 * align256(ng * 4) + align256(ng * 8) + align256(ncalls * 8) + rank_ws_bytes(ng) + 4096;
 }
 
 // the flagged calls' ng PCs (places gbase) -> their workspace lists and counts
@@ -290,31 +264,23 @@ static int xc_general(sg_ctx* ctx, const XcArgs& a, uint64_t ng, size_t base) {
   ScopedTimer tm(ctx, "exec_cover_general");
   WsPlan p;
   p.total = base;
-  const size_t o_gidx = p.add(ng * 4), o_gcall = p.add(ng * 4), o_rank = p.add(ng * 4), o_v = p.add(ng * 8),
-               o_ka = p.add(ng * 8), o_kb = p.add(ng * 8), o_pos = p.add((ng + 1) * 8), o_u = p.add(ng * 8),
-               o_first = p.add(a.ncalls * 8), o_flags = p.add(ng * 4);
-  EcGen g{};
-  g.ng = ng;
-  g.v = (uint64_t*)ws_at(ctx, o_v);
-  g.ka = (uint64_t*)ws_at(ctx, o_ka);
-  g.kb = (uint64_t*)ws_at(ctx, o_kb);
-  g.pos = (uint64_t*)ws_at(ctx, o_pos);
-  g.flags = (uint32_t*)ws_at(ctx, o_flags);
-  g.tail = p.total;
+  const size_t o_gidx = p.add(ng * 4), o_gcall = p.add(ng * 4), o_rank = p.add(ng * 4), o_u = p.add(ng * 8),
+               o_first = p.add(a.ncalls * 8);
+  const RankWs g = rank_ws(ctx, p, ng);
   uint32_t* gidx = (uint32_t*)ws_at(ctx, o_gidx);
   uint32_t* gcall = (uint32_t*)ws_at(ctx, o_gcall);
   uint32_t* rank = (uint32_t*)ws_at(ctx, o_rank);
   uint64_t* u = (uint64_t*)ws_at(ctx, o_u);
   uint64_t* first = (uint64_t*)ws_at(ctx, o_first);
   const dim3 grid(div_up(ng, 256)), b(256);
-  int rc = ec_fill(ctx, a.call_off, a.ncalls, a.npcs, a.flag, a.gbase, ng, gidx, gcall);
+  int rc = rank_fill(ctx, a.call_off, a.ncalls, a.npcs, a.flag, a.gbase, ng, gidx, gcall);
   if (rc) return rc;
   // 1. the distinct PCs U and each PC's rank in U
   hipLaunchKernelGGL(k_xc_gather, grid, b, 0, ctx->stream, a.pcs, (const uint32_t*)gidx, ng, g.v, g.ka);
-  if ((rc = ec_rank(ctx, g, ~0ull, u, rank))) return rc;
+  if ((rc = rank_values(ctx, g, ~0ull, u, rank))) return rc;
   // 2. sort call << 32 | rank; 3. first occurrences and their scan; 4. (uint32_t)U[rank]
   uint64_t* sorted = nullptr;
-  if ((rc = ec_call_first(ctx, g, gcall, rank, a.ncalls, first, &sorted))) return rc;
+  if ((rc = rank_group_first(ctx, g, gcall, rank, a.ncalls, first, &sorted))) return rc;
   hipLaunchKernelGGL(k_xc_gwrite, grid, b, 0, ctx->stream, (const uint64_t*)sorted, (const uint32_t*)g.flags,
                      (const uint64_t*)g.pos, ng, (const uint64_t*)u, (const uint64_t*)first, a.call_off, a.ncalls,
                      a.npcs, a.tmp, a.cnt);
@@ -345,8 +311,6 @@ int exec_cover(sg_ctx* ctx, const uint64_t* d_pcs, const uint64_t* d_call_off, u
   const size_t o_gbase = p.add(ncalls * 8), o_tmp = p.add(npcs * 4);
   const size_t scan_a = p.total;
   const size_t need_a = p.total + scan_ws_bytes(ncalls);
-  int rc = ws_reserve(ctx, all_general ? need_a + xc_general_bytes(npcs, ncalls) : need_a);
-  if (rc) return rc;
   XcArgs a{};
   a.pcs = d_pcs;
   a.call_off = d_call_off;
@@ -360,54 +324,30 @@ int exec_cover(sg_ctx* ctx, const uint64_t* d_pcs, const uint64_t* d_call_off, u
     a.gbase = (uint64_t*)ws_at(ctx, o_gbase);
     a.tmp = (uint32_t*)ws_at(ctx, o_tmp);
     SG_HIP(hipMemsetAsync(ws_at(ctx, 0), 0, zeroed, ctx->stream));
-    if (all_general) {
-      hipLaunchKernelGGL(k_xc_flag_all, dim3(div_up(ncalls, 256)), dim3(256), 0, ctx->stream, d_call_off, ncalls, npcs,
-                         sel, a.flag, a.gbase, a.scal);
-    } else {
-      ScopedTimer tm(ctx, "exec_cover_call");
-      a.len_lo = 0;
-      a.len_hi = kXcSmall;
-      hipLaunchKernelGGL((k_xc_call<256, kXcSmall>), dim3((uint32_t)ncalls), dim3(256), 0, ctx->stream, a);
-      if (npcs > kXcSmall) {
-        a.len_lo = kXcSmall;
-        a.len_hi = kXcMid;
-        hipLaunchKernelGGL((k_xc_call<kXcMidThreads, kXcMid>), dim3((uint32_t)ncalls), dim3(kXcMidThreads), 0,
-                           ctx->stream, a);
-      }
-      if (npcs > kXcMid) {
-        a.len_lo = kXcMid;
-        a.len_hi = ~0ull;
-        hipLaunchKernelGGL((k_xc_call<1024, kXcCap>), dim3((uint32_t)ncalls), dim3(1024), 0, ctx->stream, a);
-      }
+    if (all_general) return rank_flag_all(ctx, d_call_off, ncalls, npcs, sel, a.flag, a.gbase, a.scal);
+    ScopedTimer tm(ctx, "exec_cover_call");
+    a.len_lo = 0;
+    a.len_hi = kXcSmall;
+    hipLaunchKernelGGL((k_xc_call<256, kXcSmall>), dim3((uint32_t)ncalls), dim3(256), 0, ctx->stream, a);
+    if (npcs > kXcSmall) {
+      a.len_lo = kXcSmall;
+      a.len_hi = kXcMid;
+      hipLaunchKernelGGL((k_xc_call<kXcMidThreads, kXcMid>), dim3((uint32_t)ncalls), dim3(kXcMidThreads), 0, ctx->stream,
+                         a);
+    }
+    if (npcs > kXcMid) {
+      a.len_lo = kXcMid;
+      a.len_hi = ~0ull;
+      hipLaunchKernelGGL((k_xc_call<1024, kXcCap>), dim3((uint32_t)ncalls), dim3(1024), 0, ctx->stream, a);
     }
     SG_HIP(hipGetLastError());
     return SG_OK;
   };
-  rc = first_pass();
-  if (rc) return rc;
+  const TwoPath tp{all_general, sel != nullptr, ncalls, npcs, kXcCap, need_a, o_scal};
   uint64_t ng = 0;
-  if (all_general && !sel) {
-    ng = npcs;
-    ctx->exec_cover_general = ncalls;
-  } else if (all_general || npcs > kXcCap) {
-    // the one device-to-host read (16 B, one wait): the flagged calls' PCs size
-    // the general path's workspace.  No call of a batch of at most kXcCap PCs
-    // can be flagged: such a batch is read by nobody.
-    unsigned long long got[2] = {0, 0};
-    SG_HIP(hipMemcpyAsync(got, a.scal, sizeof(got), hipMemcpyDeviceToHost, ctx->stream));
-    SG_HIP(hipStreamSynchronize(ctx->stream));
-    ctx->exec_cover_general = got[0];
-    ng = got[1] <= npcs ? got[1] : npcs;
-    if (ng) {
-      const void* ws_before = ctx->ws.p;
-      rc = ws_reserve(ctx, need_a + xc_general_bytes(ng, ncalls));
-      if (rc) return rc;
-      if (ctx->ws.p != ws_before) {  // the workspace moved: the first pass went with it
-        rc = first_pass();
-        if (rc) return rc;
-      }
-    }
-  }
+  int rc = two_path_first(ctx, tp, first_pass, [&](uint64_t n) { return xc_general_bytes(n, ncalls); },
+                          &ctx->exec_cover_general, &ng);
+  if (rc) return rc;
   if (ng) {
     rc = xc_general(ctx, a, ng, need_a);
     if (rc) return rc;

@@ -36,33 +36,21 @@ struct CpArgs {
 
 // call c's triples: src + 3 * r0, n of them
 __device__ __forceinline__ void cp_range(const CpArgs& a, uint64_t c, uint64_t& r0, uint64_t& n) {
-  r0 = min(a.src_off[c], a.nsrc);
-  n = min(max(a.src_off[c + 1], r0), a.nsrc) - r0;
+  uint64_t r1;
+  sgd::csr_range(a.src_off, c, a.nsrc, r0, r1);
+  n = r1 - r0;
   if (a.cnt_off) {
     const uint64_t o0 = a.cnt_off[c], o1 = a.cnt_off[c + 1];
     n = min(n, o1 > o0 ? o1 - o0 : 0);
   }
 }
 
-// kcov_comparison_t::write's extension (executor.h:632-645)
-__device__ __forceinline__ uint64_t cp_extend(uint64_t typ, uint64_t x) {
-  switch (typ & 6) {
-    case 0:
-      return (uint64_t)(int64_t)(int8_t)x;
-    case 2:
-      return (uint64_t)(int64_t)(int16_t)x;
-    case 4:
-      return (uint64_t)(int64_t)(int32_t)x;
-  }
-  return x;
-}
-
 // triple i of a call: its AddComp calls (0, 1 or 2) and its operands
 __device__ __forceinline__ uint32_t cp_pairs(const uint64_t* __restrict__ t, uint64_t i, uint64_t& typ, uint64_t& op1,
                                              uint64_t& op2) {
   typ = t[3 * i];
-  op1 = cp_extend(typ, t[3 * i + 1]);
-  op2 = cp_extend(typ, t[3 * i + 2]);
+  op1 = sgd::kcov_extend(typ, t[3 * i + 1]);
+  op2 = sgd::kcov_extend(typ, t[3 * i + 2]);
   if (typ > 7 || op1 == op2) return 0;  // ipc_linux.go:266-270 (the call fails), :290-293
   return (typ & 1) ? 1u : 2u;           // :294-302: (op2, op1), and (op1, op2) unless one operand was const
 }

@@ -21,11 +21,12 @@
 //    <= 1/2), the record's pairs streamed against it (records of at most 64
 //    slots: one tile in a 1024-entry table); counted in one pass, appended in
 //    a second;
-//  - radix sorts: the candidates' replacers -> the distinct replacers U; then
-//    the keys (slot << 32 | rank in U) -> first occurrences -> rep_off, reps.
+//  - radix sorts (the distinct-values stage is sg_rank.hip's): the candidates'
+//    replacers -> the distinct replacers U; then the keys (slot << 32 | rank in
+//    U) -> first occurrences -> rep_off, reps.
 // Every loop is bounded by a count known on entry (region words, table
-// capacity, pair count).
-#include "sg_internal.h"
+// capacity, pair count) or halves its interval (sgd::lb64).
+#include "sg_rank.h"
 
 namespace sg {
 
@@ -501,32 +502,15 @@ __global__ __launch_bounds__(kHjThreads) void k_hints_join(JoinArgs a) {
   }
 }
 
-// flags[i] = 1 where a[i] starts a run of equal keys (a sorted)
-__global__ void k_hj_mark(const uint64_t* __restrict__ a, uint64_t n, uint32_t* __restrict__ flags) {
-  const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < n) flags[i] = i == 0 || a[i] != a[i - 1];
-}
-__global__ void k_hj_unique(const uint64_t* __restrict__ a, const uint32_t* __restrict__ flags,
-                            const uint64_t* __restrict__ pos, uint64_t n, uint64_t* __restrict__ u) {
-  const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < n && flags[i]) u[pos[i]] = a[i];
-}
-// keys[i] = slot << 32 | rank of candidate i's replacer among the nu distinct ones
+// keys[i] = slot << 32 | rank of candidate i's replacer among the nu distinct ones: the rank and the
+// pack in one kernel (sg_rank.hip's rank, then its pack, would be a launch and an array more)
 __global__ void k_hj_rank(const uint32_t* __restrict__ cslot, const uint64_t* __restrict__ crep, uint64_t n,
                           const uint64_t* __restrict__ u, const uint64_t* __restrict__ nu_at,
                           uint64_t* __restrict__ keys) {
   const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
-  const uint64_t x = crep[i];
-  uint64_t lo = 0, hi = *nu_at;  // first j with u[j] >= x: x is there
-  for (int step = 0; step < 64 && lo < hi; step++) {
-    const uint64_t mid = lo + (hi - lo) / 2;
-    if (u[mid] < x)
-      lo = mid + 1;
-    else
-      hi = mid;
-  }
-  keys[i] = ((uint64_t)cslot[i] << 32) | (uint32_t)lo;
+  // the first j with u[j] >= crep[i]: the replacer is there
+  keys[i] = ((uint64_t)cslot[i] << 32) | (uint32_t)sgd::lb64(u, *nu_at, crep[i]);
 }
 __global__ void k_hj_slot_count(const uint64_t* __restrict__ keys, const uint32_t* __restrict__ flags, uint64_t n,
                                 uint32_t* __restrict__ scnt) {
@@ -550,12 +534,6 @@ static void join_launch(sg_ctx* ctx, JoinArgs a) {
   a.nv_lo = kHjSmall;
   a.nv_hi = ~0ull;
   hipLaunchKernelGGL((k_hints_join<EMIT, 1024, kHjTile>), dim3((uint32_t)a.nrec), dim3(1024), 0, ctx->stream, a);
-}
-
-static uint64_t bits_below(uint64_t n) {  // a mask covering 0 .. n - 1
-  uint64_t m = 0;
-  while (m < n - 1 && m != ~0ull) m = (m << 1) | 1;
-  return n > 1 ? m : 0;
 }
 
 // The join and the sorts behind sg_hints_replacers* and sg_hints_from_kcov*
@@ -631,13 +609,8 @@ int hints_replacers(sg_ctx* ctx, const uint64_t* d_pair_off, const uint64_t* d_p
                o_reps = p.add(wcap * 8);
   const size_t tail = p.total;
   const size_t scan_n = nc > nvals ? nc : nvals;
-  const void* ws_before = ctx->ws.p;
-  rc = ws_reserve(ctx, tail + radix_sort_ws(nc) + scan_ws_bytes(scan_n) + need_a);
+  rc = ws_reserve_redo(ctx, tail + radix_sort_ws(nc) + scan_ws_bytes(scan_n) + need_a, count);  // (the counts, again)
   if (rc) return rc;
-  if (ctx->ws.p != ws_before) {  // the workspace moved: the counts went with it
-    rc = count();
-    if (rc) return rc;
-  }
   a.cand_off = (const uint64_t*)ws_at(ctx, o_coff);
   a.cslot = (uint32_t*)ws_at(ctx, o_cslot);
   a.crep = (uint64_t*)ws_at(ctx, o_crep);
@@ -663,11 +636,7 @@ int hints_replacers(sg_ctx* ctx, const uint64_t* d_pair_off, const uint64_t* d_p
     const uint64_t vary = r_and ^ r_or;  // the bits that differ between replacers
     rc = radix_sort_u64(ctx, ka, kb, nc, tail, &sorted, vary ? vary : 1);
     if (rc) return rc;
-    hipLaunchKernelGGL(k_hj_mark, g, b, 0, ctx->stream, (const uint64_t*)sorted, nc, flags);
-    rc = scan_counts(ctx, flags, pos, nc, tail);
-    if (rc) return rc;
-    hipLaunchKernelGGL(k_hj_unique, g, b, 0, ctx->stream, (const uint64_t*)sorted, (const uint32_t*)flags,
-                       (const uint64_t*)pos, nc, u);
+    if ((rc = rank_runs(ctx, sorted, nc, flags, pos, u, tail))) return rc;
     // 2. each candidate's rank; 3. sort (slot, rank)
     hipLaunchKernelGGL(k_hj_rank, g, b, 0, ctx->stream, (const uint32_t*)a.cslot, (const uint64_t*)a.crep, nc,
                        (const uint64_t*)u, (const uint64_t*)(pos + nc), ka);
@@ -676,11 +645,9 @@ int hints_replacers(sg_ctx* ctx, const uint64_t* d_pair_off, const uint64_t* d_p
     rc = radix_sort_u64(ctx, ka, kb, nc, tail, &sorted, kvary ? kvary : 1);
     if (rc) return rc;
     // 4. first occurrences -> rep_off; 5. reps = U[rank]
-    hipLaunchKernelGGL(k_hj_mark, g, b, 0, ctx->stream, (const uint64_t*)sorted, nc, flags);
+    if ((rc = rank_runs(ctx, sorted, nc, flags, pos, nullptr, tail))) return rc;
     SG_HIP(hipMemsetAsync(scnt, 0, nvals * 4, ctx->stream));
     hipLaunchKernelGGL(k_hj_slot_count, g, b, 0, ctx->stream, (const uint64_t*)sorted, (const uint32_t*)flags, nc, scnt);
-    rc = scan_counts(ctx, flags, pos, nc, tail);
-    if (rc) return rc;
     rc = scan_counts(ctx, scnt, d_rep_off, nvals, tail);
     if (rc) return rc;
     if (reps)

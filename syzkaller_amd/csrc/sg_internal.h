@@ -402,27 +402,6 @@ constexpr uint32_t kSha1Long = SG_SHA1_LONG;
 // read by sg_ctx_counter as "triage_runs_sort_cap" and "tinput_chunk"
 constexpr uint32_t kTrSort = 8192;    // values the cover fold sorts in LDS (64 KiB of keys)
 constexpr uint32_t kTinChunk = 8192;  // values of a per LDS chunk of tin_intersect (32 KiB)
-// Stages of the general path that sg_exec_cover.hip shares (sg_exec_comps.hip;
-// ctx lock held).  EcGen: ng values in v with a copy in ka, a second key buffer
-// kb, pos [ng + 1], flags [ng], and the workspace past `tail` for the sort and
-// the scan.  ec_rank: v -> its distinct values u, ascending (their number at
-// pos[ng]), and each value's rank among them.  ec_fill: the member (gidx) and
-// the call (gcall) of each of the ng places of the flagged calls, call c's
-// from gbase[c].  ec_call_first: the sort of gcall << 32 | rank (*sorted), its
-// first occurrences (flags) with their scan (pos), and each call's first
-// place among them (first, [ncalls]).
-struct EcGen {
-  uint64_t ng;
-  uint64_t *v, *ka, *kb, *pos;
-  uint32_t* flags;
-  size_t tail;
-};
-uint64_t ec_bits_below(uint64_t n);
-int ec_rank(sg_ctx* ctx, const EcGen& g, uint64_t vary, uint64_t* u, uint32_t* rank);
-int ec_fill(sg_ctx* ctx, const uint64_t* call_off, uint64_t ncalls, uint64_t nrecs, const uint8_t* flag,
-            const uint64_t* gbase, uint64_t ng, uint32_t* gidx, uint32_t* gcall);
-int ec_call_first(sg_ctx* ctx, const EcGen& g, const uint32_t* gcall, const uint32_t* rank, uint64_t ncalls,
-                  uint64_t* first, uint64_t** sorted);
 // Canonicalize of device segments in place: off (host, nseg + 1), out_len
 // (host) the canonical lengths; and the batched merge of device-resident
 // lists, pair k da[a_beg[k] .. + a_len[k]) op db[b_beg[k] .. + b_len[k]) into
@@ -531,6 +510,54 @@ __device__ __forceinline__ bool test_bit(const uint32_t* words, uint32_t s) {
 }
 __device__ __forceinline__ void set_bit(uint32_t* words, uint32_t s) {
   atomicOr(&words[set_pos(s) >> 5], 1u << (s & 31));
+}
+
+// List i of a CSR over `total` members, clamped to them: r0 <= r1 <= total
+// whatever off holds.  A device form's offsets are checked by nobody, and this
+// is what keeps it inside its buffers.
+__device__ __forceinline__ void csr_range(const uint64_t* off, uint64_t i, uint64_t total, uint64_t& r0,
+                                          uint64_t& r1) {
+  r0 = min(off[i], total);
+  r1 = min(max(off[i + 1], r0), total);
+}
+
+// kcov_comparison_t::write's extension of an operand (executor/executor.h:632-645)
+__device__ __forceinline__ uint64_t kcov_extend(uint64_t typ, uint64_t x) {
+  switch (typ & 6) {
+    case 0:
+      return (uint64_t)(int64_t)(int8_t)x;
+    case 2:
+      return (uint64_t)(int64_t)(int16_t)x;
+    case 4:
+      return (uint64_t)(int64_t)(int32_t)x;
+  }
+  return x;
+}
+
+// The first j in [0, n] with a[j] >= v (lb64) or a[j] > v (ub64), a ascending.
+// The interval halves on every iteration whatever the array holds, sorted or
+// not, so either loop ends within 64 steps without a counter of its own.
+__device__ __forceinline__ uint64_t lb64(const uint64_t* a, uint64_t n, uint64_t v) {
+  uint64_t lo = 0, hi = n;
+  while (lo < hi) {
+    uint64_t mid = (lo + hi) >> 1;
+    if (a[mid] < v)
+      lo = mid + 1;
+    else
+      hi = mid;
+  }
+  return lo;
+}
+__device__ __forceinline__ uint64_t ub64(const uint64_t* a, uint64_t n, uint64_t v) {
+  uint64_t lo = 0, hi = n;
+  while (lo < hi) {
+    uint64_t mid = (lo + hi) >> 1;
+    if (a[mid] <= v)
+      lo = mid + 1;
+    else
+      hi = mid;
+  }
+  return lo;
 }
 
 // largest r in [lo, hi] with off[r] <= i (off non-decreasing), searched in

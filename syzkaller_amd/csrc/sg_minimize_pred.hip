@@ -48,7 +48,8 @@ __global__ __launch_bounds__(kTB) void k_mp_pred(PredArgs a) {
   __shared__ IntersectLds lds;
   const uint64_t e = blockIdx.x;
   const uint64_t k = min<uint64_t>(a.cand[e], a.ncand - 1);
-  const uint64_t a0 = min(a.new_off[k], a.nnew), a1 = min(max(a.new_off[k + 1], a0), a.nnew);
+  uint64_t a0, a1;
+  sgd::csr_range(a.new_off, k, a.nnew, a0, a1);
   const uint32_t c = a.selcall[e];
   const uint64_t r0 = c == kNoCall ? 0 : a.xsig_off[c], r1 = c == kNoCall ? 0 : a.xsig_off[c + 1];
   int32_t st = SG_MP_NOT_EXECUTED;  // :580-582

@@ -44,6 +44,14 @@ inline size_t grow_cap(size_t cap, size_t need, size_t floor) {
   return nc;
 }
 
+// A mask covering 0 .. n - 1, for the radix sort's `vary` over keys below n: 0
+// for n <= 1, else the smallest 2^k - 1 that is >= n - 1.
+inline uint64_t bits_below(uint64_t n) {
+  uint64_t m = 0;
+  while (n > 1 && m < n - 1) m = (m << 1) | 1;  // (ends: all ones is >= any n - 1)
+  return m;
+}
+
 // CSR offsets of n lists: off[0] == 0 and non-decreasing up to off[n].
 inline bool offsets_ok(const uint64_t* off, size_t n) {
   if (off[0] != 0) return false;

@@ -61,8 +61,8 @@ struct HashArgs {
 
 // program p's bytes, clamped to the buffer: base[beg, beg + len)
 __device__ __forceinline__ void text_range(const HashArgs& a, uint64_t p, uint64_t& beg, uint64_t& len) {
-  const uint64_t a0 = min(a.off[p], a.nbytes);
-  const uint64_t a1 = min(max(a.off[p + 1], a0), a.nbytes);
+  uint64_t a0, a1;
+  sgd::csr_range(a.off, p, a.nbytes, a0, a1);
   beg = a.lo + a0;
   len = a1 - a0;
 }
@@ -73,8 +73,8 @@ __global__ __launch_bounds__(256) void k_sha1_keys(const uint64_t* __restrict__ 
                                                     uint64_t* __restrict__ keys) {
   const uint64_t p = (uint64_t)blockIdx.x * 256 + threadIdx.x;
   if (p >= nprogs) return;
-  const uint64_t a0 = min(off[p], nbytes);
-  const uint64_t a1 = min(max(off[p + 1], a0), nbytes);
+  uint64_t a0, a1;
+  sgd::csr_range(off, p, nbytes, a0, a1);
   const uint64_t len = a1 - a0;
   const uint32_t cls = len > kSha1Long ? kLongClass : kMaxBlocks - (uint32_t)sha1_blocks(len);
   keys[p] = ((uint64_t)cls << 32) | p;

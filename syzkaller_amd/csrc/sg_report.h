@@ -7,29 +7,6 @@
 
 namespace sg {
 
-__device__ __forceinline__ uint64_t lb64(const uint64_t* a, uint64_t n, uint64_t v) {
-  uint64_t lo = 0, hi = n;
-  while (lo < hi) {
-    uint64_t mid = (lo + hi) >> 1;
-    if (a[mid] < v)
-      lo = mid + 1;
-    else
-      hi = mid;
-  }
-  return lo;
-}
-__device__ __forceinline__ uint64_t ub64(const uint64_t* a, uint64_t n, uint64_t v) {
-  uint64_t lo = 0, hi = n;
-  while (lo < hi) {
-    uint64_t mid = (lo + hi) >> 1;
-    if (a[mid] <= v)
-      lo = mid + 1;
-    else
-      hi = mid;
-  }
-  return lo;
-}
-
 // Radix index over a sorted u64 array A[0..n): r[k] = lower_bound(A, lo + (k
 // << sh)) for k <= nb (lo = A[0]), so a lower_bound of x only searches
 // [r[k], r[k+1]] for x's bucket k (about one entry per bucket): two adjacent

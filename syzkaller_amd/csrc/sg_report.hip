@@ -46,7 +46,7 @@ __global__ void k_radix_index(const uint64_t* __restrict__ a, uint64_t n, uint64
   if (k > nb) return;
   const uint64_t d = k << sh;
   const uint64_t x = ((d >> sh) != k || lo + d < lo) ? ~0ull : lo + d;  // saturate past the top of u64
-  r[k] = (uint32_t)lb64(a, n, x);
+  r[k] = (uint32_t)sgd::lb64(a, n, x);
 }
 
 struct RepArgs {
@@ -185,11 +185,11 @@ __global__ void k_chunk_prep(ChunkArgs a) {
   uint64_t lo = 0, hi = a.nsym;
   // the previous chunk's last site (chunk nch, above every site, follows a
   // possibly partial last chunk: its bound is the last site, not pcs[nch kSites - 1])
-  if (c > 0) lo = ub64(a.send, a.nsym, a.pcs[min<uint64_t>(c * kSites, a.npcs) - 1]);
+  if (c > 0) lo = sgd::ub64(a.send, a.nsym, a.pcs[min<uint64_t>(c * kSites, a.npcs) - 1]);
   if (c < a.nch) {
     const uint64_t last = a.pcs[min<uint64_t>((c + 1) * kSites, a.npcs) - 1];
     a.bnd[c] = last;
-    hi = ub64(a.send, a.nsym, last);
+    hi = sgd::ub64(a.send, a.nsym, last);
     const uint64_t span = last - a.pcs[c * kSites];
     uint32_t sh = 0;
     while (sh < 63 && (span >> sh) >= kSiteIdx) sh++;

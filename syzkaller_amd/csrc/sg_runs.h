@@ -19,7 +19,8 @@ __global__ void k_tr_select(const uint64_t* __restrict__ prog_off, const uint32_
                             uint32_t nruns, uint64_t ncalls, uint32_t* __restrict__ selcall, uint8_t* __restrict__ sel) {
   const uint64_t e = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (e >= nexec) return;
-  const uint64_t c0 = min(prog_off[e], ncalls), c1 = min(max(prog_off[e + 1], c0), ncalls);
+  uint64_t c0, c1;
+  sgd::csr_range(prog_off, e, ncalls, c0, c1);
   const uint64_t want = call[e / nruns];
   if (c1 - c0 > want) {  // fuzzer.go:547 / :558 / :580: info[call] exists
     selcall[e] = (uint32_t)(c0 + want);

@@ -1,8 +1,8 @@
 // The buffer planner and the offsets check of syzkaller_amd/csrc/sg_plan.h, on
 // the CPU: alignment, no overlap, the total, the region-count overflow, and
 // the three largest staging layouts against the byte counts their entry points
-// summed by hand before they used the planner; and grow_cap, the capacity
-// policy of the grow-only buffers.
+// summed by hand before they used the planner; grow_cap, the capacity policy
+// of the grow-only buffers; and bits_below, the sorts' mask over keys below n.
 #include <cstdio>
 #include <vector>
 
@@ -155,6 +155,48 @@ int main() {
         }
         CHECK(got == nc);
       }
+  }
+  {  // bits_below: 0 for n <= 1, else the smallest 2^k - 1 that is >= n - 1, on 0 .. 9; 2^k - 1, 2^k, 2^k + 1
+     // for k in {8, 31, 32, 33, 63}; 2^64 - 1
+    const struct {
+      uint64_t n, want;
+    } cases[] = {{0x0ull, 0x0ull},
+                 {0x1ull, 0x0ull},
+                 {0x2ull, 0x1ull},
+                 {0x3ull, 0x3ull},
+                 {0x4ull, 0x3ull},
+                 {0x5ull, 0x7ull},
+                 {0x6ull, 0x7ull},
+                 {0x7ull, 0x7ull},
+                 {0x8ull, 0x7ull},
+                 {0x9ull, 0xfull},
+                 {0xffull, 0xffull},
+                 {0x100ull, 0xffull},
+                 {0x101ull, 0x1ffull},
+                 {0x7fffffffull, 0x7fffffffull},
+                 {0x80000000ull, 0x7fffffffull},
+                 {0x80000001ull, 0xffffffffull},
+                 {0xffffffffull, 0xffffffffull},
+                 {0x100000000ull, 0xffffffffull},
+                 {0x100000001ull, 0x1ffffffffull},
+                 {0x1ffffffffull, 0x1ffffffffull},
+                 {0x200000000ull, 0x1ffffffffull},
+                 {0x200000001ull, 0x3ffffffffull},
+                 {0x7fffffffffffffffull, 0x7fffffffffffffffull},
+                 {0x8000000000000000ull, 0x7fffffffffffffffull},
+                 {0x8000000000000001ull, 0xffffffffffffffffull},
+                 {0xffffffffffffffffull, 0xffffffffffffffffull}};
+    for (const auto& c : cases) {
+      const uint64_t got = sg::bits_below(c.n);
+      if (got != c.want) {
+        printf("FAIL bits_below(0x%llx) = 0x%llx, expected 0x%llx\n", (unsigned long long)c.n, (unsigned long long)got,
+               (unsigned long long)c.want);
+        fails++;
+      }
+      CHECK((got & (got + 1)) == 0);            // 2^k - 1
+      CHECK(c.n <= 1 || got >= c.n - 1);        // covers 0 .. n - 1
+      CHECK(got == 0 || (got >> 1) < c.n - 1);  // and no shorter mask does
+    }
   }
   if (fails) return 1;
   printf("PASS\n");

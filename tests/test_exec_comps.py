@@ -189,6 +189,53 @@ def test_full_buffers(ctx, ctx_option):
 
 
 @pytest.mark.gpu
+def test_workspace_growth_between_the_two_paths(ctx):  # (ctx: the session's context exists before any other, as for every GPU test here)
+    """Three calls on one fresh context, on the auto path: the edge cases (the
+    workspace takes its first 64 MiB); a batch whose first pass fits in those
+    and whose general path does not; the edge cases again.  The second call's
+    first pass has run when the workspace grows and drops its contents: the
+    call has to run it again, with its pointers bound to the new block.
+
+    The bytes, from exec_comps() and ec_general_bytes() (regions rounded up to
+    256 B).  First pass: 24 B per record (tmp) and 17 B per call, plus the
+    scan's few KiB.  General path over ng records: gidx, gcall, rlo, rhi
+    (4 x 4 B), the five tables (5 x 8 B), v, ka, kb (3 x 8 B), pos (8 B), flags
+    (4 B) = 92 B per record; 8 B per call; the sort's 256 counters of 12 B per
+    tile of 8,192 keys; the scans; 4 KiB.  With calls of 65,535 distinct
+    records (all on the general path: 65,535 > 4,096) that is, first pass /
+    both:
+      8 calls, 524,280 records: 12,585,216 / 61,025,792 B  (fits 67,108,864)
+      9 calls, 589,815 records: 14,158,080 / 68,653,056 B  (does not)
+    so 9 calls is the smallest such batch."""
+    from syzkaller_amd import cover as C
+    from syzkaller_amd import hints as G
+
+    rng = np.random.default_rng(37)
+    ncalls, per = 9, 65535
+    # EC.distinct's records, drawn as arrays: the multiplier is odd, so arg1 alone tells the records of a call apart
+    i = np.arange(per, dtype=np.uint64)
+    big = np.empty((ncalls, per, 4), np.uint64)
+    for c in range(ncalls):
+        big[c, :, 0] = i % np.uint64(8)
+        big[c, :, 1] = rng.permutation(per).astype(np.uint64) * np.uint64(0x9E3779B97F4A7C15)
+        big[c, :, 2] = rng.integers(0, 1 << 62, size=per, dtype=np.uint64)
+        big[c, :, 3] = np.uint64(EC.PC0) + np.uint64(4) * i
+    big, big_off = big.reshape(-1, 4), np.arange(ncalls + 1, dtype=np.uint64) * np.uint64(per)
+    small, small_off = EC.to_arrays(list(_edges().values()))
+    e_small, e_big = X.batch(small, small_off), X.batch(big, big_off)
+    assert np.diff(e_big[0].astype(np.int64)).tolist() == [per] * ncalls
+    c = C.Context()
+    try:
+        _same(G.exec_comps(small, small_off, ctx=c), e_small)
+        assert c.counter("workspace_bytes") == 64 << 20 and c.counter("exec_comps_general") == 0
+        _same(G.exec_comps(big, big_off, ctx=c), e_big)
+        assert c.counter("exec_comps_general") == ncalls and c.counter("workspace_bytes") > 64 << 20
+        _same(G.exec_comps(small, small_off, ctx=c), e_small)
+    finally:
+        c.close()
+
+
+@pytest.mark.gpu
 def test_capacity_convention_and_arguments(ctx, ctx_option):
     import torch
 

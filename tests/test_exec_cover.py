@@ -265,6 +265,46 @@ def test_staging_buffer_growth():
 
 
 @pytest.mark.gpu
+def test_workspace_growth_between_the_two_paths(ctx):  # (ctx: the session's context exists before any other, as for every GPU test here)
+    """Three calls on one fresh context, on the auto path: a few hundred PCs
+    (the workspace takes its first 64 MiB); a batch whose first pass fits in
+    those and whose general path does not; the first batch again.  The second
+    call's first pass has run when the workspace grows and drops its contents:
+    the call has to run it again, with its pointers bound to the new block.
+
+    The bytes, from exec_cover() and xc_general_bytes() (regions rounded up to
+    256 B).  First pass: 4 B per PC (tmp) and 13 B per call, plus the scan's
+    few KiB.  General path over ng PCs: gidx, gcall, rank (3 x 4 B), U (8 B),
+    v, ka, kb (3 x 8 B), pos (8 B), flags (4 B) = 56 B per PC; 8 B per call;
+    the sort's 256 counters of 12 B per tile of 8,192 keys; the scans; 4 KiB.
+    With calls of 65,535 distinct PCs (a full KCOV buffer, all on the general
+    path: 65,535 > 8,192) that is, first pass / both:
+      16 calls, 1,048,560 PCs: 4,196,352 / 63,321,344 B  (fits 67,108,864)
+      17 calls, 1,114,095 PCs: 4,458,496 / 67,278,592 B  (does not)
+    so 17 calls is the smallest such batch."""
+    from syzkaller_amd import cover as C
+
+    rng = np.random.default_rng(49)
+    ncalls, per = 17, 65535
+    small = X.to_arrays([draw(rng, 200, 30), [], distinct(rng, 90)])
+    big = (distinct(rng, ncalls * per), np.arange(ncalls + 1, dtype=np.uint64) * np.uint64(per))
+    e_small, e_big = X.batch(*small), X.batch(*big)
+    assert int(e_big[1][-1]) == ncalls * per
+    c = C.Context()
+    try:
+        cov, cvo = C.exec_cover(*small, ctx=c)
+        assert np.array_equal(cvo, e_small[1]) and np.array_equal(cov, e_small[0])
+        assert c.counter("workspace_bytes") == 64 << 20 and c.counter("exec_cover_general") == 0
+        cov, cvo = C.exec_cover(*big, ctx=c)
+        assert np.array_equal(cvo, e_big[1]) and np.array_equal(cov, e_big[0])
+        assert c.counter("exec_cover_general") == ncalls and c.counter("workspace_bytes") > 64 << 20
+        cov, cvo = C.exec_cover(*small, ctx=c)
+        assert np.array_equal(cvo, e_small[1]) and np.array_equal(cov, e_small[0])
+    finally:
+        c.close()
+
+
+@pytest.mark.gpu
 def test_capacity_convention_and_arguments(ctx, ctx_option):
     import torch
 

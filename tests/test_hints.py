@@ -258,6 +258,58 @@ def test_shrink_expand_batch_shapes(ctx):
 
 
 @pytest.mark.gpu
+def test_workspace_growth_between_count_and_sort(ctx):  # (ctx: the session's context exists before any other, as for every GPU test here)
+    """Three calls on one fresh context: a small batch (the workspace takes its
+    first 64 MiB); one whose count pass fits in those and whose candidates do
+    not; the small batch again.  The second call's counts are in the workspace
+    when it grows and drops its contents: the call has to count again.
+
+    The bytes, from hints_replacers() (regions rounded up to 256 B).  Count
+    pass: one record, 2,304 B.  Then per candidate cslot (4 B), crep, ka, kb
+    (3 x 8 B), flags (4 B), pos (8 B), U (8 B) and, for the host form with a
+    capacity of at least the candidates, its replacer (8 B) = 56 B; 4 B per
+    value slot; the sort's 256 counters of 12 B per tile of 8,192 keys; the
+    scans.  One record of 2,048 pairs (v, x_j), x_j distinct, and value slots
+    all holding v: every pair matches every slot at the full width alone, 2,048
+    candidates per slot.
+      581 slots, 1,189,888 candidates: 67,097,344 B  (fits 67,108,864)
+      582 slots, 1,191,936 candidates: 67,212,032 B  (does not)
+    The expected lists are the oracle's for one slot, once per slot:
+    HC.expected_replacers gives slot i H.shrink_expand(vals[i], the record's
+    CompMap), which reads no other slot."""
+    from syzkaller_amd import cover as C
+    from syzkaller_amd import hints as G
+
+    rng = np.random.default_rng(10)
+    v, npairs, nslots = 0x1234567890abcdef, 2048, 582
+    xs = sorted({int(x) for x in rng.integers(1 << 40, 1 << 64, size=npairs + 64, dtype=np.uint64)} - {v})[:npairs]
+    added = [(v, xs[int(j)]) for j in rng.permutation(npairs)]
+    (one,), matches = HC.expected_replacers([added], [v], [0, 1])
+    assert len(one) == matches == npairs
+    pairs, po = HC.pairs_csr([added])
+    vals, vo = np.full(nslots, v, np.uint64), np.array([0, nslots], np.uint64)
+    (_, _, _, _, s_vals, s_vo), s_lists = _pool_batch(1)
+    s_pairs, s_po = HC.pairs_csr(s_lists)
+    s_exp, _ = HC.expected_replacers(s_lists, s_vals, s_vo)
+    c = C.Context()
+    try:
+        def small():
+            reps, ro = G.shrink_expand_batch(s_pairs, s_po, s_vals, s_vo, ctx=c)
+            assert np.diff(ro.astype(np.int64)).tolist() == [len(x) for x in s_exp]
+            assert reps.tolist() == [x for s in s_exp for x in s]
+
+        small()
+        assert c.counter("workspace_bytes") == 64 << 20
+        reps, ro = G.shrink_expand_batch(pairs, po, vals, vo, ctx=c, cap=nslots * npairs)
+        assert np.array_equal(ro, np.arange(nslots + 1, dtype=np.uint64) * np.uint64(npairs))
+        assert np.array_equal(reps.reshape(nslots, npairs), np.tile(np.array(one, np.uint64), (nslots, 1)))
+        assert c.counter("hints_candidates") == nslots * npairs and c.counter("workspace_bytes") > 64 << 20
+        small()
+    finally:
+        c.close()
+
+
+@pytest.mark.gpu
 def test_end_to_end_regions_to_replacers(ctx):
     from syzkaller_amd import hints as G
 
