@@ -1,6 +1,8 @@
-"""Cases of tests/test_hub_state.py: program texts at the edges of the CallSet scan (64-byte steps, 256-byte
-tiles, the long-line limit), names crafted for the dictionary's probe paths, and corpora for the hub's add,
-pending and purge.  What each case relies on is asserted on the case itself by the CPU tests."""
+"""Cases of tests/test_hub_state.py: program texts for the rules of CallSet, a call line at every place of the
+scan's 64-byte step, lines at the long-line limit, names crafted for the dictionary's probe paths, and corpora
+for the hub's add, pending and purge.  What each case relies on is asserted on the case itself by the CPU
+tests.  The edges of the scan's 256-byte tiles, of its 64-line stores and of a wave's share of the tiles are
+not met here: tests/call_set_cases.py has the cases for those."""
 import json
 import os
 
@@ -20,13 +22,13 @@ def kats():
         return [(c["text"].encode(), c["ok"], [n.encode() for n in c["names"]]) for c in json.load(f)["cases"]]
 
 
-def offset_batch():
-    """One call line `rN = name(` at every start offset of OFFSETS in its program, the program at every start
-    misalignment 0..3 of the buffer: (progs, [(index, misalignment, offset, name)]).  The line's '=', '(' and
-    '\\n' so each fall on both sides of every 64-byte step."""
+def offset_batch(offsets=OFFSETS):
+    """One call line `rN = name(` at every start offset of `offsets` in its program, the program at every start
+    misalignment 0..3 of the buffer: (progs, [(index, misalignment, offset, name)]).  With OFFSETS the line's
+    '=', '(' and '\\n' so each fall on both sides of every 64-byte step."""
     progs, marks, pos = [], [], 0
     for a in range(4):
-        for o in OFFSETS:
+        for o in offsets:
             fill = (a - pos) % 4 or 4
             progs.append(b"f(\n\n"[:fill])
             pos += fill

@@ -3,6 +3,7 @@
 rejected argument, the no-device result, the oracle against the reference's table and the pinned scanner rules,
 and the conditions the cases rely on.  On the GPU every status, span, id, key, seq and count exactly as the
 oracle's (tests/hub_state_oracle.py: pure Python over dicts); no tolerance anywhere."""
+import hashlib
 import os
 import re
 import subprocess
@@ -11,16 +12,16 @@ import numpy as np
 import pytest
 
 from tests import hub_state_cases as K
+from tests import hub_state_checks as C
 from tests import hub_state_oracle as OR
 from tests import prog_hashes_cases as PK
 from tests.conftest import ROOT
 
 U8, U32, U64 = np.uint8, np.uint32, np.uint64
+FILL, UNK = C.FILL, C.UNK
 NAMES = ("sg_nametab_create", "sg_nametab_destroy", "sg_nametab_count", "sg_nametab_add", "sg_call_sets",
          "sg_call_sets_dev", "sg_sigset_remove", "sg_hubcorpus_create", "sg_hubcorpus_destroy", "sg_hubcorpus_count",
          "sg_hubcorpus_export", "sg_hubcorpus_add", "sg_hubcorpus_pending", "sg_hubcorpus_purge")
-FILL = 0xA5
-UNK = 0xFFFFFFFF
 
 
 def _has_gpu():
@@ -254,6 +255,7 @@ def test_oracle_long_line_rule():
 
 def test_case_conditions():
     progs, marks = K.offset_batch()
+    assert hashlib.sha1(b"\x00".join(progs)).hexdigest() == "825f43d2fff851b2f748a9f001f97906b9afb5d5"  # as before it took offsets
     starts = np.concatenate([[0], np.cumsum([len(p) for p in progs])])
     assert sorted({(a, o) for _, a, o, _ in marks}) == [(a, o) for a in range(4) for o in K.OFFSETS]
     seen = {c: set() for c in b"=(\n"}
@@ -312,16 +314,7 @@ def test_oracle_state_mirrors_the_go_lines():
 
 
 # ---- GPU: CallSet ---------------------------------------------------------------
-def _check_sets(ctx, progs, table=None, otable=None):
-    from syzkaller_amd import hub as H
-
-    st, lo, pos, ln, ids = H.call_sets(progs, table=table, ctx=ctx)
-    est, elo, epos, eln, names = OR.call_sets(progs)
-    assert np.array_equal(st, est) and np.array_equal(lo, elo)
-    assert np.array_equal(pos, epos) and np.array_equal(ln, eln)
-    eids = [UNK if otable is None else otable.get(x, UNK) for x in names]
-    assert ids.tolist() == eids
-    return st, lo, pos, ln, ids
+_check_sets = C.check_sets  # (shared with tests/test_call_set_edges.py)
 
 
 @pytest.mark.gpu
@@ -413,10 +406,7 @@ def test_callset_cap_one_too_small_and_null_table(ctx):
     assert nl.value == 0 and lo[0] == 0
 
 
-def _to_dev(a):
-    import torch
-
-    return torch.from_numpy(np.ascontiguousarray(a).view(np.uint8).copy()).to("cuda")
+_to_dev = C.to_dev
 
 
 @pytest.mark.gpu
@@ -424,7 +414,6 @@ def test_callset_device_form_clamps_garbage_offsets(ctx):
     import torch
 
     from syzkaller_amd import hub as H
-    from syzkaller_amd._lib import call
     from syzkaller_amd.corpus import texts_csr
 
     table = H.NameTable(ctx)
@@ -432,35 +421,10 @@ def test_callset_device_form_clamps_garbage_offsets(ctx):
     otab = {x: i for i, x in enumerate(K.NAMES[:5])}
 
     def run(tab, d_bytes_ptr, nbytes, offs, count, cap):
-        """The five outputs, each with 16 guard bytes behind it that must stay as they were."""
-        sizes = (count, 8 * (count + 1), 8 * cap, 4 * cap, 4 * cap)
-        bufs = [torch.full((m + 16,), FILL, dtype=torch.uint8, device="cuda") for m in sizes]
-        torch.cuda.synchronize()
-        call("sg_call_sets_dev", ctx.h, tab.h if tab else None, d_bytes_ptr, _to_dev(offs).data_ptr(), count, nbytes,
-             *[t.data_ptr() for t in bufs], cap)
-        ctx.sync()
-        outs = [t.cpu().numpy() for t in bufs]
-        for o, m in zip(outs, sizes):
-            assert (o[m:] == FILL).all()
-        lo = outs[1][:sizes[1]].view(U64)
-        nl = int(lo[-1])
-        written = nl if nl <= cap else 0
-        for o, w in zip(outs[2:], (8, 4, 4)):
-            assert (o[w * written:] == FILL).all()
-        return (outs[0][:count].tolist(), lo.tolist(), outs[2][:8 * written].view(U64).tolist(),
-                outs[3][:4 * written].view(U32).tolist(), outs[4][:4 * written].view(U32).tolist())
+        return C.dev_run(ctx, tab, d_bytes_ptr, nbytes, offs, count, cap)
 
     def expect(view, ranges, tab=otab):
-        st, lo, pos, ln, ids = [], [0], [], [], []
-        for a0, a1 in ranges:
-            s, lines = OR.call_lines(view[a0:a1])
-            st.append(s)
-            for p, m in lines:
-                pos.append(a0 + p)
-                ln.append(m)
-                ids.append(tab.get(view[a0 + p:a0 + p + m], UNK))
-            lo.append(len(pos))
-        return st, lo, pos, ln, ids
+        return C.dev_expect(view, ranges, tab)
 
     progs = K.mixed(130, 31)
     b, off = texts_csr(progs)
@@ -574,10 +538,7 @@ def test_sigset_remove(ctx):
 
 
 # ---- GPU: the corpus ----------------------------------------------------------------
-def _same_corpus(c, o):
-    for g, e in zip(c.export(), o.export()):
-        assert np.array_equal(g, e)
-    assert c.count() == len(o.recs)
+_same_corpus = C.same_corpus
 
 
 @pytest.mark.gpu
