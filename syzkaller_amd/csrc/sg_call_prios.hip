@@ -302,19 +302,15 @@ int prio_add(sg_prio_table* t, const uint32_t* d_ids, const uint64_t* d_off, uin
     hipLaunchKernelGGL(k_prio_merge, dim3(std::min<uint64_t>(div_up(nprogs, kPT), 1u << 20)), dim3(kPT), 0, ctx->stream, a);
   }
   SG_HIP(hipGetLastError());
-  // the bands, and parts enough for about 2048 workgroups (1024 measured slower), none of more than kPrioPart places
-  const uint32_t rows = std::max(1u, std::min(kPrioBandCells / t->ncalls, t->ncalls));
-  const uint32_t nbands = div_up(t->ncalls, rows);
-  uint64_t nparts = std::min<uint64_t>(div_up(2048, nbands), div_up(nids, 4 * kBandT));  // (a part is worth a workgroup)
-  nparts = std::max<uint64_t>(nparts, div_up(nids, kPrioPart));
-  const uint64_t part = (uint64_t)div_up(div_up(nids, nparts), kBandT) * kBandT;  // <= kPrioPart, a multiple of kBandT too
+  // the bands, and the parts of the places, none of more than kPrioPart places (sg_plan.h)
+  const BandPlan bp = band_plan(t->ncalls, nids, kPrioBandCells, kBandT, kPrioPart);
   // (more than 64 KiB of LDS has to be allowed per kernel and device)
   constexpr uint32_t kBandBytes = kPrioBandCells * 4;
   SG_HIP(hipFuncSetAttribute((const void*)k_prio_band, hipFuncAttributeMaxDynamicSharedMemorySize, kBandBytes));
   {
     ScopedTimer tm(ctx, "prio_band");
-    hipLaunchKernelGGL(k_prio_band, dim3(nbands, div_up(nids, part)), dim3(kBandT), kBandBytes, ctx->stream, a.ent, nids,
-                       t->ncalls, rows, part, t->counts);
+    hipLaunchKernelGGL(k_prio_band, dim3(bp.nbands, bp.gridy), dim3(kBandT), kBandBytes, ctx->stream, a.ent, nids,
+                       t->ncalls, bp.rows, bp.part, t->counts);
   }
   SG_HIP(hipGetLastError());
   {

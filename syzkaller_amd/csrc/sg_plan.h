@@ -1,5 +1,6 @@
 // sg_plan.h -- layout arithmetic of the context's device buffers (the
-// workspace and the host forms' staging buffer).  Plain C++: no HIP, so a host
+// workspace and the host forms' staging buffer) and launch arithmetic that a
+// test has to reach without a device (band_plan).  Plain C++: no HIP, so a host
 // compiler builds it alone (tests/cpp/plan_test.cc).
 #pragma once
 
@@ -50,6 +51,33 @@ inline uint64_t bits_below(uint64_t n) {
   uint64_t m = 0;
   while (n > 1 && m < n - 1) m = (m << 1) | 1;  // (ends: all ones is >= any n - 1)
   return m;
+}
+
+// The launch of k_prio_band (sg_call_prios.hip) for a matrix of ncalls rows and
+// nids >= 1 places of entries: a band of `rows` rows whose u32 cells fit
+// band_cells, nbands of them (grid x); the places cut into gridy parts (grid y)
+// of `part` places each, a multiple of band_threads and at most part_max:
+// parts enough for about 2048 workgroups (1024 measured slower), a part worth
+// a workgroup (4 * band_threads places), none longer than part_max.  Computed
+// in 64 bits; with ncalls <= 2^13 and nids < 2^32 every value fits 32 bits but
+// part, which reaches part_max (tests/cpp/plan_test.cc sweeps it).
+struct BandPlan {
+  uint32_t rows, nbands;
+  uint64_t nparts, part;
+  uint32_t gridy;
+};
+inline BandPlan band_plan(uint32_t ncalls, uint64_t nids, uint32_t band_cells, uint32_t band_threads, uint64_t part_max) {
+  const auto up = [](uint64_t a, uint64_t b) { return (a + b - 1) / b; };
+  const auto lo = [](uint64_t a, uint64_t b) { return a < b ? a : b; };
+  BandPlan p;
+  const uint64_t fit = lo(band_cells / ncalls, ncalls);
+  p.rows = (uint32_t)(fit ? fit : 1);
+  p.nbands = (uint32_t)up(ncalls, p.rows);
+  p.nparts = lo(up(2048, p.nbands), up(nids, 4 * (uint64_t)band_threads));
+  if (p.nparts < up(nids, part_max)) p.nparts = up(nids, part_max);
+  p.part = up(up(nids, p.nparts), band_threads) * band_threads;
+  p.gridy = (uint32_t)up(nids, p.part);
+  return p;
 }
 
 // CSR offsets of n lists: off[0] == 0 and non-decreasing up to off[n].

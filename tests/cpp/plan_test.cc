@@ -2,7 +2,9 @@
 // the CPU: alignment, no overlap, the total, the region-count overflow, and
 // the three largest staging layouts against the byte counts their entry points
 // summed by hand before they used the planner; grow_cap, the capacity policy
-// of the grow-only buffers; and bits_below, the sorts' mask over keys below n.
+// of the grow-only buffers; bits_below, the sorts' mask over keys below n; and
+// band_plan, the launch arithmetic of k_prio_band.
+#include <algorithm>
 #include <cstdio>
 #include <vector>
 
@@ -197,6 +199,53 @@ int main() {
       CHECK(c.n <= 1 || got >= c.n - 1);        // covers 0 .. n - 1
       CHECK(got == 0 || (got >> 1) < c.n - 1);  // and no shorter mask does
     }
+  }
+  {  // band_plan: k_prio_band's launch for every matrix size and the id counts about its thresholds, against
+     // the expressions sg_prio_table_add computed inline before (div_up returned uint32_t there), and what
+     // the kernel relies on, in 64-bit arithmetic.  The digest and the table pin tests/call_prios_cases.py's
+     // band_plan to this one (tests/test_call_prios_edges.py reads them).
+    const uint32_t kCells = 40960, kT = 1024;
+    const uint64_t kPart = 1ull << 26;
+    const auto div_up = [](uint64_t a, uint64_t b) { return (uint32_t)((a + b - 1) / b); };
+    const auto up64 = [](uint64_t a, uint64_t b) { return (a + b - 1) / b; };
+    const uint64_t nids_set[] = {1, 4095, 4096, 4097, kPart - 1, kPart, kPart + 1, (1ull << 32) - 1};
+    uint64_t h = 14695981039346656037ull;
+    int bad = 0;
+    for (uint32_t ncalls = 1; ncalls <= 8192; ncalls++)
+      for (uint64_t nids : nids_set) {
+        const sg::BandPlan p = sg::band_plan(ncalls, nids, kCells, kT, kPart);
+        // as sg_prio_table_add had it
+        const uint32_t rows = std::max(1u, std::min(kCells / ncalls, ncalls));
+        const uint32_t nbands = div_up(ncalls, rows);
+        uint64_t nparts = std::min<uint64_t>(div_up(2048, nbands), div_up(nids, 4 * kT));
+        nparts = std::max<uint64_t>(nparts, div_up(nids, kPart));
+        const uint64_t part = (uint64_t)div_up(div_up(nids, nparts), kT) * kT;
+        const uint32_t gridy = div_up(nids, part);
+        bool ok = p.rows == rows && p.nbands == nbands && p.nparts == nparts && p.part == part && p.gridy == gridy;
+        // what the kernel relies on
+        ok = ok && p.rows >= 1 && (uint64_t)p.rows * ncalls <= kCells;  // (ncalls <= kCells throughout)
+        ok = ok && (uint64_t)p.nbands * p.rows >= ncalls && ncalls > (uint64_t)(p.nbands - 1) * p.rows;
+        ok = ok && p.part % kT == 0 && p.part >= kT && p.part <= kPart;
+        ok = ok && (uint64_t)p.gridy * p.part >= nids && nids > (uint64_t)(p.gridy - 1) * p.part;
+        // nothing truncated: every intermediate of the old form, in 64 bits, is its 32-bit value
+        ok = ok && up64(ncalls, rows) == nbands && up64(2048, nbands) == div_up(2048, nbands);
+        ok = ok && up64(nids, 4 * kT) == div_up(nids, 4 * kT) && up64(nids, kPart) == div_up(nids, kPart);
+        ok = ok && up64(nids, nparts) == div_up(nids, nparts) && up64(up64(nids, nparts), kT) * kT == part;
+        ok = ok && up64(nids, part) == gridy && gridy <= 65535;  // (a grid's y extent)
+        if (!ok && bad++ < 5) printf("FAIL band_plan(%u, %llu)\n", ncalls, (unsigned long long)nids);
+        for (uint64_t v : {(uint64_t)p.rows, (uint64_t)p.nbands, p.nparts, p.part, (uint64_t)p.gridy})
+          h = (h ^ v) * 1099511628211ull;
+      }
+    fails += bad;
+    printf("band_plan digest %016llx\n", (unsigned long long)h);
+    for (uint32_t ncalls : {1u, 8u, 70u, 202u, 203u, 256u, 257u, 300u, 320u, 512u, 513u, 1025u, 1541u, 8191u, 8192u})
+      for (uint64_t nids : {uint64_t(1), uint64_t(4097), uint64_t(45056), kPart + 1}) {
+        const sg::BandPlan p = sg::band_plan(ncalls, nids, kCells, kT, kPart);
+        printf("band_plan %u %llu %u %u %llu %llu %u\n", ncalls, (unsigned long long)nids, p.rows, p.nbands,
+               (unsigned long long)p.nparts, (unsigned long long)p.part, p.gridy);
+      }
+    // ncalls past the band (not reachable: SG_PRIO_MAX_CALLS is 8192): a one-row band is still planned
+    CHECK(sg::band_plan(kCells + 1, 1, kCells, kT, kPart).rows == 1);
   }
   if (fails) return 1;
   printf("PASS\n");

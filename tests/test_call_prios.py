@@ -14,6 +14,7 @@ import numpy as np
 import pytest
 
 from tests import call_prios_cases as K
+from tests import call_prios_checks as CK
 from tests import call_prios_oracle as OR
 from tests.conftest import ROOT
 
@@ -25,17 +26,7 @@ NAMES = ("sg_prio_table_create", "sg_prio_table_destroy", "sg_prio_table_clear",
 FILLF, FILLI = F32(-7.5), -123456789
 
 
-def _has_gpu():
-    try:
-        import torch
-
-        return torch.cuda.device_count() > 0
-    except Exception:
-        return False
-
-
-def _bits(a):
-    return np.ascontiguousarray(a, F32).view(U32)
+_has_gpu, _bits, _same, _to_dev = CK.has_gpu, CK.bits, CK.same, CK.to_dev  # (shared with the edge file)
 
 
 # ---- CPU: the boundary ---------------------------------------------------------
@@ -225,14 +216,6 @@ def _table(ctx, name):
     return PrioTable(st, mm, en, ctx=ctx), ids, off, exp
 
 
-def _same(got, exp, what):
-    cnt, dyn, pr, run = exp
-    gd, gp, gr = got
-    assert np.array_equal(_bits(gd), _bits(dyn)), (what, "dynamic", int((_bits(gd) != _bits(dyn)).sum()))
-    assert np.array_equal(_bits(gp), _bits(pr)), (what, "prios")
-    assert gr.dtype == I32 and np.array_equal(gr, run), (what, "run")
-
-
 @pytest.mark.gpu
 @pytest.mark.parametrize("name", ("example", "corpus12") + tuple(map(str, K.SIZES)))
 def test_bit_exact(ctx, name):
@@ -319,15 +302,6 @@ def test_two_adds_clear_and_from_progs(ctx):
     for a, b in zip(three, one):
         assert np.array_equal(a.view(U32), b.view(U32))
     t.close()
-
-
-def _to_dev(a):
-    import torch
-
-    a = np.ascontiguousarray(a)
-    if a.dtype == U64:
-        return torch.from_numpy(a.view(np.int64).copy()).to("cuda")
-    return torch.from_numpy(a.view(np.int32).copy()).to("cuda")
 
 
 @pytest.mark.gpu
