@@ -109,6 +109,10 @@ int sg_ctx_kernel_time(sg_ctx* ctx, const char* name, double* ms, uint64_t* laun
  * path of sg_prog_hashes*, sg_sigset_add_progs and sg_hub_sync on this
  * context since it was created; counted on the device, read here after a
  * stream sync) and "sha1_long_len" (constant: SG_SHA1_LONG);
+ * "inflate_long_streams" (the streams that took the wave-per-stream path of
+ * sg_inflate_batch*, sg_db_open on this context since it was created, once
+ * per call that counted them; counted on the device, read here after a stream
+ * sync) and "inflate_long_len" (constant: SG_INFLATE_LONG);
  * "owned_big_records" (the
  * records the last
  * ordered-output call -- sg_triage_batch[_dev] with diff lists, sg_merge_poll
@@ -1299,6 +1303,128 @@ int sg_hubcorpus_pending(sg_hubcorpus* h, sg_sigset* mgr, uint64_t mgr_seq, uint
  * > 0. */
 int sg_hubcorpus_purge(sg_hubcorpus* h, sg_sigset* const* mgrs, size_t nmgrs, uint8_t* del_sigs, size_t del_cap,
 		       size_t* ndel);
+
+/* ---- the corpus database: db.Open and loadDB from the file bytes ------------ */
+/* pkg/db (pkg/db/db.go:38-52 Open, :125-131 the constants, :167-249
+ * deserializeDB / deserializeHeader / deserializeRecord) reads a database
+ * record by record and inflates every value on one thread through
+ * compress/flate; the hub's loadDB (syz-hub/state/state.go:83-110) and the
+ * manager's start-up (syz-manager/manager.go:178-216) wait for it before they
+ * look at a single program.  Every value is its own raw DEFLATE stream (RFC
+ * 1951), so a corpus is as many independent decoders as it has records.  Only
+ * the read side is here: Save, Delete, Flush and compact need a compressor and
+ * stay with the caller.
+ *
+ * The decoder (csrc/sg_inflate.h, one source for host and device) follows
+ * zlib 1.2.11's inflate of a raw stream.  A stream's status:
+ *   SG_INFLATE_OK 0 the final block ended; SG_INFLATE_CORRUPT 1 zlib raises;
+ *   SG_INFLATE_TRUNCATED 2 the input ended before the final block did, and
+ *   nothing corrupt was seen before that point; SG_INFLATE_TOO_LARGE 3 the
+ *   output reached 2^32 bytes (this library's limit per stream, not zlib's:
+ *   the decoder stops there; reached by a CPU test of the decoder only, no
+ *   GPU test inflates 4 GiB).
+ * consumed is the number of input bytes up to and including the byte that
+ * holds the last bit of the final block (0 unless OK); bytes after it are
+ * ignored, as Go's reader ignores them inside the LimitedReader of :242.
+ * A stream as Go writes it (Flush then Close of a flate.Writer, :161-162) is
+ * read here, from that package's source, as the deflate data, an empty stored
+ * block (sync flush) and the final empty stored block 01 00 00 ff ff; the
+ * source is not part of this repository's references, so parity with Go's
+ * writer is unpinned -- any valid stream is decoded whatever wrote it.
+ * A stream longer than SG_INFLATE_LONG compressed bytes gets a wave to itself;
+ * the context counter "inflate_long_streams" counts them, "inflate_long_len"
+ * is the constant. */
+#define SG_INFLATE_OK 0
+#define SG_INFLATE_CORRUPT 1
+#define SG_INFLATE_TRUNCATED 2
+#define SG_INFLATE_TOO_LARGE 3
+#define SG_INFLATE_LONG 65536
+/* A CSR of streams in, a CSR of outputs out: stream k is in[in_off[k] ..
+ * in_off[k+1]) and owns out[out_off[k] .. out_off[k+1]); a stream that is not
+ * OK owns no output.  status, consumed (n each) and out_off (n + 1) are always
+ * written; *nout is always the total, and out is written only when it is <=
+ * cap.  SG_EINVAL, before the context is touched: a NULL ctx, out_off or nout;
+ * status or consumed NULL with n > 0; out NULL with cap > 0; what
+ * sg_prog_hashes rejects of a CSR; 2^32 streams or more.  SG_EINVAL after the
+ * count pass, with nothing written: 2^33 output bytes or more.  SG_ENODEV
+ * without a device.  Two waits. */
+int sg_inflate_batch(sg_ctx* ctx, const uint8_t* in, const uint64_t* in_off, size_t n, uint8_t* status,
+		     uint64_t* consumed, uint64_t* out_off, uint8_t* out, size_t cap, size_t* nout);
+/* Device form (nbytes = the bytes in d_in): every pointer is device memory,
+ * stream-ordered, nothing is read back; d_out_off[n] is the total and d_out is
+ * written only when it is <= cap.  The offsets follow sg_prog_hashes_dev's
+ * rule: each start is clamped to nbytes and each end to [start, nbytes], so
+ * garbage offsets give garbage streams (which mostly fail), never a read
+ * outside [d_in, d_in + nbytes) or a write outside [d_out, d_out + cap).
+ * SG_EINVAL: a NULL ctx or d_out_off; d_in_off, d_status or d_consumed NULL
+ * with n > 0; d_in NULL with nbytes > 0; d_out NULL with cap > 0; n >= 2^32. */
+int sg_inflate_batch_dev(sg_ctx* ctx, const uint8_t* d_in, const uint64_t* d_in_off, uint64_t n, uint64_t nbytes,
+			 uint8_t* d_status, uint64_t* d_consumed, uint64_t* d_out_off, uint8_t* d_out, uint64_t cap);
+
+/* deserializeHeader (:193-211) and the framing half of deserializeRecord
+ * (:213-249) over a file's bytes; host only: no context, no device.  Records
+ * come in file order: key = bytes[key_pos .. + key_len), seq, and the value's
+ * stream bytes[val_pos .. + val_len).  seq == ~0 is a deletion and has no
+ * value field (val_pos = val_len = 0); val_len == 0 is an empty value.  *end:
+ *   SG_DB_END_EOF 0 clean end at a record boundary; SG_DB_END_MAGIC 1 bad
+ *   header magic; SG_DB_END_VERSION 2 bad version (0, or above 1);
+ *   SG_DB_END_RECORD 3 bad record magic; SG_DB_END_TRUNCATED 4 a header field,
+ *   a key or a value runs past the file.
+ * The record at which *end != 0 arises is not counted.  An empty file is a
+ * valid empty database (:196-198); a file of 1 to 7 bytes is end 4, or end 1
+ * once four bytes disagree with the magic.  A record's framing always advances
+ * by val_len, whatever the stream inside consumed: the reference leaves that
+ * to how far its inner bufio reader happened to read, so this is a pinned
+ * choice and parity is unpinned where a stream ends before its frame.
+ * *nrec is always the count; the arrays are written only when it is <= cap.
+ * SG_EINVAL: a NULL nrec or end, bytes NULL with nbytes > 0, an array NULL
+ * with cap > 0.  The return value is SG_OK whatever *end is. */
+#define SG_DB_END_EOF 0
+#define SG_DB_END_MAGIC 1
+#define SG_DB_END_VERSION 2
+#define SG_DB_END_RECORD 3
+#define SG_DB_END_TRUNCATED 4
+#define SG_DB_END_VALUE 5
+#define SG_DB_SEQ_DELETED (~0ull)
+int sg_db_scan(const uint8_t* bytes, size_t nbytes, uint64_t* key_pos, uint32_t* key_len, uint64_t* seq,
+	       uint64_t* val_pos, uint32_t* val_len, size_t cap, size_t* nrec, int* end);
+
+/* db.Open (:38-52) without the compaction: the file is scanned on the host
+ * and uploaded once, and EVERY framed stream is counted and validated on the
+ * device.  The first record whose stream is not OK ends the database there,
+ * as deserializeDB :180-183 returns at the first error -- also when a later
+ * record would have overwritten it -- and end becomes SG_DB_END_VALUE 5.  Over
+ * the prefix that parsed, the last write of a key wins and a deletion removes
+ * the key (:185-189), resolved on the host after the one read-back of statuses
+ * and lengths; only the live records' streams are then written out.  Live
+ * records are in file order of their winning write: Go has map order there, so
+ * this is a pinned choice, not a parity claim.  The texts stay on the device
+ * until sg_db_destroy.  SG_EINVAL: a NULL ctx or out, bytes NULL with nbytes >
+ * 0; 2^32 records or 2^33 text bytes or more.  SG_ENODEV without a device.
+ * The database lives in ctx and must be destroyed before it. */
+typedef struct sg_db sg_db;
+int sg_db_open(sg_ctx* ctx, const uint8_t* bytes, size_t nbytes, sg_db** out);
+void sg_db_destroy(sg_db* db);
+/* counts[0] nlive = len(db.Records); [1] uncompacted, the records parsed,
+ * deletions included (:184); [2] the live texts' bytes; [3] the live keys'
+ * bytes; [4] end. */
+int sg_db_counts(sg_db* db, uint64_t counts[5]);
+/* The live records to the host: key_off (nlive + 1) and keys, seqs (nlive),
+ * text_off (nlive + 1) and texts, sized by sg_db_counts; any of them may be
+ * NULL.  One wait when texts or text_off are asked for. */
+int sg_db_export(sg_db* db, uint64_t* key_off, uint8_t* keys, uint64_t* seqs, uint64_t* text_off, uint8_t* texts);
+/* The device pointers of the texts and their nlive + 1 offsets, as
+ * sg_prog_hashes_dev and sg_call_sets_dev take them; valid until
+ * sg_db_destroy. */
+int sg_db_device(sg_db* db, const uint8_t** d_texts, const uint64_t** d_text_off);
+/* loadDB's loop (state.go:91-105) over the resident texts; no text crosses the
+ * bus again.  bad[k] = 1 when prog.CallSet fails (sg_call_sets_dev's status is
+ * not 0), else 2 when the key is not exactly the 40 lower-case hex characters
+ * of sg_prog_hashes_dev's hash, else 0; *max_seq is taken over the records
+ * with bad == 0 (:102-104).  tab may be NULL (no ids are looked up); one of
+ * another context is SG_EINVAL, as are a NULL db or max_seq and bad NULL with
+ * live records.  One wait. */
+int sg_db_verify(sg_db* db, sg_nametab* tab, uint8_t* bad, uint64_t* max_seq);
 
 #ifdef __cplusplus
 }

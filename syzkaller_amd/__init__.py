@@ -10,18 +10,21 @@ shrinkExpand over batches of argument values), and `syzkaller_amd.prio` the
 call priorities (corpus call ids to CalculatePriorities and the ChoiceTable),
 and `syzkaller_amd.corpus` the corpus' identities (pkg/hash, the identity sets
 and hubSync's Add / Del), and `syzkaller_amd.hub` the hub's corpus (prog.CallSet,
-the name dictionary, addInputs, pendingInputs and purgeCorpus).
+the name dictionary, addInputs, pendingInputs and purgeCorpus), and
+`syzkaller_amd.db` the corpus database's read side (raw DEFLATE of every value,
+db.Open and loadDB from the file's bytes).
 """
 from ._lib import LIB_PATH, SyzSigError, lib  # noqa: F401  (fails loudly if the library is missing)
 
 _PRIO = ("PrioTable", "CalculatePriorities", "BuildChoiceTable", "ChoiceTable")
 _CORPUS = ("Hash", "String", "prog_hashes", "SigSet", "HubSync", "VerifyKeys")
 _HUB = ("NameTable", "call_sets", "CallSet", "HubCorpus", "HubState")
+_DB = ("inflate_batch", "db_scan", "DB", "LoadDB")
 
-__all__ = ["LIB_PATH", "SyzSigError", "lib", *_PRIO, *_CORPUS, *_HUB]
+__all__ = ["LIB_PATH", "SyzSigError", "lib", *_PRIO, *_CORPUS, *_HUB, *_DB]
 
 
-def __getattr__(name):  # syzkaller_amd.prio's, .corpus' and .hub's names, bound on first use (the modules need numpy)
+def __getattr__(name):  # syzkaller_amd.prio's, .corpus', .hub's and .db's names, bound on first use (the modules need numpy)
     if name in _PRIO:
         from . import prio
 
@@ -34,4 +37,8 @@ def __getattr__(name):  # syzkaller_amd.prio's, .corpus' and .hub's names, bound
         from . import hub
 
         return getattr(hub, name)
+    if name in _DB:
+        from . import db
+
+        return getattr(db, name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

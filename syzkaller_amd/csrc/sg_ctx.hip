@@ -800,6 +800,13 @@ int sg_ctx_counter(sg_ctx* ctx, const char* name, uint64_t* out) {
     *out = v;
   } else if (!strcmp(name, "sha1_long_len"))  // bytes of the longest program on the short SHA-1 path (SG_SHA1_LONG)
     *out = kSha1Long;
+  else if (!strcmp(name, "inflate_long_streams")) {  // streams that took the wave-per-stream path (sg_inflate.hip)
+    uint64_t v = 0;
+    SG_HIP(hipStreamSynchronize(ctx->stream));
+    SG_HIP(hipMemcpy(&v, ctx->own_big + kInflateLongSlot, 8, hipMemcpyDeviceToHost));
+    *out = v;
+  } else if (!strcmp(name, "inflate_long_len"))  // compressed bytes of the longest stream on the lane path (SG_INFLATE_LONG)
+    *out = kInflateLong;
   else if (!strcmp(name, "prio_band_cells"))  // u32 cells of a row band of the pair count
     *out = kPrioBandCells;
   else if (!strcmp(name, "prio_short_len"))  // calls of a program on the pair count's band path

@@ -155,6 +155,8 @@ struct sg_ctx {
   sg::PinBuf pin;
   // grow-only device staging for the host entry points' inputs / outputs (dstage_reserve)
   sg::DevBuf<char> dstage;
+  // sg_inflate_batch's outputs on their way to the host (grow-only from 16 MiB; sg_inflate.hip)
+  sg::DevBuf<uint8_t> inflate_out;
   // the host ingest pipeline (sg_host.hip): its copy stream and the events
   // between the two staging slots' DMA and triage
   hipStream_t copy_stream = nullptr;
@@ -469,6 +471,32 @@ int call_sets_emit(sg_ctx* ctx, sg_nametab* tab, const uint8_t* d_bytes, const u
                    uint32_t* d_name_len, uint32_t* d_name_id, uint64_t cap, size_t ws_used);
 sg_ctx* nametab_ctx(const sg_nametab* tab);
 uint64_t nametab_names(const sg_nametab* tab);
+
+// Raw DEFLATE over a batch of streams (sg_inflate.hip; ctx lock held, the
+// device ensured).  Stream p is d_in[d_beg[p], d_end[p]), clamped to nbytes: a
+// CSR passes off and off + 1, a database file the starts and ends of its
+// framed values.  inflate_count: status, consumed and output length of every
+// stream, from inflate_ws(n) bytes of the workspace at ws_used, reserved by
+// the caller; *d_sorted is where that workspace holds the sorted keys.
+// inflate_offsets: scan_counts of the lengths (which the caller may have
+// edited: a zero length is a stream nobody wants) in the same workspace.
+// inflate_write, with the workspace untouched since the count: the outputs of
+// the OK streams with a span, when d_out_off[n] <= cap (compared on the
+// device).  n < 2^32.
+// ... at u32 slot kInflateLongSlot of own_big one 64-bit counter,
+// "inflate_long_streams": the streams that took the wave-per-stream path on
+// this context; "inflate_long_len" reads SG_INFLATE_LONG.
+constexpr uint32_t kInflateLongSlot = 32;
+constexpr uint32_t kInflateLong = SG_INFLATE_LONG;
+constexpr uint64_t kInflateMaxOut = 1ull << 33;
+size_t inflate_ws(uint64_t n);
+int inflate_count(sg_ctx* ctx, const uint8_t* d_in, const uint64_t* d_beg, const uint64_t* d_end, uint64_t n,
+                  uint64_t nbytes, uint8_t* d_status, uint64_t* d_consumed, uint32_t* d_olen, size_t ws_used,
+                  const uint64_t** d_sorted);
+int inflate_offsets(sg_ctx* ctx, const uint32_t* d_olen, uint64_t* d_out_off, uint64_t n, size_t ws_used);
+int inflate_write(sg_ctx* ctx, const uint8_t* d_in, const uint64_t* d_beg, const uint64_t* d_end, uint64_t n,
+                  uint64_t nbytes, const uint64_t* d_sorted, const uint8_t* d_status, const uint64_t* d_out_off,
+                  uint8_t* d_out, uint64_t cap);
 
 }  // namespace sg
 
