@@ -76,22 +76,9 @@ class Context:
         call("sg_ctx_timing", self.h, 1 if enable else 0)
 
     def counter(self, name):
-        """sg_ctx_counter: "owner_resets", "owner_floor", "owner_key_space", "max_launch_records",
-        the host ingest's "host_copy_bytes" / "host_copy_ns" / "host_wait_ns" / "host_copy_threads",
-        "cpu_quota_milli", "hints_candidates", "exec_cover_general" / "exec_cover_fast_cap", "triage_runs_wide",
-        the last triage_runs_from_kcov call's candidates per route of the cover fold "triage_runs_copied" /
-        "triage_runs_sorted" / "triage_runs_ranked" / "triage_runs_foreach", the constants
-        "triage_runs_sort_cap" (the most values the LDS-sort route folds) and "tinput_chunk" (the values of a
-        new list that Intersection holds in LDS at a time),
-        the call priorities' "prio_bad_ids" (ids the device form skipped) and its constants "prio_band_cells" /
-        "prio_short_len",
-        the program identities' "sha1_long_progs" (programs that took the long SHA-1 path on this context) and
-        its constant "sha1_long_len",
-        the last ordered-output call's "owned_big_records",
-        the last merge's pairs per path "merge_pairs_generic" / "merge_pairs_diff_small" /
-        "merge_pairs_gap" / "merge_pairs_tile", the last Canonicalize's "canon_wave_lists" /
-        "canon_block_lists" / "canon_big_segments" / "canon_merge_passes"
-        (include/syzsig.h lists them all)."""
+        """sg_ctx_counter: one named 64-bit value of the context.  The names, what each one counts and where
+        it lives (a host field, a device word read after a stream sync, a constant of the build) are the rows
+        of kCounters in csrc/sg_ctx.hip; an unknown name is SG_EINVAL."""
         v = c_uint64()
         call("sg_ctx_counter", self.h, name.encode(), byref(v))
         return v.value

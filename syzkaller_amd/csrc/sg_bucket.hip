@@ -905,20 +905,21 @@ int buckets_one(sg_ctx* ctx, const BucketPlan& bp, uint32_t* mwords, uint32_t* n
   // to kernels on other streams)
   const int64_t cap_blocks = ctx->opt[kOptBucketBlocks];
   if (cap_blocks > 0 && (uint64_t)cap_blocks < bgrid) bgrid = (uint32_t)cap_blocks;
-  uint64_t* ddbg = nullptr;
+  DevBuf<uint64_t> ddbg;
   if (dbg) {
-    SG_HIP(hipMalloc(&ddbg, (size_t)bgrid * 88));
-    ba.dbg = ddbg;
+    const int rc = ddbg.grow_drop((size_t)bgrid * 11, nullptr);
+    if (rc) return rc;
+    ba.dbg = ddbg.p;
   }
   // The flags path in two launches (option flag_skip): the first 1 / 2^k of
   // the bucket list with every flag stored, the record-flag summary, then the
   // rest of the list without the stores that the summary shows to rewrite a 1.
   const bool split = !emit && !dbg && d_rec_new && nrec <= kMaxLaunchRecords && fs_split(ctx);
   uint32_t* fsum = ba.ticket + 4;
-  uint32_t* fcnt = (uint32_t*)ctx->dscal + 33;  // (a device scalar of the context)
+  uint32_t* fcnt = &ctx->dev.p->fs_full_blocks;
   if (split) {
-    if (!ctx->fs_ev) SG_HIP(hipEventCreateWithFlags(&ctx->fs_ev, hipEventDisableTiming));
-    int rc = m0f_host_alloc(ctx);
+    int rc = ctx->fs_ev.create(hipEventDisableTiming);
+    if (!rc) rc = m0f_host_alloc(ctx);
     if (rc) return rc;
     SG_HIP(hipMemsetAsync(fcnt, 0, 4, ctx->stream));
   }
@@ -947,7 +948,7 @@ int buckets_one(sg_ctx* ctx, const BucketPlan& bp, uint32_t* mwords, uint32_t* n
     }
   }
   if (split) {
-    SG_HIP(hipMemcpyAsync(ctx->m0f_host + 4, fcnt, 4, hipMemcpyDeviceToHost, ctx->stream));
+    SG_HIP(hipMemcpyAsync(&ctx->pinned.p->fs_full_blocks, fcnt, 4, hipMemcpyDeviceToHost, ctx->stream));
     SG_HIP(hipEventRecord(ctx->fs_ev, ctx->stream));
     ctx->fs_pending = true;
     ctx->fs_used++;
@@ -969,14 +970,13 @@ int buckets_one(sg_ctx* ctx, const BucketPlan& bp, uint32_t* mwords, uint32_t* n
     std::vector<uint4> bd(kNumBuckets);
     std::vector<uint64_t> hd((size_t)bgrid * 11);
     SG_HIP(hipMemcpy(bd.data(), bdesc, bd.size() * 16, hipMemcpyDeviceToHost));
-    SG_HIP(hipMemcpy(hd.data(), ddbg, hd.size() * 8, hipMemcpyDeviceToHost));
+    SG_HIP(hipMemcpy(hd.data(), ddbg.p, hd.size() * 8, hipMemcpyDeviceToHost));
     double qa = 0, qb = 0, qc = 0;
     for (uint32_t i = 0; i < bgrid; i++) {
       qa += hd[8 * bgrid + 3 * i];
       qb += hd[8 * bgrid + 3 * i + 1];
       qc += hd[8 * bgrid + 3 * i + 2];
     }
-    SG_HIP(hipFree(ddbg));
     std::vector<uint32_t> sz(kNumBuckets);
     uint64_t rounds = 0;
     for (uint32_t b = 0; b < kNumBuckets; b++) {

@@ -1,7 +1,8 @@
-// sg_buf.h -- the owner of a grow-only device (or pinned host) block: pointer
-// and capacity as one unit.  Every growing buffer of the library is one of
-// these; the capacity asked for is the caller's (grow_cap of sg_plan.h with the
-// buffer's floor, or an exact size).
+// sg_buf.h -- the owners of what the library holds from HIP.  Buf is a device
+// (or pinned host) block, pointer and capacity as one unit: every buffer of the
+// library is one, grow-only or of one exact size; the capacity asked for is the
+// caller's (grow_cap of sg_plan.h with the buffer's floor, or an exact size).
+// Event and Stream own a handle each.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -90,5 +91,25 @@ struct Buf {
 template <typename T>
 using DevBuf = Buf<T>;
 using PinBuf = Buf<char, true>;
+
+// The owner of an event or of a stream: made once by create (nothing when it
+// exists), passed as the handle it holds, destroyed with its owner.
+template <typename H, hipError_t (*kCreate)(H*, unsigned), hipError_t (*kDestroy)(H)>
+struct Handle {
+  H h = nullptr;
+  Handle() = default;
+  Handle(const Handle&) = delete;
+  Handle& operator=(const Handle&) = delete;
+  ~Handle() {
+    if (h) (void)kDestroy(h);
+  }
+  int create(unsigned flags) {
+    const hipError_t e = h ? hipSuccess : kCreate(&h, flags);
+    return e == hipSuccess ? SG_OK : hip_fail(e, "creating an event or a stream");
+  }
+  operator H() const { return h; }
+};
+using Event = Handle<hipEvent_t, hipEventCreateWithFlags, hipEventDestroy>;
+using Stream = Handle<hipStream_t, hipStreamCreateWithFlags, hipStreamDestroy>;
 
 }  // namespace sg

@@ -52,7 +52,7 @@
 
 struct sg_prio_table {
   sg_ctx* ctx = nullptr;
-  void* mem = nullptr;  // the one device block: static, enabled, counts
+  sg::DevBuf<char> mem;  // the one device block: static, enabled, counts
   uint32_t ncalls = 0, mmap_id = SG_NO_CALL;
   float* stat = nullptr;                 // [ncalls * ncalls]
   uint8_t* enabled = nullptr;            // [ncalls]
@@ -294,7 +294,7 @@ int prio_add(sg_prio_table* t, const uint32_t* d_ids, const uint64_t* d_off, uin
   int rc = ws_reserve(ctx, plan);
   if (rc) return rc;
   AddArgs a{d_ids, d_off, nprogs, nids, t->ncalls, t->mmap_id, (uint32_t*)ws_at(ctx, o_ent), (uint64_t*)ws_at(ctx, o_long),
-            long_cap, (unsigned long long*)ws_at(ctx, o_nl), (unsigned long long*)(ctx->own_big + kPrioBadSlot), t->counts};
+            long_cap, (unsigned long long*)ws_at(ctx, o_nl), (unsigned long long*)&ctx->dev.p->prio_bad_ids, t->counts};
   SG_HIP(hipMemsetAsync(a.ent, 0xFF, nids * 4, ctx->stream));
   SG_HIP(hipMemsetAsync(a.nlong, 0, 8, ctx->stream));
   {
@@ -387,10 +387,6 @@ int progs_ok(const char* fn, const sg_prio_table* t, const uint32_t* call_ids, c
   return SG_OK;
 }
 
-void table_free(sg_prio_table* t) {
-  if (t->mem) hipFree(t->mem);
-  delete t;
-}
 
 }  // namespace
 }  // namespace sg
@@ -431,12 +427,12 @@ int sg_prio_table_create(sg_ctx* ctx, uint32_t ncalls, uint32_t mmap_id, const f
   t->mmap_id = mmap_id;
   WsPlan bp;
   const size_t o_cnt = bp.add(cells * 8), o_st = bp.add(cells * 4), o_en = bp.add(ncalls);
-  hipError_t e = hipMalloc(&t->mem, bp.total);
-  if (e != hipSuccess) {
-    table_free(t);
-    return hip_fail(e, "hipMalloc (prio table)");
+  rc = t->mem.grow_drop(bp.total, nullptr);
+  if (rc) {
+    delete t;
+    return rc;
   }
-  char* b = (char*)t->mem;
+  char* b = t->mem.p;
   t->counts = (unsigned long long*)(b + o_cnt);
   t->stat = (float*)(b + o_st);
   t->enabled = (uint8_t*)(b + o_en);
@@ -455,7 +451,7 @@ int sg_prio_table_create(sg_ctx* ctx, uint32_t ncalls, uint32_t mmap_id, const f
   rc = fill();
   if (rc) {
     (void)hipStreamSynchronize(ctx->stream);
-    table_free(t);
+    delete t;
     return rc;
   }
   *out = t;
@@ -469,7 +465,7 @@ void sg_prio_table_destroy(sg_prio_table* t) {
     hipSetDevice(t->ctx->device);
     hipStreamSynchronize(t->ctx->stream);
   }
-  table_free(t);
+  delete t;
 }
 
 int sg_prio_table_clear(sg_prio_table* t) {

@@ -43,7 +43,7 @@
 
 struct sg_cover_table {
   sg_ctx* ctx = nullptr;
-  void* mem = nullptr;  // the one device block everything below lives in
+  sg::DevBuf<char> mem;  // the one device block everything below lives in
   bool has_rep = false;  // symbols and call sites: the uncovered side exists
   sg::RepTables rep{};
   uint64_t nsym = 0, nall = 0, ntab = 0, nfr = 0, nslots = 0;
@@ -244,11 +244,6 @@ __global__ void k_cl_files(LinesArgs a) {
   if (f < a.nfiles) a.out_fseen[f] = (uint8_t)a.fseen[f];
 }
 
-static void table_free(sg_cover_table* t) {
-  if (!t) return;
-  if (t->mem) (void)hipFree(t->mem);
-  delete t;
-}
 
 // Both report forms behind their argument checks (ctx lock held, the device
 // ensured): d_cov is device memory of the context (its staging buffer).
@@ -473,13 +468,13 @@ int sg_cover_table_create(sg_ctx* ctx, const uint64_t* sym_start, const uint64_t
                o_row = bp.add(nall * 4), o_fo = bp.add(((uint64_t)ntab + 1) * 4), o_sl = bp.add(nfr * 4),
                o_fu = bp.add(nfr * 4), o_fi = bp.add(nfr * 4), o_ln = bp.add(nfr * 4),  // (nslots <= nfr)
                o_fso = bp.add(((uint64_t)nfiles + 1) * 4);
-  hipError_t e = hipMalloc(&t->mem, bp.total);
-  if (e != hipSuccess) {
-    table_free(t);
-    return hip_fail(e, "hipMalloc (cover table)");
+  rc = t->mem.grow_drop(bp.total, nullptr);
+  if (rc) {
+    delete t;
+    return rc;
   }
-  char* b = (char*)t->mem;
-  if (t->has_rep) report_tables_bind(t->mem, to, t->rep);
+  char* b = t->mem.p;
+  if (t->has_rep) report_tables_bind(b, to, t->rep);
   t->tab = (uint64_t*)(b + o_tab);
   t->itab.r = (const uint32_t*)(b + o_it);
   t->site_row = (uint32_t*)(b + o_row);
@@ -546,7 +541,7 @@ int sg_cover_table_create(sg_ctx* ctx, const uint64_t* sym_start, const uint64_t
   rc = build();
   if (rc) {
     (void)hipStreamSynchronize(ctx->stream);
-    table_free(t);
+    delete t;
     return rc;
   }
   *out = t;
@@ -560,7 +555,7 @@ void sg_cover_table_destroy(sg_cover_table* t) {
     hipSetDevice(t->ctx->device);
     hipStreamSynchronize(t->ctx->stream);
   }
-  table_free(t);
+  delete t;
 }
 
 int sg_cover_table_slots(sg_cover_table* t, uint64_t* nslots) {

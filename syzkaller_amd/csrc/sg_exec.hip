@@ -512,11 +512,13 @@ int exec_signal_body(sg_ctx* ctx, const uint32_t* d_pcs, const uint64_t* d_call_
   if (pstop && nprog)
     hipLaunchKernelGGL(k_prog_stop, dim3(div_up(nprog, 256)), dim3(256), 0, ctx->stream, d_prog_off, d_rec_new, nprog,
                        pstop);
-  unsigned long long* ddbg = nullptr;
+  DevBuf<unsigned long long> dbgbuf;
   if (ctx->debug_part && nprog) {  // diagnostics: the per-program cycle breakdown (stderr)
-    SG_HIP(hipMalloc(&ddbg, nprog * 64));
-    SG_HIP(hipMemsetAsync(ddbg, 0, nprog * 64, ctx->stream));
+    rc = dbgbuf.grow_drop(nprog * 8, nullptr);
+    if (rc) return rc;
+    SG_HIP(hipMemsetAsync(dbgbuf.p, 0, nprog * 64, ctx->stream));
   }
+  unsigned long long* const ddbg = dbgbuf.p;
   if (nprog) {
     ScopedTimer tm(ctx, "exec_signal");
     if (ddbg)
@@ -530,7 +532,6 @@ int exec_signal_body(sg_ctx* ctx, const uint32_t* d_pcs, const uint64_t* d_call_
     std::vector<unsigned long long> h(nprog * 8);
     SG_HIP(hipMemcpyAsync(h.data(), ddbg, nprog * 64, hipMemcpyDeviceToHost, ctx->stream));
     SG_HIP(hipStreamSynchronize(ctx->stream));
-    hipFree(ddbg);
     double t[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     uint64_t nrun = 0;
     for (uint64_t q = 0; q < nprog; q++) {
@@ -675,22 +676,21 @@ int sg_triage_traces_queued(sg_ctx* ctx, sg_set* maxsig, sg_set* newsig, const u
 namespace sg {
 // Alias tables and permutation of the Zipf generator, cached per context.
 static int gen_tables(sg_ctx* ctx, uint64_t seed, double zipf_s, uint32_t nranks) {
-  if (ctx->gen_prob && ctx->gen_seed == seed && ctx->gen_s == zipf_s && ctx->gen_nranks == nranks) return SG_OK;
+  if (ctx->gen_prob.p && ctx->gen_seed == seed && ctx->gen_s == zipf_s && ctx->gen_nranks == nranks) return SG_OK;
   std::vector<uint32_t> prob, alias, perm;
   build_zipf_tables(seed, zipf_s, nranks, prob, alias, perm);
-  SG_HIP(hipStreamSynchronize(ctx->stream));
-  if (ctx->gen_prob) {
-    hipFree(ctx->gen_prob);
-    hipFree(ctx->gen_alias);
-    hipFree(ctx->gen_perm);
-    ctx->gen_prob = ctx->gen_alias = ctx->gen_perm = nullptr;
+  // new tables, swapped in together once filled (the old ones, which kernels in flight may read, go after the wait)
+  DevBuf<uint32_t> nb[3];
+  const std::vector<uint32_t>* src[3] = {&prob, &alias, &perm};
+  for (int i = 0; i < 3; i++) {
+    const int rc = nb[i].grow_drop(nranks, nullptr);
+    if (rc) return rc;
+    SG_HIP(hipMemcpy(nb[i].p, src[i]->data(), nranks * 4, hipMemcpyHostToDevice));
   }
-  SG_HIP(hipMalloc(&ctx->gen_prob, nranks * 4));
-  SG_HIP(hipMalloc(&ctx->gen_alias, nranks * 4));
-  SG_HIP(hipMalloc(&ctx->gen_perm, nranks * 4));
-  SG_HIP(hipMemcpy(ctx->gen_prob, prob.data(), nranks * 4, hipMemcpyHostToDevice));
-  SG_HIP(hipMemcpy(ctx->gen_alias, alias.data(), nranks * 4, hipMemcpyHostToDevice));
-  SG_HIP(hipMemcpy(ctx->gen_perm, perm.data(), nranks * 4, hipMemcpyHostToDevice));
+  SG_HIP(hipStreamSynchronize(ctx->stream));
+  ctx->gen_prob.swap(nb[0]);
+  ctx->gen_alias.swap(nb[1]);
+  ctx->gen_perm.swap(nb[2]);
   ctx->gen_seed = seed;
   ctx->gen_s = zipf_s;
   ctx->gen_nranks = nranks;
@@ -712,7 +712,7 @@ int sg_gen_zipf_traces_dev(sg_ctx* ctx, uint64_t seed, uint64_t trace_seed, doub
   uint64_t n = nprog * per_prog;
   if (n == 0) return SG_OK;
   hipLaunchKernelGGL(k_gen_traces, dim3(std::min<uint64_t>(div_up(n, 256), 65536)), dim3(256), 0, ctx->stream, trace_seed,
-                     nranks, prog_base * per_prog, n, ctx->gen_prob, ctx->gen_alias, ctx->gen_perm, d_pcs);
+                     nranks, prog_base * per_prog, n, ctx->gen_prob.p, ctx->gen_alias.p, ctx->gen_perm.p, d_pcs);
   SG_HIP(hipGetLastError());
   return SG_OK;
 }
@@ -734,8 +734,8 @@ int sg_gen_population_traces_dev(sg_ctx* ctx, uint64_t universe_seed, uint64_t p
   const double q = noise * 4294967296.0;
   const uint32_t thr = q >= 4294967295.0 ? 0xFFFFFFFFu : (uint32_t)q;
   hipLaunchKernelGGL(k_gen_pop_traces, dim3(std::min<uint64_t>(div_up(n, 256), 65536)), dim3(256), 0, ctx->stream,
-                     pop_seed, trace_seed, nranks, npop, thr, prog_base, nprog, per_prog, ctx->gen_prob,
-                     ctx->gen_alias, ctx->gen_perm, d_pcs);
+                     pop_seed, trace_seed, nranks, npop, thr, prog_base, nprog, per_prog, ctx->gen_prob.p,
+                     ctx->gen_alias.p, ctx->gen_perm.p, d_pcs);
   SG_HIP(hipGetLastError());
   return SG_OK;
 }

@@ -116,22 +116,22 @@ int host_pipeline(sg_ctx* ctx, uint32_t* mwords, uint32_t* nwords, const uint32_
   int rc = ensure_device(ctx);
   if (rc) return rc;
   // (the staging buffers may still be read by an earlier call's copies)
-  if (ctx->copy_stream) SG_HIP(hipStreamSynchronize(ctx->copy_stream));
+  if (ctx->copy_stream.h) SG_HIP(hipStreamSynchronize(ctx->copy_stream));
   rc = pin_reserve(ctx, 2 * b_slot);
   if (rc) return rc;
   rc = dstage_reserve(ctx, 2 * b_slot + b_flag);
   if (rc) return rc;
-  if (!ctx->copy_stream) {
-    SG_HIP(hipStreamCreateWithFlags(&ctx->copy_stream, hipStreamNonBlocking));
-    for (auto& e : ctx->pipe_ev) SG_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-  }
+  rc = ctx->copy_stream.create(hipStreamNonBlocking);
+  for (auto& e : ctx->pipe_ev)
+    if (!rc) rc = e.create(hipEventDisableTiming);
+  if (rc) return rc;
   ctx->host_copy_bytes = ctx->host_copy_ns = ctx->host_wait_ns = 0;
   ctx->host_threads = (uint64_t)threads;
   char* pin = ctx->pin.p;
   char* dst = ctx->dstage.p;
   uint8_t* dflag = (uint8_t*)(dst + 2 * b_slot);
-  hipEvent_t* ev_dma = ctx->pipe_ev;      // slot k's DMA done (pinned k free, device k filled)
-  hipEvent_t* ev_tri = ctx->pipe_ev + 2;  // slot k's triage done (device k free)
+  const Event* ev_dma = ctx->pipe_ev;     // slot k's DMA done (pinned k free, device k filled)
+  const Event* ev_tri = ctx->pipe_ev + 2;  // slot k's triage done (device k free)
   for (size_t i = 0; i < sl.size(); i++) {
     const HostSlice& s = sl[i];
     const int k = (int)(i & 1);

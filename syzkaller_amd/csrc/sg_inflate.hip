@@ -215,7 +215,7 @@ int inflate_count(sg_ctx* ctx, const uint8_t* d_in, const uint64_t* d_beg, const
     hipLaunchKernelGGL(k_inflate_long<false>, dim3(nl), dim3(kIT), 0, ctx->stream, a);
   }
   hipLaunchKernelGGL(k_inflate_nlong, dim3(1), dim3(1), 0, ctx->stream, (const uint64_t*)sorted, n,
-                     (unsigned long long*)(ctx->own_big + kInflateLongSlot));
+                     (unsigned long long*)&ctx->dev.p->inflate_long_streams);
   SG_HIP(hipGetLastError());
   *d_sorted = sorted;
   return SG_OK;

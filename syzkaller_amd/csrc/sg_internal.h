@@ -4,8 +4,10 @@
 #include <hip/hip_runtime.h>
 
 #include <cstdarg>
+#include <cstddef>
 #include <cstdint>
 #include <cstdio>
+#include <deque>
 #include <map>
 #include <mutex>
 #include <string>
@@ -13,6 +15,7 @@
 
 #include "../../include/syzsig.h"
 #include "sg_buf.h"
+#include "sg_opts.h"
 #include "sg_plan.h"
 
 namespace sg {
@@ -47,6 +50,7 @@ struct KernelTimer {
   };
   std::vector<Rec> pending;
   std::vector<hipEvent_t> pool;
+  std::deque<Event> events;  // the owner of every event of pending and pool
   std::map<std::string, int> ids;
   std::vector<std::string> names;
   std::vector<double> ms;
@@ -77,44 +81,54 @@ struct PrefixSlot {
 };
 constexpr uint32_t kPrefixSlots = 2;
 
-// Context options (sg_ctx_set_option): each regime selects its own path, and
-// an option only forces one, for a test or a measurement.  -1 = the regime's
-// choice.  No option is read from the environment on a call; sg_ctx_create
-// seeds the diagnostics ones (debug_part, bucket_blocks, prefix_pairs,
-// flag_skip) from SG_DEBUG_PART / SG_BUCKET_BLOCKS / SG_PREFIX_PAIRS /
-// SG_FLAG_SKIP for the GPU scripts.
-enum SgOpt : int {
-  kOptBucketBlocks = 0,     // cap of the persistent bucket grid (0: none)
-  kOptPrefixPairs,          // prefix_begin's form when the caller passes -1 (0 kept partitions, 1 pairs)
-  kOptFoldMap,              // one-group fold: -1 by range, 0 never the byte map
-  kOptMinimizeFilter,       // Minimize's value filter: 1 on, 0 off
-  kOptMinimizeFilterRanks,  // Minimize phase A length (0: the default)
-  kOptReportDirect,         // cover report: 1 the global-search form at any size
-  kOptRpcEncodeElems,       // delta encode: -1 by shape, 0 per-list, 1 per-element
-  kOptRpcDecodeBlocks,      // delta decode: -1 by shape, 0 per-list, 1 per-block
-  kOptHostSlice,            // host ingest: entries per record slice (0: the default)
-  kOptHostCopyThreads,      // host ingest: pageable -> pinned copy threads (0: from the CPU quota)
-  kOptM0Filter,             // flags path: the M0 filter (sg_m0filter.hip): -1 by the last batches, 0 never, 1 always tried
-  kOptM0Halves,             // the filter's index per slice in 2^k parts (-1 by its fill, 0..2 forced)
-  kOptExecCompsPath,        // sg_exec_comps: -1 by each call's distinct records, 0 the general path for every call
-  kOptFlagSkip,             // bucket stage in two launches, the second skipping the flag stores of fully queued
-                            // record blocks (sg_bucket.hip): -1 by the last partitioned slice, 0 never, 1 always
-  kOptFlagSkipSplit,        // ... the first launch takes the first 1 / 2^k of the bucket list
-  kOptExecCoverPath,        // sg_exec_cover: -1 by each call's distinct PCs, 0 the general path for every call
-  kOptCount
+namespace sg {
+// The cover fold's routes (sg_triage_runs.hip), counted in CtxDev::tr_route
+enum : uint32_t { kTrCopied = 0, kTrSorted = 1, kTrRanked = 2, kTrForeach = 3, kTrRoutes = 4 };
+// The context's device words: one allocation, zeroed at creation (sg_ctx::dev).
+// A launch site takes &ctx->dev.p->field; the counters among them are read by
+// sg_ctx_counter alone, after a stream sync (its table says what each counts).
+struct CtxDev {
+  uint64_t scalar;          // call-scoped: sg_set_new's, sg_set_count_missing_dev's, has_difference's, a marker's
+  uint32_t m0f_queued;      // queued records of the last counted partitioned slice (sg_m0filter.hip)
+  uint32_t fs_full_blocks;  // full record blocks of the last split bucket launch (sg_bucket.hip)
+  uint32_t owned_big;       // "owned_big_records": zeroed by an ordered-output call, added to by each slice's launch
+  uint32_t tr_wide;         // "triage_runs_wide", and the cover fold's routes after it (zeroed together)
+  uint32_t tr_route[kTrRoutes];
+  uint64_t prio_bad_ids, sha1_long_progs, inflate_long_streams;  // (cumulative over the context's life)
 };
+static_assert(offsetof(CtxDev, scalar) % 8 == 0 && offsetof(CtxDev, prio_bad_ids) % 8 == 0 &&
+                  offsetof(CtxDev, sha1_long_progs) % 8 == 0 && offsetof(CtxDev, inflate_long_streams) % 8 == 0,
+              "64-bit device words are 8-byte aligned");
+static_assert(offsetof(CtxDev, tr_route) == offsetof(CtxDev, tr_wide) + 4, "wide and the routes are zeroed together");
+// ... and the pinned words two of them are copied to, read without a host wait once the event has passed
+struct CtxPinned {
+  uint32_t m0f_queued;      // behind sg_ctx::m0f_ev
+  uint32_t fs_full_blocks;  // behind sg_ctx::fs_ev
+};
+}  // namespace sg
 
+// Nothing here is a raw owning handle: sg_ctx_destroy waits for stream and copy_stream and deletes the
+// context.  The members go in reverse order of declaration, so the two streams stand first: every event is
+// destroyed before the stream it was recorded on, and every buffer before either stream.
 struct sg_ctx {
   int device = 0;
-  int64_t opt[kOptCount] = {0, 0, -1, 1, 0, 0, -1, -1, 0, 0, -1, -1, -1, -1, 3, -1};
+  sg::Stream own_stream;
+  hipStream_t stream = nullptr;  // own_stream, or the caller's (sg_ctx_set_stream)
+  // the host ingest pipeline (sg_host.hip): its copy stream and the events
+  // between the two staging slots' DMA and triage
+  sg::Stream copy_stream;
+  sg::Event pipe_ev[4];
+  int64_t opt[kOptCount];
+  sg_ctx() { for (int i = 0; i < kOptCount; i++) opt[i] = kSgOpts[i].def; }
+  sg::DevBuf<sg::CtxDev> dev;
   // the M0 filter's buffers (lazy, sg_m0filter.hip) and its regime state: the
   // last record slice's outcome (1 filtered, 0 partitioned), the queued
   // records of the last partitioned slice (counted on the device, read back
-  // through m0f_host once m0f_ev has passed: no host wait) and its record
+  // through pinned once m0f_ev has passed: no host wait) and its record
   // count; slices it filtered and fell back on (counters)
-  void* m0f = nullptr;
-  uint32_t* m0f_host = nullptr;  // pinned: the queued-record count
-  hipEvent_t m0f_ev = nullptr;
+  sg::DevBuf<char> m0f;
+  sg::Buf<sg::CtxPinned, true> pinned;  // (lazy, with m0f_ev: m0f_host_alloc)
+  sg::Event m0f_ev;
   int m0f_last = -1;             // -1 nothing yet
   bool m0f_pending = false;
   uint64_t m0f_nrec = 0;
@@ -122,10 +136,10 @@ struct sg_ctx {
   uint64_t m0f_used = 0, m0f_fallback = 0, m0f_survivors = 0;
   uint32_t m0f_backoff = 0, m0f_skip = 0;  // auto: slices not to try after fallbacks (doubling, <= 64)
   // the split bucket stage (flag_skip): launches split, and the summary bits
-  // of the last one (counted on the device, read through m0f_host[4] once
-  // fs_ev has passed)
+  // of the last one (counted on the device, read through pinned once fs_ev
+  // has passed)
   uint64_t fs_used = 0, fs_full_blocks = 0;
-  hipEvent_t fs_ev = nullptr;
+  sg::Event fs_ev;
   bool fs_pending = false;
   int m0f_logh = 0;  // auto: the index in 2^m0f_logh parts per slice (raised when a slice's index overflows)
   // host CPUs this process may use (cgroup cpu.max quota, else the affinity
@@ -147,8 +161,6 @@ struct sg_ctx {
   // rank-merge passes (sg_merge.hip): host arithmetic over the lengths
   uint64_t merge_pairs[4] = {0, 0, 0, 0};
   uint64_t canon_stats[4] = {0, 0, 0, 0};
-  hipStream_t own_stream = nullptr;
-  hipStream_t stream = nullptr;
   // grow-only device workspace and pinned host staging (capacities in bytes;
   // grown by ws_reserve / pin_reserve, contents dropped)
   sg::DevBuf<char> ws;
@@ -157,13 +169,9 @@ struct sg_ctx {
   sg::DevBuf<char> dstage;
   // sg_inflate_batch's outputs on their way to the host (grow-only from 16 MiB; sg_inflate.hip)
   sg::DevBuf<uint8_t> inflate_out;
-  // the host ingest pipeline (sg_host.hip): its copy stream and the events
-  // between the two staging slots' DMA and triage
-  hipStream_t copy_stream = nullptr;
-  hipEvent_t pipe_ev[4] = {};
   // first-owner table and its decreasing key floor; the key space is 2^32 - 1
   // (option owner_key_space lowers it, so tests reach the generation reset)
-  uint32_t* owner = nullptr;
+  sg::DevBuf<uint32_t> owner;  // (lazy: owner_keys)
   uint64_t owner_floor = 0;
   uint64_t owner_key_space = 0xFFFFFFFFull;
   uint64_t owner_resets = 0;
@@ -176,17 +184,9 @@ struct sg_ctx {
   // rebased record offsets of record slices (grow-only, to the exact size: slice_off_reserve)
   sg::DevBuf<uint64_t> slice_off;
   // a batch's record-slice cuts, found on the device (sg_part_triage.hip k_slice_cuts)
-  uint64_t* slice_cuts = nullptr;
-  // small device scalars (counters / flags)
-  uint64_t* dscal = nullptr;
-  // records the last ordered-output call listed for k_own_big (sg_triage.hip):
-  // zeroed by the call, added to by each slice's launch, read by
-  // sg_ctx_counter("owned_big_records") after a stream sync
-  uint32_t* own_big = nullptr;
-  // cached Zipf generator tables (alias method + rank->pc permutation)
-  uint32_t* gen_prob = nullptr;
-  uint32_t* gen_alias = nullptr;
-  uint32_t* gen_perm = nullptr;
+  sg::DevBuf<uint64_t> slice_cuts;
+  // cached Zipf generator tables (alias method + rank->pc permutation; sg_exec.hip gen_tables)
+  sg::DevBuf<uint32_t> gen_prob, gen_alias, gen_perm;
   uint64_t gen_seed = 0;
   double gen_s = 0;
   uint32_t gen_nranks = 0;
@@ -196,8 +196,8 @@ struct sg_ctx {
 
 struct sg_set {
   sg_ctx* ctx = nullptr;
-  uint32_t* words = nullptr;
-  bool owned = true;
+  uint32_t* words = nullptr;  // the bitmap: mem's block, or the caller's (sg_set_wrap_dev)
+  sg::DevBuf<uint32_t> mem;   // empty in a wrapper
 };
 
 // map[hash.Sig]bool on the device (sg_sigset.hip)
@@ -281,13 +281,13 @@ struct ScopedTimer {
 inline uint32_t div_up(uint64_t a, uint64_t b) { return (uint32_t)((a + b - 1) / b); }
 
 // Device exclusive scan of u32 counts into u64 offsets, out[n] = total
-// (sg_ctx.hip).  Uses the workspace tail beyond `ws_used`.
+// (sg_scan.hip).  Uses the workspace tail beyond `ws_used`.
 int scan_counts(sg_ctx* ctx, const uint32_t* d_in, uint64_t* d_out, uint64_t n, size_t ws_used);
 size_t scan_ws_bytes(uint64_t n);
 
-// Members of a set, ascending, into device memory (sg_ctx.hip; ctx lock held).
+// Members of a set, ascending, into device memory (sg_set.hip; ctx lock held).
 int set_export_dev(sg_set* set, uint32_t* d_out, uint64_t cap, uint64_t* total);
-// SignalAdd of device-resident values (sg_ctx.hip; ctx lock held, stream-ordered).
+// SignalAdd of device-resident values (sg_set.hip; ctx lock held, stream-ordered).
 int set_add_dev_locked(sg_set* set, const uint32_t* d_vals, uint64_t n);
 
 // A batch in host memory through pinned double-buffered staging, record
@@ -383,22 +383,9 @@ int exec_signal_body(sg_ctx* ctx, const uint32_t* d_pcs, const uint64_t* d_call_
 // the others get empty lists.  Plans the workspace from 0.
 int exec_cover(sg_ctx* ctx, const uint64_t* d_pcs, const uint64_t* d_call_off, uint64_t ncalls, uint64_t npcs, int dedup,
                uint64_t* d_cov_off, uint32_t* d_cov, uint64_t cov_cap, const uint8_t* sel = nullptr);
-// own_big is 256 B of device counters read by sg_ctx_counter alone: [0]
-// "owned_big_records", [kTrWideSlot] "triage_runs_wide" and after it the four
-// routes of the cover fold, "triage_runs_copied" / "_sorted" / "_ranked" /
-// "_foreach" (sg_triage_runs.hip)
-constexpr uint32_t kTrWideSlot = 16;
-constexpr uint32_t kTrRouteSlot = kTrWideSlot + 1;  // + kTrCopied .. kTrForeach
-enum : uint32_t { kTrCopied = 0, kTrSorted = 1, kTrRanked = 2, kTrForeach = 3, kTrRoutes = 4 };
-// ... and at u32 slot kPrioBadSlot one 64-bit counter, "prio_bad_ids": the ids
-// >= ncalls that sg_prio_table_add_dev has skipped on this context (sg_call_prios.hip)
-constexpr uint32_t kPrioBadSlot = 24;
 // read by sg_ctx_counter as "prio_band_cells" and "prio_short_len"
 constexpr uint32_t kPrioBandCells = 40960;  // u32 cells of a row band: the CU's 160 KiB of LDS
 constexpr uint32_t kPrioShort = 64;         // calls of a program on the band path; longer ones take k_prio_long
-// ... and at u32 slot kSha1LongSlot one 64-bit counter, "sha1_long_progs": the
-// programs that took sg_prog_hash.hip's long path on this context
-constexpr uint32_t kSha1LongSlot = 28;
 // read by sg_ctx_counter as "sha1_long_len" (SG_SHA1_LONG)
 constexpr uint32_t kSha1Long = SG_SHA1_LONG;
 // read by sg_ctx_counter as "triage_runs_sort_cap" and "tinput_chunk"
@@ -483,10 +470,7 @@ uint64_t nametab_names(const sg_nametab* tab);
 // inflate_write, with the workspace untouched since the count: the outputs of
 // the OK streams with a span, when d_out_off[n] <= cap (compared on the
 // device).  n < 2^32.
-// ... at u32 slot kInflateLongSlot of own_big one 64-bit counter,
-// "inflate_long_streams": the streams that took the wave-per-stream path on
-// this context; "inflate_long_len" reads SG_INFLATE_LONG.
-constexpr uint32_t kInflateLongSlot = 32;
+// "inflate_long_len" reads SG_INFLATE_LONG.
 constexpr uint32_t kInflateLong = SG_INFLATE_LONG;
 constexpr uint64_t kInflateMaxOut = 1ull << 33;
 size_t inflate_ws(uint64_t n);
@@ -510,7 +494,7 @@ namespace sgd {
 // triage's bucket (sg_bucket.hip) -- one contiguous 8 KiB slice: the raw top
 // byte of an edge signal is the top byte of hash(prev PC) and would pile the
 // edges of the hottest PCs into a few buckets.  Export walks the words in s
-// order (sg_ctx.hip), so members still come out ascending.
+// order (sg_set.hip), so members still come out ascending.
 __host__ __device__ __forceinline__ uint32_t set_pos(uint32_t s) {
   return ((s & 0x00FFFF00u) << 8) | ((s >> 16) & 0xFF00u) | (s & 0xFFu);
 }

@@ -84,8 +84,7 @@ static size_t m0f_bytes() {
          (uint64_t)kFIdx * kFSpill * 4 + 256ull * kFParts * kFWgCap * 8 +
          256ull * kFParts * 4 + (8ull << kFTableBits);
 }
-static M0F m0f_bind(sg_ctx* ctx) {
-  char* b = (char*)ctx->m0f;
+static M0F m0f_bind(char* b) {
   M0F f;
   f.tab = (uint4*)b;
   b += (uint64_t)kFIdx * kFBuckets * 16;
@@ -478,21 +477,22 @@ __global__ void k_m0_tail_flush(unsigned long long* __restrict__ table, uint32_t
   if (nwords) atomicOr(&nwords[t >> 5], bit);
 }
 
-// pinned words the regimes read without a host wait: [0] the queued records of
-// the last counted partitioned slice (behind m0f_ev), [4] a split launch's
-// full record blocks (behind fs_ev)
+// the pinned words the regimes read without a host wait (CtxPinned), with
+// m0f_ev; the block is adopted last
 int m0f_host_alloc(sg_ctx* ctx) {
-  if (ctx->m0f_host) return SG_OK;
-  SG_HIP(hipHostMalloc((void**)&ctx->m0f_host, 64, hipHostMallocDefault));
-  SG_HIP(hipEventCreateWithFlags(&ctx->m0f_ev, hipEventDisableTiming));
-  return SG_OK;
+  if (ctx->pinned.p) return SG_OK;
+  Buf<CtxPinned, true> nb;
+  int rc = nb.grow_drop(1, nullptr);
+  if (!rc) rc = ctx->m0f_ev.create(hipEventDisableTiming);
+  if (!rc) ctx->pinned.swap(nb);
+  return rc;
 }
 
 // the queued fraction of the last counted partitioned slice, once its copy has landed
 void m0f_poll(sg_ctx* ctx) {
   if (ctx->m0f_pending && hipEventQuery(ctx->m0f_ev) == hipSuccess) {
     ctx->m0f_pending = false;
-    ctx->m0f_queued = (double)*ctx->m0f_host / (double)(ctx->m0f_nrec ? ctx->m0f_nrec : 1);
+    ctx->m0f_queued = (double)ctx->pinned.p->m0f_queued / (double)(ctx->m0f_nrec ? ctx->m0f_nrec : 1);
   }
 }
 
@@ -504,11 +504,14 @@ int m0_filter(sg_ctx* ctx, const BucketPlan& bp, uint32_t* mwords, uint32_t* nwo
   const uint32_t* v1 = bp.at<uint32_t>(ctx, kV1);
   const uint32_t* goff1 = bp.at<uint32_t>(ctx, kO1);
   *done = false;
-  if (!ctx->m0f) {
-    SG_HIP(hipMalloc(&ctx->m0f, m0f_bytes()));
-    SG_HIP(hipMemsetAsync(m0f_bind(ctx).table, 0xFF, 8ull << kFTableBits, ctx->stream));
+  if (!ctx->m0f.p) {  // (adopted once its table is empty)
+    DevBuf<char> nb;
+    const int rc = nb.grow_drop(m0f_bytes(), nullptr);
+    if (rc) return rc;
+    SG_HIP(hipMemsetAsync(m0f_bind(nb.p).table, 0xFF, 8ull << kFTableBits, ctx->stream));
+    ctx->m0f.swap(nb);
   }
-  const M0F f = m0f_bind(ctx);
+  const M0F f = m0f_bind(ctx->m0f.p);
   const uint32_t T = (uint32_t)bp.T;
   SG_HIP(hipMemsetAsync(f.cursor, 0, kFIdx * 4 + 256 + kFIdx * 4, ctx->stream));  // cursors, survivor and spill counts
   // the index in 2^logh parts per slice (auto: 1, or 2 after a part
@@ -587,11 +590,11 @@ int m0f_note_partitioned(sg_ctx* ctx, const uint8_t* d_rec_new, uint64_t nrec) {
   if ((ctx->opt[kOptM0Filter] >= 0 && ctx->opt[kOptFlagSkip] >= 0) || ctx->m0f_pending) return SG_OK;
   int rc = m0f_host_alloc(ctx);
   if (rc) return rc;
-  uint32_t* dcnt = (uint32_t*)ctx->dscal + 32;  // (a device scalar of the context)
+  uint32_t* dcnt = &ctx->dev.p->m0f_queued;
   SG_HIP(hipMemsetAsync(dcnt, 0, 4, ctx->stream));
   hipLaunchKernelGGL(k_count_flags, dim3(std::min<uint64_t>(256, div_up(nrec, 1024))), dim3(256), 0, ctx->stream,
                      d_rec_new, nrec, dcnt);
-  SG_HIP(hipMemcpyAsync(ctx->m0f_host, dcnt, 4, hipMemcpyDeviceToHost, ctx->stream));
+  SG_HIP(hipMemcpyAsync(&ctx->pinned.p->m0f_queued, dcnt, 4, hipMemcpyDeviceToHost, ctx->stream));
   SG_HIP(hipEventRecord(ctx->m0f_ev, ctx->stream));
   ctx->m0f_pending = true;
   ctx->m0f_nrec = nrec;

@@ -1452,12 +1452,12 @@ int sg_has_difference(sg_ctx* ctx, const uint32_t* a, size_t na, const uint32_t*
   uint32_t* db = (uint32_t*)ws_at(ctx, o_b);
   SG_HIP(hipMemcpyAsync(da, a, na * 4, hipMemcpyHostToDevice, ctx->stream));
   if (nb) SG_HIP(hipMemcpyAsync(db, b, nb * 4, hipMemcpyHostToDevice, ctx->stream));
-  SG_HIP(hipMemsetAsync(ctx->dscal, 0, 8, ctx->stream));
+  SG_HIP(hipMemsetAsync(&ctx->dev.p->scalar, 0, 8, ctx->stream));
   hipLaunchKernelGGL(k_has_difference, dim3((uint32_t)std::min<uint64_t>(div_up(na, 256), 4096)), dim3(256), 0,
-                     ctx->stream, da, (uint64_t)na, db, (uint64_t)nb, ctx->dscal);
+                     ctx->stream, da, (uint64_t)na, db, (uint64_t)nb, &ctx->dev.p->scalar);
   SG_HIP(hipGetLastError());
   uint64_t f = 0;
-  SG_HIP(hipMemcpyAsync(&f, ctx->dscal, 8, hipMemcpyDeviceToHost, ctx->stream));
+  SG_HIP(hipMemcpyAsync(&f, &ctx->dev.p->scalar, 8, hipMemcpyDeviceToHost, ctx->stream));
   SG_HIP(hipStreamSynchronize(ctx->stream));
   *out = f ? 1 : 0;
   return SG_OK;

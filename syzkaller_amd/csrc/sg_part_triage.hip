@@ -135,18 +135,19 @@ static int record_slices_host(sg_ctx* ctx, const uint64_t* d_off, uint64_t nrec,
 int record_slices(sg_ctx* ctx, const uint64_t* d_off, uint64_t nrec, std::vector<RecSlice>& out, uint64_t lim) {
   out.clear();
   if (nrec == 0) return SG_OK;
-  if (!ctx->slice_cuts) SG_HIP(hipMalloc(&ctx->slice_cuts, (1 + 4 * (size_t)kCutCap) * 8));
+  const int rc = ctx->slice_cuts.grow_drop(1 + 4 * (size_t)kCutCap, ctx->stream);
+  if (rc) return rc;
   hipLaunchKernelGGL(k_slice_cuts, dim3(1), dim3(64), 0, ctx->stream, d_off, nrec, (uint64_t)ctx->max_launch_recs,
-                     lim, ctx->slice_cuts);
+                     lim, ctx->slice_cuts.p);
   SG_HIP(hipGetLastError());
   std::vector<uint64_t> h(1 + 4 * (size_t)kCutHead);
-  SG_HIP(hipMemcpyAsync(h.data(), ctx->slice_cuts, h.size() * 8, hipMemcpyDeviceToHost, ctx->stream));
+  SG_HIP(hipMemcpyAsync(h.data(), ctx->slice_cuts.p, h.size() * 8, hipMemcpyDeviceToHost, ctx->stream));
   SG_HIP(hipStreamSynchronize(ctx->stream));
   const uint64_t k = h[0];
   if (k > kCutCap) return record_slices_host(ctx, d_off, nrec, out, lim);
   if (k > kCutHead) {
     h.resize(1 + 4 * k);
-    SG_HIP(hipMemcpy(h.data(), ctx->slice_cuts, h.size() * 8, hipMemcpyDeviceToHost));
+    SG_HIP(hipMemcpy(h.data(), ctx->slice_cuts.p, h.size() * 8, hipMemcpyDeviceToHost));
   }
   for (uint64_t j = 0; j < k; j++) out.push_back({h[1 + 4 * j], h[2 + 4 * j], h[3 + 4 * j], h[4 + 4 * j]});
   return SG_OK;

@@ -1063,11 +1063,12 @@ int partition_pass1(sg_ctx* ctx, const uint32_t* d_vals, const uint64_t* d_off, 
   if (rc) return rc;
   P1Args a1{d_vals, d_off, bp.nrec, tstart, trec, T, goff1, hist1, bp.at<uint32_t>(ctx, kV1),
             plane ? bp.at<uint8_t>(ctx, kB1) : nullptr, nullptr, keep};
-  unsigned long long* p1dbg = nullptr;
+  DevBuf<unsigned long long> p1dbg;
   if (dbg) {
-    SG_HIP(hipMalloc(&p1dbg, 64));
-    SG_HIP(hipMemsetAsync(p1dbg, 0, 64, ctx->stream));
-    a1.dbg = p1dbg;
+    rc = p1dbg.grow_drop(8, nullptr);
+    if (rc) return rc;
+    SG_HIP(hipMemsetAsync(p1dbg.p, 0, 64, ctx->stream));
+    a1.dbg = p1dbg.p;
   }
   {
     ScopedTimer tm(ctx, "p1_scatter");
@@ -1077,8 +1078,7 @@ int partition_pass1(sg_ctx* ctx, const uint32_t* d_vals, const uint64_t* d_off, 
   }
   if (dbg) {
     unsigned long long h[8];
-    SG_HIP(hipMemcpy(h, p1dbg, 64, hipMemcpyDeviceToHost));
-    SG_HIP(hipFree(p1dbg));
+    SG_HIP(hipMemcpy(h, p1dbg.p, 64, hipMemcpyDeviceToHost));
     fprintf(stderr, "sg p1_scatter per tile (cycles, wave 0): load+meta %.0f build+lookup %.0f rank %.0f stage %.0f "
             "write %.0f (tiles %llu)\n", (double)h[0] / h[5], (double)h[1] / h[5], (double)h[2] / h[5],
             (double)h[3] / h[5], (double)h[4] / h[5], h[5]);

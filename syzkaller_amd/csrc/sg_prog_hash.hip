@@ -343,7 +343,7 @@ int prog_hashes(sg_ctx* ctx, const uint8_t* d_bytes, const uint64_t* d_off, uint
     hipLaunchKernelGGL(k_sha1_long, dim3((uint32_t)nlong_max), dim3(kHT), 0, ctx->stream, a);
   }
   hipLaunchKernelGGL(k_sha1_count, dim3(1), dim3(1), 0, ctx->stream, (const uint64_t*)sorted, nprogs,
-                     (unsigned long long*)(ctx->own_big + kSha1LongSlot));
+                     (unsigned long long*)&ctx->dev.p->sha1_long_progs);
   SG_HIP(hipGetLastError());
   return SG_OK;
 }

@@ -424,12 +424,12 @@ int sg_shard_owners_dev(sg_ctx* ctx, const uint32_t* d_pairs, uint64_t npairs, u
   {
     ScopedTimer tm(ctx, "shard_owner");
     hipLaunchKernelGGL(k_shard_claim, dim3(grid), dim3(256), 0, ctx->stream, (const uint2*)d_pairs, npairs,
-                       ctx->owner, key_lo);
+                       ctx->owner.p, key_lo);
   }
   {
     ScopedTimer tm(ctx, "shard_resolve");
     hipLaunchKernelGGL(k_shard_resolve, dim3(std::min<uint64_t>(div_up(npairs, (uint64_t)kResT * kResPer), 4096)),
-                       dim3(kResT), 0, ctx->stream, (const uint2*)d_pairs, npairs, (const uint32_t*)ctx->owner, key_lo,
+                       dim3(kResT), 0, ctx->stream, (const uint2*)d_pairs, npairs, (const uint32_t*)ctx->owner.p, key_lo,
                        rec_flag, d_new_vals, (unsigned long long*)d_nnew);
     hipLaunchKernelGGL(k_pack_flags, dim3(div_up(div_up(nrec_total, 32), 256)), dim3(256), 0, ctx->stream,
                        (const uint8_t*)rec_flag, nrec_total, d_rec_bits);

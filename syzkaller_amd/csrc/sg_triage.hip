@@ -1000,7 +1000,7 @@ static int owned_outputs(sg_ctx* ctx, uint32_t* mwords, uint32_t* nwords, const 
     set_error("ordered triage: a batch holds < 2^32 signal entries and < 2^32 - 1 records");
     return SG_EINVAL;
   }
-  SG_HIP(hipMemsetAsync(ctx->own_big, 0, 4, ctx->stream));  // (read by sg_ctx_counter only: no wait here)
+  SG_HIP(hipMemsetAsync(&ctx->dev.p->owned_big, 0, 4, ctx->stream));  // (read by sg_ctx_counter only: no wait here)
   if (nrec && d_rec_new) SG_HIP(hipMemsetAsync(d_rec_new, 0, nrec, ctx->stream));
   if (nvals == 0) {
     if (d_out_off) SG_HIP(hipMemsetAsync(d_out_off, 0, (nrec + 1) * 8, ctx->stream));
@@ -1089,7 +1089,7 @@ static int owned_outputs(sg_ctx* ctx, uint32_t* mwords, uint32_t* nwords, const 
     hipLaunchKernelGGL(k_own_bounds_search, dim3(div_up(nr, 256)), dim3(256), 0, ctx->stream, (const uint64_t*)sorted,
                        np, (uint32_t)nr, po);
     OwnArgs oa{d_vals, roff, e0, (uint32_t)nr, sorted, po, d_rec_new ? d_rec_new + r0 : nullptr, s.dmask, big, nvals,
-               big + nr + 1, ctx->own_big};
+               big + nr + 1, &ctx->dev.p->owned_big};
     SG_HIP(hipMemsetAsync(big + nr + 1, 0, 4, ctx->stream));
     if (aligned)
       rc = launch_own<true>(ctx, oa, nr, dedup);
@@ -1351,7 +1351,7 @@ int sg_merge_poll(sg_ctx* ctx, sg_set* mgr_max, const uint32_t* a_vals, const ui
   int rc = ensure_device(ctx);
   if (rc) return rc;
   if (nv == 0) {
-    SG_HIP(hipMemsetAsync(ctx->own_big, 0, 4, ctx->stream));  // (no record listed)
+    SG_HIP(hipMemsetAsync(&ctx->dev.p->owned_big, 0, 4, ctx->stream));  // (no record listed)
     for (size_t k = 0; k <= npoll; k++) new_off[k] = 0;
     return SG_OK;
   }
@@ -1435,7 +1435,7 @@ int sg_minimize(sg_ctx* ctx, const uint32_t* vals, const uint64_t* off, size_t n
     ScopedTimer tm(ctx, "min_claim");
     SG_HIP(hipMemsetAsync(dtouch, 0, kSetBytes, ctx->stream));
     hipLaunchKernelGGL(k_min_claim, dim3((uint32_t)R), dim3(kBlock), 0, ctx->stream, (const uint32_t*)din,
-                       (const uint64_t*)doff, (const uint32_t*)dord, key_lo, (uint32_t)(key_lo + n), ctx->owner,
+                       (const uint64_t*)doff, (const uint32_t*)dord, key_lo, (uint32_t)(key_lo + n), ctx->owner.p,
                        dtouch);
     if (R < n) {
       uint32_t* dfilt = (uint32_t*)ws_at(ctx, o_fs);
@@ -1462,7 +1462,7 @@ int sg_minimize(sg_ctx* ctx, const uint32_t* vals, const uint64_t* off, size_t n
       hipLaunchKernelGGL(k_min_filter, dim3(16, (uint32_t)R - 1), dim3(kBlock), 0, ctx->stream, (const uint32_t*)din,
                          (const uint64_t*)doff, (const uint32_t*)dord, (const uint32_t*)dfirst, dfilt);
       MinClaimF f{(const uint32_t*)din, droff, dsoff, nr, nel, (uint32_t)(key_lo + R), (uint32_t)(key_lo + n),
-                  ctx->owner, dtouch, dfilt, dwr};
+                  ctx->owner.p, dtouch, dfilt, dwr};
       if (nel) {
       int per_cu = 0, cus = 0;
       if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void*)k_min_claim_f, kFT, 0) != hipSuccess ||
@@ -1477,7 +1477,7 @@ int sg_minimize(sg_ctx* ctx, const uint32_t* vals, const uint64_t* off, size_t n
   {
     ScopedTimer tm(ctx, "min_owners");
     hipLaunchKernelGGL(k_min_owners, dim3(4096), dim3(256), 0, ctx->stream, (const uint32_t*)dtouch,
-                       (const uint32_t*)ctx->owner, key_lo, (const uint32_t*)dord, dflag);
+                       (const uint32_t*)ctx->owner.p, key_lo, (const uint32_t*)dord, dflag);
   }
   SG_HIP(hipGetLastError());
   // selected indices in processing order: compact order[k] where flag[order[k]]

@@ -476,10 +476,9 @@ int triage_runs(sg_ctx* ctx, sg_set* corpus, const TrIo& io, const TrPlan& p) {
   uint8_t* covsrc = dstage_at<uint8_t>(ctx, p.covsrc);
   uint32_t* buf0 = dstage_at<uint32_t>(ctx, p.buf0);
   uint32_t* buf1 = dstage_at<uint32_t>(ctx, p.buf1);
-  uint32_t* wide = ctx->own_big + kTrWideSlot;
+  uint32_t* wide = &ctx->dev.p->tr_wide;
   const dim3 b(256);
   int rc;
-  static_assert(kTrRouteSlot == kTrWideSlot + 1, "wide and the routes are zeroed together");
   SG_HIP(hipMemsetAsync(wide, 0, 4 * (1 + kTrRoutes), ctx->stream));  // (read by sg_ctx_counter only: no wait here)
   // 1. the calls that count, the truncated PCs
   SG_HIP(hipMemsetAsync(sel, 0, ncalls + 1, ctx->stream));
@@ -533,7 +532,7 @@ int triage_runs(sg_ctx* ctx, sg_set* corpus, const TrIo& io, const TrPlan& p) {
     ScopedTimer tm(ctx, "triage_runs_cover");
     CoverArgs ca{io.nruns, ncalls,      npcs,   io.minimized, selcall, io.prog_off, io.call_off, xcov_off, xcov, state,
                  cur_len,  io.status,   newlen, covlen,       covsrc,  {buf0, buf1},
-                 wide,     ctx->own_big + kTrRouteSlot};
+                 wide,     ctx->dev.p->tr_route};
     hipLaunchKernelGGL(k_tr_cover, dim3((uint32_t)n), dim3(kTB), 0, ctx->stream, ca);
   }
   SG_HIP(hipGetLastError());
