@@ -82,7 +82,9 @@ int sg_ctx_kernel_time(sg_ctx* ctx, const char* name, double* ms, uint64_t* laun
  * queued fraction of the last partitioned slice, x1000, that auto reads),
  * "m0_filter_halves_log" (the index parts per slice, log2, auto uses now);
  * "flag_skip_used" (bucket launches run in two phases), "flag_skip_full_blocks"
- * (fully queued 4096-record blocks the last of them found after its first phase);
+ * (fully queued 4096-record blocks the last of them found after its first phase),
+ * "flag_skip_all_flagged" (those that found every block so and ran their second
+ * phase without the owner map);
  * "hints_candidates" (the last sg_hints_replacers* call's (slot, pair)
  * matches, before deduplication); "exec_comps_general" (the calls the last
  * sg_exec_comps* call sent down its general path), "exec_comps_fast_cap"

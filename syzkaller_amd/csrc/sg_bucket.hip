@@ -36,6 +36,11 @@ struct BucketArgs {
   // win 1 takes entries [0, A), win 2 [A, *nlist), 0 all of them
   uint32_t win, win_shift;
   const uint32_t* fsum;    // nullable: bit per kFsRecs records of the launch, set: every flag of the block is set already
+  // the second phase of a split launch: all-flagged iff *fs_cnt (the summary's full blocks) == fs_nblk (the
+  // launch's blocks); then k_bucket_sets takes window 2 and counts itself in *fs_all, else k_bucket<.., kSkip>
+  const uint32_t* fs_cnt;
+  uint32_t fs_nblk;
+  uint32_t* fs_all;
   uint64_t* dbg;          // diagnostics (k_bucket<true>): per block {start, end, buckets, rounds, 4 phase cycle sums}
   // candidate emission (sharded triage, sg_shard.hip; the prefix protocol's
   // begin): instead of flagging records and updating maxSignal, every
@@ -317,6 +322,7 @@ __device__ __forceinline__ uint32_t take_ticket(uint32_t* p) { return atomicAdd(
 template <bool kDbg, int kEmit, bool kSkip = false>
 __global__ __launch_bounds__(kBThreads) __attribute__((amdgpu_waves_per_eu(kBWaves))) void k_bucket(BucketArgs a) {
   static_assert(!kSkip || kEmit == 0, "the summary guards flag stores");
+  if (kSkip && *a.fs_cnt == a.fs_nblk) return;  // all-flagged: k_bucket_sets has this window
   __shared__ uint32_t fsum[kSkip ? kFsWords : 1];
   __shared__ uint32_t mslice[kBucketWords];
   __shared__ uint32_t nbits[kBucketWords];
@@ -747,6 +753,172 @@ __global__ __launch_bounds__(kBThreads) __attribute__((amdgpu_waves_per_eu(kBWav
   }
 }
 
+// ------------------------------------------------------------ sets only ---
+// The second phase of a split launch whose records are all flagged already
+// (sg_part.h): no flag store of the window can change anything, so what is
+// left of a bucket is its set update, the bits of its entries that are not in
+// mwords | owords.  That needs no owner: no map, no records, no group
+// boundaries, and the bucket cannot spill.  Same list, window, tickets and
+// entry loads as k_bucket; per bucket the slice and a zeroed new-bits slice in
+// LDS, a test and an LDS OR per candidate entry, and the write-back of the
+// words that gained bits from their only writer.  Two barriers per bucket:
+// after its rounds, and after the write-back that also installs the next
+// bucket's slice (a thread owns the same kWPT words of both).
+// (The slice read decides the OR.  ORing every live entry and masking at the
+// write-back needs no slice in LDS but three times the LDS atomics: measured
+// slower, 1.58 against 1.37 ms per C2 bucket stage in alternated runs of one
+// job)
+constexpr int kSQ = 2;                           // 16-B loads per thread and round, each contiguous over the workgroup
+constexpr uint32_t kSQuad = kBThreads * 4;       // entries of one of them
+constexpr uint32_t kSRound = kSQuad * kSQ;
+struct SetsPre {  // a bucket's first loads, held in registers
+  uint32_t msw[kWPT];
+  uint32_t nsw[kWPT];
+};
+
+__device__ __forceinline__ uint32_t sets_pos(uint32_t base, int j) { return base + j * kSQuad + threadIdx.x * 4; }
+
+// (base 4-aligned; a quad is loaded when its first entry is below hi: the
+// padded pass-2 buffer covers the rest of it, as in bucket_round_load)
+__device__ __forceinline__ void sets_round_load(const BucketArgs& a, uint32_t base, uint32_t hi, v4u32 (&x)[kSQ]) {
+#pragma unroll
+  for (int j = 0; j < kSQ; j++) {
+    x[j] = v4u32{0, 0, 0, 0};
+    const uint32_t p = sets_pos(base, j);
+    if (p < hi) x[j] = __builtin_nontemporal_load(reinterpret_cast<const v4u32*>(a.in + p));
+  }
+}
+
+__device__ __forceinline__ void sets_pre_load(const BucketArgs& a, uint32_t b, SetsPre& P) {
+  const uint64_t w0 = bucket_word(b, kWPT * threadIdx.x);
+  wvec m = *reinterpret_cast<const wvec*>(a.mwords + w0);
+  if (a.owords) m |= *reinterpret_cast<const wvec*>(a.owords + w0);
+  wvec nw = {};
+  if (a.nwords) nw = *reinterpret_cast<const wvec*>(a.nwords + w0);
+#pragma unroll
+  for (int j = 0; j < kWPT; j++) {
+    P.msw[j] = m[j];
+    P.nsw[j] = nw[j];
+  }
+}
+
+__global__ __launch_bounds__(kBThreads) __attribute__((amdgpu_waves_per_eu(8))) void k_bucket_sets(BucketArgs a) {
+  if (*a.fs_cnt != a.fs_nblk) return;  // some record is not flagged yet: k_bucket<.., kSkip> has this window
+  __shared__ alignas(16) uint32_t mslice[kBucketWords];
+  __shared__ alignas(16) uint32_t nbits[kBucketWords];
+  __shared__ uint32_t sh_b[2];
+  __shared__ uint4 sh_q[2];
+  const int tid = threadIdx.x;
+  uint32_t nl = *a.nlist, l0 = 0;
+  if (a.win) {
+    const uint32_t na = nl >> a.win_shift;
+    l0 = a.win == 2 ? na : 0;
+    nl = a.win == 2 ? nl - na : na;
+  }
+  // list entries and tickets as in k_bucket
+  uint32_t pend_t = 0;
+  if (tid == 0) {
+    uint4 q0 = make_uint4(0, 0, 0, 0), q1 = make_uint4(0, 0, 0, 0);
+    sh_b[0] = list_bucket(a, blockIdx.x, l0, nl, &q0);
+    sh_q[0] = q0;
+    sh_b[1] = list_bucket(a, gridDim.x + blockIdx.x, l0, nl, &q1);
+    sh_q[1] = q1;
+    pend_t = take_ticket(a.ticket);
+    if (blockIdx.x == 0) atomicAdd(a.fs_all, 1u);  // "flag_skip_all_flagged"
+  }
+  __syncthreads();
+  uint32_t b = uni(sh_b[0]), b1 = uni(sh_b[1]);
+  uint4 q = uni(sh_q[0]), q1 = uni(sh_q[1]);
+  if (b >= kNumBuckets) return;
+  v4u32 x[kSQ], y[kSQ];
+  SetsPre P;
+  sets_round_load(a, q.x & ~3u, q.y, x);
+  sets_pre_load(a, b, P);
+  // the bucket's words kWPT tid .. + kWPT - 1: mwords | owords into the slice (read back at the bucket's end),
+  // newSignal's held in registers
+  wvec ns;
+  {
+    wvec mv;
+#pragma unroll
+    for (int j = 0; j < kWPT; j++) {
+      mv[j] = P.msw[j];
+      ns[j] = P.nsw[j];
+    }
+    reinterpret_cast<wvec*>(mslice)[tid] = mv;
+    reinterpret_cast<wvec*>(nbits)[tid] = wvec{};
+  }
+  __syncthreads();
+  while (b < kNumBuckets) {
+    const uint32_t lo = q.x, hi = q.y;
+    // thread 0: resolve the pending ticket (published after the rounds) and take the next one
+    uint32_t pend_b = kNumBuckets;
+    uint4 pend_q = make_uint4(0, 0, 0, 0);
+    if (tid == 0) {
+      pend_b = list_bucket(a, 2 * gridDim.x + pend_t, l0, nl, &pend_q);
+      pend_t = take_ticket(a.ticket);
+    }
+    for (uint32_t base = lo & ~3u;;) {
+      // the next round in flight: this bucket's, or the next bucket's first with its words
+      const uint32_t next = base + kSRound;
+      const bool last = next >= hi;
+      if (!last || b1 < kNumBuckets) sets_round_load(a, last ? q1.x & ~3u : next, last ? q1.y : hi, y);
+      if (last && b1 < kNumBuckets) sets_pre_load(a, b1, P);
+#pragma unroll
+      for (int j = 0; j < kSQ; j++) {  // a quad at a time: its LDS reads issued before the first use
+        uint32_t mw[4];
+#pragma unroll
+        for (int u = 0; u < 4; u++) mw[u] = mslice[x[j][u] >> 21];
+#pragma unroll
+        for (int u = 0; u < 4; u++) {
+          const uint32_t i = sets_pos(base, j) + u, v = x[j][u];
+          const uint32_t bit = 1u << ((v >> 16) & 31);
+          if (i >= lo && i < hi && !(mw[u] & bit)) atomicOr(&nbits[v >> 21], bit);
+        }
+      }
+      // (after the last round too: then the next bucket's first round, if there is one)
+#pragma unroll
+      for (int j = 0; j < kSQ; j++) x[j] = y[j];
+      if (last) break;
+      base = next;
+    }
+    if (tid == 0) {  // the bucket after next
+      sh_b[0] = pend_b;
+      sh_q[0] = pend_q;
+    }
+    __syncthreads();  // every OR of the bucket is done
+    {
+      // words kWPT tid ..: this block is their only writer
+      const uint64_t w0 = bucket_word(b, kWPT * tid);
+      const wvec nb = reinterpret_cast<const wvec*>(nbits)[tid];
+      const wvec cm = reinterpret_cast<const wvec*>(mslice)[tid];
+      uint32_t any = 0;
+#pragma unroll
+      for (int j = 0; j < kWPT; j++) {
+        any |= nb[j];
+        if (nb[j]) {
+          a.mwords[w0 + j] = cm[j] | nb[j];
+          if (a.nwords) a.nwords[w0 + j] = ns[j] | nb[j];
+        }
+      }
+      if (any) reinterpret_cast<wvec*>(nbits)[tid] = wvec{};
+      if (b1 < kNumBuckets) {  // the next bucket's words (P was loaded in the last round)
+        wvec mv;
+#pragma unroll
+        for (int j = 0; j < kWPT; j++) {
+          mv[j] = P.msw[j];
+          ns[j] = P.nsw[j];
+        }
+        reinterpret_cast<wvec*>(mslice)[tid] = mv;
+      }
+    }
+    b = b1;
+    q = q1;
+    b1 = uni(sh_b[0]);
+    q1 = uni(sh_q[0]);
+    __syncthreads();  // the slices stand; sh_b[0] / sh_q[0] are read
+  }
+}
+
 // Buckets with too many distinct candidates: a direct first-owner table over
 // one eighth of the bucket (8192 signals, 32 KiB of LDS) per job; the
 // (bucket, eighth) jobs are independent (each owns its eighth's 256 bitmap
@@ -944,11 +1116,27 @@ int buckets_one(sg_ctx* ctx, const BucketPlan& bp, uint32_t* mwords, uint32_t* n
       ba.win = 2;
       ba.ticket++;
       ba.fsum = fsum;  // (the direct-table kernel below honours it too)
+      // Both forms of the second phase over the window; each reads the
+      // summary's count first and returns unless the launch is its case (the
+      // decision stays on the device: the call is stream-ordered).  Every
+      // record flagged: the map-free k_bucket_sets, with a ticket of its own.
+      ba.fs_cnt = fcnt;
+      ba.fs_nblk = (uint32_t)div_up(nrec, kFsRecs);
+      ba.fs_all = &ctx->dev.p->fs_all_flagged;
       hipLaunchKernelGGL((k_bucket<false, 0, true>), dim3(bgrid), dim3(kBThreads), 0, ctx->stream, ba);
+      BucketArgs bs = ba;
+      bs.ticket = ba.ticket + 1;
+      uint32_t sgrid = persistent_grid(ctx, (const void*)k_bucket_sets, kBThreads);
+      if (cap_blocks > 0 && (uint64_t)cap_blocks < sgrid) sgrid = (uint32_t)cap_blocks;
+      hipLaunchKernelGGL(k_bucket_sets, dim3(sgrid), dim3(kBThreads), 0, ctx->stream, bs);
     }
   }
   if (split) {
-    SG_HIP(hipMemcpyAsync(&ctx->pinned.p->fs_full_blocks, fcnt, 4, hipMemcpyDeviceToHost, ctx->stream));
+    // (both words: the last launch's full blocks and the context's all-flagged launches so far)
+    static_assert(offsetof(CtxDev, fs_all_flagged) == offsetof(CtxDev, fs_full_blocks) + 4 &&
+                      offsetof(CtxPinned, fs_all_flagged) == offsetof(CtxPinned, fs_full_blocks) + 4,
+                  "the two words travel in one copy");
+    SG_HIP(hipMemcpyAsync(&ctx->pinned.p->fs_full_blocks, fcnt, 8, hipMemcpyDeviceToHost, ctx->stream));
     SG_HIP(hipEventRecord(ctx->fs_ev, ctx->stream));
     ctx->fs_pending = true;
     ctx->fs_used++;

@@ -363,7 +363,7 @@ int sg_ctx_get_option(sg_ctx* ctx, const char* key, int64_t* out) {
 namespace {
 typedef uint64_t Quad[4];
 enum CtrKind { kHost, kHost4, kDev32, kDev64, kConst, kCalc };
-enum CtrCalc : uint64_t { kOwnerFloor, kM0Queued, kM0Logh, kCpuQuota, kFsFullBlocks, kWsBytes };
+enum CtrCalc : uint64_t { kOwnerFloor, kM0Queued, kM0Logh, kCpuQuota, kFsFullBlocks, kFsAllFlagged, kWsBytes };
 #define SG_DEV(field) offsetof(CtxDev, field)
 struct Counter {
   const char* name;
@@ -389,6 +389,7 @@ const Counter kCounters[] = {
     {"m0_filter_halves_log", kCalc, kM0Logh},      // the index's parts per slice (log2) the auto regime uses now
     {"flag_skip_used", kHost, 0, &sg_ctx::fs_used},     // bucket launches run in two phases (sg_bucket.hip)
     {"flag_skip_full_blocks", kCalc, kFsFullBlocks},    // fully queued record blocks the last of them found
+    {"flag_skip_all_flagged", kCalc, kFsAllFlagged},    // ... and those whose second phase ran map-free (k_bucket_sets)
     {"hints_candidates", kHost, 0, &sg_ctx::hints_cands},  // the last sg_hints_replacers* call's matches (sg_hints.hip)
     {"exec_comps_general", kHost, 0, &sg_ctx::exec_comps_general},  // the last sg_exec_comps* call's general-path calls
     {"exec_cover_general", kHost, 0, &sg_ctx::exec_cover_general},  // the last sg_exec_cover* call's general-path calls
@@ -424,10 +425,11 @@ const Counter kCounters[] = {
 };
 
 int counter_calc(sg_ctx* ctx, uint64_t which, uint64_t* out) {
-  if (which == kFsFullBlocks && ctx->fs_pending) {  // (the last split launch's count may still be on its way)
+  if ((which == kFsFullBlocks || which == kFsAllFlagged) && ctx->fs_pending) {  // (the last split launch's words may still be on their way)
     SG_HIP(hipEventSynchronize(ctx->fs_ev));
     ctx->fs_pending = false;
     ctx->fs_full_blocks = ctx->pinned.p->fs_full_blocks;
+    ctx->fs_all_flagged = ctx->pinned.p->fs_all_flagged;
   }
   switch (which) {
     case kOwnerFloor: *out = ctx->owner.p ? ctx->owner_floor : ctx->owner_key_space; break;
@@ -435,6 +437,7 @@ int counter_calc(sg_ctx* ctx, uint64_t which, uint64_t* out) {
     case kM0Logh: *out = (uint64_t)ctx->m0f_logh; break;
     case kCpuQuota: *out = (uint64_t)(ctx->cpu_quota * 1000.0 + 0.5); break;
     case kFsFullBlocks: *out = ctx->fs_full_blocks; break;
+    case kFsAllFlagged: *out = ctx->fs_all_flagged; break;
     case kWsBytes: *out = ctx->ws.cap; break;
   }
   return SG_OK;

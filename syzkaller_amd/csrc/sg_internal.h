@@ -91,6 +91,7 @@ struct CtxDev {
   uint64_t scalar;          // call-scoped: sg_set_new's, sg_set_count_missing_dev's, has_difference's, a marker's
   uint32_t m0f_queued;      // queued records of the last counted partitioned slice (sg_m0filter.hip)
   uint32_t fs_full_blocks;  // full record blocks of the last split bucket launch (sg_bucket.hip)
+  uint32_t fs_all_flagged;  // ... and the split launches whose second phase ran map-free (cumulative; copied with it)
   uint32_t owned_big;       // "owned_big_records": zeroed by an ordered-output call, added to by each slice's launch
   uint32_t tr_wide;         // "triage_runs_wide", and the cover fold's routes after it (zeroed together)
   uint32_t tr_route[kTrRoutes];
@@ -104,6 +105,7 @@ static_assert(offsetof(CtxDev, tr_route) == offsetof(CtxDev, tr_wide) + 4, "wide
 struct CtxPinned {
   uint32_t m0f_queued;      // behind sg_ctx::m0f_ev
   uint32_t fs_full_blocks;  // behind sg_ctx::fs_ev
+  uint32_t fs_all_flagged;  // likewise (one copy)
 };
 }  // namespace sg
 
@@ -137,8 +139,9 @@ struct sg_ctx {
   uint32_t m0f_backoff = 0, m0f_skip = 0;  // auto: slices not to try after fallbacks (doubling, <= 64)
   // the split bucket stage (flag_skip): launches split, and the summary bits
   // of the last one (counted on the device, read through pinned once fs_ev
-  // has passed)
-  uint64_t fs_used = 0, fs_full_blocks = 0;
+  // has passed), with the launches so far whose second phase ran map-free
+  // (every record flagged by the first; the device's running count, same copy)
+  uint64_t fs_used = 0, fs_full_blocks = 0, fs_all_flagged = 0;
   sg::Event fs_ev;
   bool fs_pending = false;
   int m0f_logh = 0;  // auto: the index in 2^m0f_logh parts per slice (raised when a slice's index overflows)

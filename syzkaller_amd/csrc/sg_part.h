@@ -107,6 +107,9 @@ __device__ __forceinline__ uint32_t last_le(const uint32_t* row, uint32_t lo, ui
 // Nothing clears a flag within a call, so a store to such a record would
 // rewrite a 1: the second launch (kSkip) and the direct-table kernel leave it
 // out.  At the launch maximum of 2^24 records the summary is 512 B.
+// When every block's bit is set (the count of set bits equals the launch's
+// blocks), no flag store is left at all and the second launch's work is the
+// set update alone: k_bucket_sets takes it, without the owner map.
 constexpr uint32_t kFsBits = 12, kFsRecs = 1u << kFsBits;
 constexpr uint32_t kFsWords = (uint32_t)(kMaxLaunchRecords >> kFsBits) / 32;
 static_assert(kFsWords * 32ull * kFsRecs == kMaxLaunchRecords, "summary covers a launch's records");
@@ -132,7 +135,7 @@ enum Region : int {
   kCD, kDT,            // per pass-2 block: chunk descriptor, tile range
   kBD, kGB,            // buckets: descriptors {lo, hi, c0, nch}, group boundaries [bucket][group]
   kH2, kO2, kV2,       // pass 2: histogram [byte][chunk], its scan, entries
-  kSP, kTK,            // spilled buckets (count, list); two tickets (a split launch's phases) + record-flag summary
+  kSP, kTK,            // spilled buckets (count, list); four ticket words (a split launch's phases: 0, 1 and, map-free, 2) + record-flag summary
   kBN, kBP,            // bucket non-empty flags, their scan ([kNumBuckets] = the list's length)
   kLB, kLQ,            // the non-empty buckets in bucket order, and their descriptors
   kSC, kKM,            // scan32's block sums; trace batches' kept-entry words
