@@ -115,6 +115,12 @@ int sg_ctx_kernel_time(sg_ctx* ctx, const char* name, double* ms, uint64_t* laun
  * sg_inflate_batch*, sg_db_open on this context since it was created, once
  * per call that counted them; counted on the device, read here after a stream
  * sync) and "inflate_long_len" (constant: SG_INFLATE_LONG);
+ * "deflate_long_streams" (likewise for sg_deflate_batch*, sg_db_serialize and
+ * sg_db_compact) and "deflate_long_len" (constant: SG_DEFLATE_LONG);
+ * "deflate_stored_streams", "deflate_fixed_streams" and
+ * "deflate_dynamic_streams" (the streams of the last such call per form,
+ * summing to its streams; a database call counts a deletion or an empty value
+ * as the two-byte fixed stream it does not write);
  * "owned_big_records" (the
  * records the last
  * ordered-output call -- sg_triage_batch[_dev] with diff lists, sg_merge_poll
@@ -1313,9 +1319,9 @@ int sg_hubcorpus_purge(sg_hubcorpus* h, sg_sigset* const* mgrs, size_t nmgrs, ui
  * compress/flate; the hub's loadDB (syz-hub/state/state.go:83-110) and the
  * manager's start-up (syz-manager/manager.go:178-216) wait for it before they
  * look at a single program.  Every value is its own raw DEFLATE stream (RFC
- * 1951), so a corpus is as many independent decoders as it has records.  Only
- * the read side is here: Save, Delete, Flush and compact need a compressor and
- * stay with the caller.
+ * 1951), so a corpus is as many independent decoders as it has records.  The
+ * write side (Save, Delete, Flush and compact: "the corpus database, written"
+ * below) has its compressor in csrc/sg_deflate.h.
  *
  * The decoder (csrc/sg_inflate.h, one source for host and device) follows
  * zlib 1.2.11's inflate of a raw stream.  A stream's status:
@@ -1427,6 +1433,79 @@ int sg_db_device(sg_db* db, const uint8_t** d_texts, const uint64_t** d_text_off
  * another context is SG_EINVAL, as are a NULL db or max_seq and bad NULL with
  * live records.  One wait. */
 int sg_db_verify(sg_db* db, sg_nametab* tab, uint8_t* bad, uint64_t* max_seq);
+
+/* ---- the corpus database, written: deflate, serializeRecord and compact ------ */
+/* pkg/db's write side: serializeRecord (pkg/db/db.go:137-165) deflates a value
+ * at flate.BestCompression, on one thread; compact() (:95-116) does that to
+ * every live record, and Flush (:75-93) reaches it from minimizeCorpus under
+ * mgr.mu (syz-manager/manager.go:786-795), from the end of the hub's loadDB
+ * (syz-hub/state/state.go:106) and from purgeCorpus (:349-351); Open reaches it
+ * when nine tenths of the file is dead (:48-50); the hub's addInputs
+ * (state.go:310-336) is a run of Saves and two Flushes.
+ *
+ * The encoder (csrc/sg_deflate.h, one source for host and device) writes a
+ * value as ONE block, fixed or dynamic, or as a chain of stored blocks of at
+ * most 65,535 bytes, whichever is shortest in bytes (of equal lengths: stored
+ * before fixed before dynamic); the last block carries BFINAL and nothing
+ * follows it.  The empty input is 03 00.  The parse is LZ77 with a 512-entry
+ * table of last positions, greedy, one probe; the dynamic code's lengths are
+ * Shannon lengths made complete, not Huffman's.  Go's reader takes any valid
+ * stream inside its LimitedReader (:242); equality with the bytes Go's
+ * flate.Writer would have written is no goal, and parity with it stays
+ * unpinned as said above.  A stream's bytes depend on its input bytes alone:
+ * not on the batch, not on the side that ran it.
+ * An input longer than SG_DEFLATE_LONG bytes gets a wave to itself; the context
+ * counter "deflate_long_streams" counts them, "deflate_long_len" is the
+ * constant. */
+#define SG_DEFLATE_LONG 65536
+/* The stored form's length, len + 5 * max(1, ceil(len / 65535)): what no
+ * stream of len input bytes exceeds.  Host only. */
+size_t sg_deflate_bound(size_t len);
+/* The encoder on the host: no device, no context (as sg_db_scan has none), for
+ * a lone Save (manager.go:921-922) whose bytes are then what the device would
+ * have written.  A CSR of inputs in, a CSR of streams out: out_off (n + 1) is
+ * always written, *nout is always the total, and out is written only when it
+ * is <= cap (out NULL with cap 0 is the count form).  SG_EINVAL: a NULL out_off
+ * or nout; out NULL with cap > 0; what sg_prog_hashes rejects of a CSR; an
+ * input of more than 2^32 - 2^20 bytes. */
+int sg_deflate_host(const uint8_t* in, const uint64_t* in_off, size_t n, uint64_t* out_off, uint8_t* out, size_t cap,
+		    size_t* nout);
+/* The same on the device, a lane per stream, with sg_inflate_batch's
+ * conventions.  SG_EINVAL, before the context is touched: a NULL ctx, and what
+ * sg_deflate_host rejects.  SG_EINVAL after the count phase, with nothing
+ * written: 2^33 output bytes or more.  SG_ENODEV without a device.  Two waits. */
+int sg_deflate_batch(sg_ctx* ctx, const uint8_t* in, const uint64_t* in_off, size_t n, uint64_t* out_off, uint8_t* out,
+		     size_t cap, size_t* nout);
+/* Device form (nbytes = the bytes in d_in): every pointer is device memory,
+ * stream-ordered, nothing is read back; d_out_off[n] is the total and d_out is
+ * written only when it is <= cap.  Offsets are clamped as sg_inflate_batch_dev
+ * clamps them; an input is cut at 2^32 - 2^20 bytes.  SG_EINVAL: a NULL ctx or
+ * d_out_off; d_in_off NULL with n > 0; d_in NULL with nbytes > 0; d_out NULL
+ * with cap > 0; n >= 2^32. */
+int sg_deflate_batch_dev(sg_ctx* ctx, const uint8_t* d_in, const uint64_t* d_in_off, uint64_t n, uint64_t nbytes,
+			 uint64_t* d_out_off, uint8_t* d_out, uint64_t cap);
+/* serializeHeader (when with_header != 0) and serializeRecord (:132-165) for n
+ * records in the given order: record k has key keys[key_off[k] ..
+ * key_off[k+1]), seq seqs[k] and value texts[text_off[k] .. text_off[k+1]).
+ * Each record is the magic 0xfee1bad, u32 len(key), the key and u64 seq; for
+ * seq == SG_DB_SEQ_DELETED it ends there; otherwise u32 val_len and the stream
+ * follow, and an empty value has val_len 0 and no stream (:148-149).  The
+ * whole byte string is assembled on the device and downloaded once.  *nout is
+ * always its length; out is written only when it is <= cap.  SG_EINVAL, before
+ * the context is touched: a NULL ctx or nout; seqs NULL with n > 0; out NULL
+ * with cap > 0; what sg_prog_hashes rejects of either CSR; a key of 2^32 bytes
+ * or more; a deletion with a non-empty value (Go panics, :143-145); a value
+ * whose stream could reach 2^32 bytes (more than 2^32 - 2^20 bytes of input).
+ * SG_EINVAL after the count phase: a file of 2^33 bytes or more.  SG_ENODEV
+ * without a device.  Two waits. */
+int sg_db_serialize(sg_ctx* ctx, const uint8_t* keys, const uint64_t* key_off, const uint64_t* seqs, const uint8_t* texts,
+		    const uint64_t* text_off, size_t n, int with_header, uint8_t* out, size_t cap, size_t* nout);
+/* compact()'s buffer (:96-100) for an opened database, from its resident texts
+ * with no upload but the keys: the header, then the live records in
+ * sg_db_export's order (Go has map order there; the pinned choice of
+ * sg_db_open).  *nout and out as above.  SG_EINVAL: a NULL db or nout, out NULL
+ * with cap > 0. */
+int sg_db_compact(sg_db* db, uint8_t* out, size_t cap, size_t* nout);
 
 #ifdef __cplusplus
 }

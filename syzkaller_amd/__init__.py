@@ -11,15 +11,15 @@ call priorities (corpus call ids to CalculatePriorities and the ChoiceTable),
 and `syzkaller_amd.corpus` the corpus' identities (pkg/hash, the identity sets
 and hubSync's Add / Del), and `syzkaller_amd.hub` the hub's corpus (prog.CallSet,
 the name dictionary, addInputs, pendingInputs and purgeCorpus), and
-`syzkaller_amd.db` the corpus database's read side (raw DEFLATE of every value,
-db.Open and loadDB from the file's bytes).
+`syzkaller_amd.db` the corpus database (raw DEFLATE of every value both ways,
+db.Open and loadDB from the file's bytes, Save, Delete, Flush and compact).
 """
 from ._lib import LIB_PATH, SyzSigError, lib  # noqa: F401  (fails loudly if the library is missing)
 
 _PRIO = ("PrioTable", "CalculatePriorities", "BuildChoiceTable", "ChoiceTable")
 _CORPUS = ("Hash", "String", "prog_hashes", "SigSet", "HubSync", "VerifyKeys")
 _HUB = ("NameTable", "call_sets", "CallSet", "HubCorpus", "HubState")
-_DB = ("inflate_batch", "db_scan", "DB", "LoadDB")
+_DB = ("inflate_batch", "db_scan", "DB", "LoadDB", "deflate_batch", "deflate_host", "deflate_bound", "db_serialize")
 
 __all__ = ["LIB_PATH", "SyzSigError", "lib", *_PRIO, *_CORPUS, *_HUB, *_DB]
 

@@ -191,6 +191,12 @@ SIGNATURES = {
     "sg_db_export": (c_int, [c_void_p, P64, P8, P64, P64, P8]),
     "sg_db_device": (c_int, [c_void_p, POINTER(c_void_p), POINTER(c_void_p)]),
     "sg_db_verify": (c_int, [c_void_p, c_void_p, P8, P64]),
+    "sg_deflate_bound": (c_size_t, [c_size_t]),
+    "sg_deflate_host": (c_int, [P8, P64, c_size_t, P64, P8, c_size_t, PSZ]),
+    "sg_deflate_batch": (c_int, [c_void_p, P8, P64, c_size_t, P64, P8, c_size_t, PSZ]),
+    "sg_deflate_batch_dev": (c_int, [c_void_p, c_void_p, c_void_p, c_uint64, c_uint64, c_void_p, c_void_p, c_uint64]),
+    "sg_db_serialize": (c_int, [c_void_p, P8, P64, P64, P8, P64, c_size_t, c_int, P8, c_size_t, PSZ]),
+    "sg_db_compact": (c_int, [c_void_p, P8, c_size_t, PSZ]),
     "sg_ipc_parse": (c_int,[c_void_p, P32, P64, P64, P32, c_size_t, POINTER(c_int64), P8, POINTER(c_int32), P64, P32,
                              P64, P32]),
     "sg_ipc_parse_dev": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_uint64, c_uint64, c_void_p,

@@ -414,6 +414,11 @@ const Counter kCounters[] = {
     {"sha1_long_len", kConst, kSha1Long},  // bytes of the longest program on the short SHA-1 path (SG_SHA1_LONG)
     {"inflate_long_streams", kDev64, SG_DEV(inflate_long_streams)},  // wave-per-stream path (sg_inflate.hip)
     {"inflate_long_len", kConst, kInflateLong},  // longest compressed stream on the lane path (SG_INFLATE_LONG)
+    {"deflate_long_streams", kDev64, SG_DEV(deflate_long_streams)},  // wave-per-stream path (sg_deflate.hip)
+    {"deflate_long_len", kConst, kDeflateLong},  // longest input on the lane path (SG_DEFLATE_LONG)
+    {"deflate_stored_streams", kDev64, SG_DEV(deflate_forms[0])},  // the last deflate count's streams per form
+    {"deflate_fixed_streams", kDev64, SG_DEV(deflate_forms[1])},
+    {"deflate_dynamic_streams", kDev64, SG_DEV(deflate_forms[2])},
     {"prio_band_cells", kConst, kPrioBandCells},  // u32 cells of a row band of the pair count
     {"prio_short_len", kConst, kPrioShort},       // calls of a program on the pair count's band path
     {"triage_runs_sort_cap", kConst, kTrSort},    // values a cover fold may hold on the LDS-sort route

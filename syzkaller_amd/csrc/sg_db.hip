@@ -13,6 +13,15 @@
 // ones into the database's own text buffer, where sg_prog_hashes_dev and
 // sg_call_sets_dev take them.  sg_db_verify is those two over the resident
 // texts and a 40-byte compare per record on the host.
+//
+// The write side (:95-116 compact, :132-165 serializeHeader and
+// serializeRecord): sg_db_serialize and sg_db_compact point sg_deflate.hip's
+// passes at the records' texts (uploaded, or an opened database's resident
+// ones), zero the lengths of deletions and empty values, and assemble the file
+// on the device: the host sends each record's prefix of bytes that are not
+// streams, k_db_frames writes magic, key, seq and val_len a thread per record,
+// the write phase puts every stream behind its frame, and one copy brings the
+// file back.
 #include "sg_internal.h"
 
 #include <algorithm>
@@ -83,12 +92,188 @@ int db_scan(const uint8_t* b, uint64_t n, F&& rec) {
   }
 }
 
+// ---- the write side: serializeHeader and serializeRecord (:132-165) ----------
+// A record's bytes that are not its stream: magic, len(key), key, seq, and the
+// value's length unless the record is a deletion.
+uint64_t frame_bytes(uint64_t key_len, uint64_t seq) { return 4 + 4 + key_len + 8 + (seq == SG_DB_SEQ_DELETED ? 0 : 4); }
+
+// A deletion and an empty value have no stream: their lengths are zeroed before the scan.
+__global__ __launch_bounds__(256) void k_db_mask(const uint64_t* __restrict__ seqs, const uint64_t* __restrict__ text_off,
+                                                  uint64_t n, uint32_t* __restrict__ olen) {
+  const uint64_t k = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+  if (k >= n) return;
+  if (seqs[k] == SG_DB_SEQ_DELETED || text_off[k + 1] <= text_off[k]) olen[k] = 0;
+}
+
+__device__ __forceinline__ void put_le(uint8_t* out, uint64_t cap, uint64_t at, uint64_t v, uint32_t nbytes) {
+  for (uint32_t j = 0; j < nbytes; j++)
+    if (at + j < cap) out[at + j] = (uint8_t)(v >> (8 * j));
+}
+
+// Everything of the file but the streams, a thread per record: record k's
+// stream starts at shift[k] + soff[k] (shift: the frames before it and its own,
+// from the host), so its frame starts frame_bytes before that.  Every store is
+// clamped to cap.
+__global__ __launch_bounds__(256) void k_db_frames(const uint8_t* __restrict__ keys, const uint64_t* __restrict__ key_off,
+                                                    const uint64_t* __restrict__ seqs, const uint64_t* __restrict__ shift,
+                                                    const uint64_t* __restrict__ soff, uint64_t n, uint64_t nkeys,
+                                                    int with_header, uint8_t* __restrict__ out, uint64_t cap) {
+  const uint64_t k = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+  if (k == 0 && with_header) {
+    put_le(out, cap, 0, kDbMagic, 4);
+    put_le(out, cap, 4, kCurVersion, 4);
+  }
+  if (k >= n) return;
+  uint64_t k0, k1;
+  sgd::csr_range(key_off, k, nkeys, k0, k1);
+  const uint64_t seq = seqs[k], klen = k1 - k0;
+  const bool del = seq == SG_DB_SEQ_DELETED;
+  uint64_t at = shift[k] + soff[k] - (4 + 4 + klen + 8 + (del ? 0 : 4));
+  put_le(out, cap, at, kRecMagic, 4);
+  put_le(out, cap, at + 4, klen, 4);
+  at += 8;
+  for (uint64_t j = 0; j < klen; j++)
+    if (at + j < cap) out[at + j] = keys[k0 + j];
+  at += klen;
+  put_le(out, cap, at, seq, 8);
+  if (!del) put_le(out, cap, at + 8, soff[k + 1] - soff[k], 4);
+}
+
+// serializeHeader (with_header) and serializeRecord for n records whose texts
+// are on the device already: keys and seqs from the host, the file assembled
+// on the device and downloaded once.  ctx lock held, the device ensured, every
+// argument checked.
+int db_serialize_body(sg_ctx* ctx, const char* fn, const uint8_t* keys, const uint64_t* key_off, const uint64_t* seqs,
+                      const uint8_t* d_texts, const uint64_t* d_text_off, uint64_t ntext, uint64_t n,
+                      int with_header, uint8_t* out, size_t cap, size_t* nout) {
+  const uint64_t head = with_header ? 8 : 0;
+  if (n == 0) {
+    *nout = head;
+    if (head && head <= cap) {
+      const uint32_t h[2] = {kDbMagic, kCurVersion};
+      memcpy(out, h, 8);
+    }
+    return SG_OK;
+  }
+  // shift[k]: where record k's stream would start if no record before it had one
+  std::vector<uint64_t> shift(n);
+  uint64_t frames = head;
+  for (uint64_t k = 0; k < n; k++) {
+    frames += frame_bytes(key_off[k + 1] - key_off[k], seqs[k]);
+    shift[k] = frames;
+  }
+  const uint64_t nkeys = key_off[n];
+  WsPlan plan;
+  const size_t o_keys = plan.add(nkeys + 4), o_koff = plan.add((n + 1) * 8), o_seqs = plan.add(n * 8),
+               o_shift = plan.add(n * 8), o_olen = plan.add(n * 4), o_form = plan.add(n), o_soff = plan.add((n + 1) * 8);
+  int rc;
+  if ((rc = dstage_reserve(ctx, plan))) return rc;
+  if ((rc = ws_reserve(ctx, deflate_ws(n)))) return rc;
+  uint8_t* dkeys = dstage_at<uint8_t>(ctx, o_keys);
+  uint64_t* dkoff = dstage_at<uint64_t>(ctx, o_koff);
+  uint64_t* dseqs = dstage_at<uint64_t>(ctx, o_seqs);
+  uint64_t* dshift = dstage_at<uint64_t>(ctx, o_shift);
+  uint32_t* dolen = dstage_at<uint32_t>(ctx, o_olen);
+  uint8_t* dform = dstage_at<uint8_t>(ctx, o_form);
+  uint64_t* dsoff = dstage_at<uint64_t>(ctx, o_soff);
+  if ((rc = upload(ctx, dkeys, keys, nkeys))) return rc;
+  if ((rc = upload(ctx, dkoff, key_off, (n + 1) * 8))) return rc;
+  if ((rc = upload(ctx, dseqs, seqs, n * 8))) return rc;
+  if ((rc = upload(ctx, dshift, shift.data(), n * 8))) return rc;
+  const uint64_t* sorted = nullptr;
+  if ((rc = deflate_count(ctx, d_texts, d_text_off, d_text_off + 1, n, ntext, dolen, dform, 0, &sorted))) return rc;
+  hipLaunchKernelGGL(k_db_mask, dim3(div_up(n, 256)), dim3(256), 0, ctx->stream, (const uint64_t*)dseqs, d_text_off, n,
+                     dolen);
+  SG_HIP(hipGetLastError());
+  if ((rc = deflate_offsets(ctx, dolen, dsoff, n, 0))) return rc;
+  uint64_t streams = 0;
+  SG_HIP(hipMemcpyAsync(&streams, dsoff + n, 8, hipMemcpyDeviceToHost, ctx->stream));
+  SG_HIP(hipStreamSynchronize(ctx->stream));  // (shift is this call's host memory, too)
+  const uint64_t total = frames + streams;
+  if (total >= kInflateMaxOut) {
+    set_error("%s: a file of %llu bytes (the limit is 2^33 - 1)", fn, (unsigned long long)total);
+    return SG_EINVAL;
+  }
+  *nout = total;
+  if (total > cap) return SG_OK;
+  if ((rc = ctx->inflate_out.grow_drop(grow_cap(ctx->inflate_out.cap, total, 16u << 20), ctx->stream))) return rc;
+  uint8_t* dout = ctx->inflate_out.p;
+  {
+    ScopedTimer tm(ctx, "db_frames");
+    hipLaunchKernelGGL(k_db_frames, dim3(div_up(n, 256)), dim3(256), 0, ctx->stream, (const uint8_t*)dkeys,
+                       (const uint64_t*)dkoff, (const uint64_t*)dseqs, (const uint64_t*)dshift, (const uint64_t*)dsoff, n,
+                       nkeys, with_header, dout, total);
+  }
+  SG_HIP(hipGetLastError());
+  if ((rc = deflate_write(ctx, d_texts, d_text_off, d_text_off + 1, n, ntext, sorted, dsoff, dshift, frames, dout, total)))
+    return rc;
+  SG_HIP(hipMemcpyAsync(out, dout, total, hipMemcpyDeviceToHost, ctx->stream));
+  SG_HIP(hipStreamSynchronize(ctx->stream));
+  return SG_OK;
+}
+
 }  // namespace
 }  // namespace sg
 
 using namespace sg;
 
 extern "C" {
+
+int sg_db_serialize(sg_ctx* ctx, const uint8_t* keys, const uint64_t* key_off, const uint64_t* seqs, const uint8_t* texts,
+                    const uint64_t* text_off, size_t n, int with_header, uint8_t* out, size_t cap, size_t* nout) {
+  const char* fn = "sg_db_serialize";
+  if (!ctx || !nout || (n && !seqs) || (cap && !out)) {
+    set_error("%s: invalid argument", fn);
+    return SG_EINVAL;
+  }
+  int rc = prog_texts_ok(fn, keys, key_off, n);
+  if (rc) return rc;
+  if ((rc = deflate_texts_ok(fn, texts, text_off, n))) return rc;
+  for (size_t k = 0; k < n; k++) {
+    if (key_off[k + 1] - key_off[k] >= (1ull << 32)) {
+      set_error("%s: record %llu has a key of 2^32 bytes or more", fn, (unsigned long long)k);
+      return SG_EINVAL;
+    }
+    if (seqs[k] == SG_DB_SEQ_DELETED && text_off[k + 1] != text_off[k]) {
+      set_error("%s: record %llu is a deletion with a value", fn, (unsigned long long)k);
+      return SG_EINVAL;
+    }
+  }
+  std::lock_guard<std::mutex> g(ctx->mu);
+  if ((rc = ensure_device(ctx))) return rc;
+  const uint64_t ntext = n ? text_off[n] : 0;
+  uint8_t* dtexts = nullptr;
+  uint64_t* dtoff = nullptr;
+  if (n) {  // the texts go to the workspace's tail, behind what the deflate passes take of it
+    const size_t o_texts = deflate_ws(n), o_toff = o_texts + align256(ntext + 4);
+    if ((rc = ws_reserve(ctx, o_toff + align256((n + 1) * 8)))) return rc;
+    dtexts = (uint8_t*)ws_at(ctx, o_texts);
+    dtoff = (uint64_t*)ws_at(ctx, o_toff);
+    if ((rc = upload(ctx, dtexts, texts, ntext))) return rc;
+    if ((rc = upload(ctx, dtoff, text_off, (n + 1) * 8))) return rc;
+  }
+  return db_serialize_body(ctx, fn, keys, key_off, seqs, dtexts, dtoff, ntext, n, with_header, out, cap, nout);
+}
+
+int sg_db_compact(sg_db* db, uint8_t* out, size_t cap, size_t* nout) {
+  const char* fn = "sg_db_compact";
+  if (!db || !nout || (cap && !out)) {
+    set_error("%s: invalid argument", fn);
+    return SG_EINVAL;
+  }
+  const uint64_t n = db->seqs.size();
+  for (uint64_t k = 0; k < n; k++)
+    if (db->text_off[k + 1] - db->text_off[k] > kDeflateMaxIn) {
+      set_error("%s: record %llu has a value of more than 2^32 - 2^20 bytes", fn, (unsigned long long)k);
+      return SG_EINVAL;
+    }
+  sg_ctx* ctx = db->ctx;
+  std::lock_guard<std::mutex> g(ctx->mu);
+  const int rc = ensure_device(ctx);
+  if (rc) return rc;
+  return db_serialize_body(ctx, fn, db->keys.data(), db->key_off.data(), db->seqs.data(), db->d_texts.p, db->d_text_off.p,
+                           db->text_off.back(), n, 1, out, cap, nout);
+}
 
 int sg_db_scan(const uint8_t* bytes, size_t nbytes, uint64_t* key_pos, uint32_t* key_len, uint64_t* seq,
                uint64_t* val_pos, uint32_t* val_len, size_t cap, size_t* nrec, int* end) {

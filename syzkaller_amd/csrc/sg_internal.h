@@ -96,9 +96,12 @@ struct CtxDev {
   uint32_t tr_wide;         // "triage_runs_wide", and the cover fold's routes after it (zeroed together)
   uint32_t tr_route[kTrRoutes];
   uint64_t prio_bad_ids, sha1_long_progs, inflate_long_streams;  // (cumulative over the context's life)
+  uint64_t deflate_long_streams;  // likewise (sg_deflate.hip)
+  uint64_t deflate_forms[3];      // the last deflate_count's streams per form: stored, fixed, dynamic
 };
 static_assert(offsetof(CtxDev, scalar) % 8 == 0 && offsetof(CtxDev, prio_bad_ids) % 8 == 0 &&
-                  offsetof(CtxDev, sha1_long_progs) % 8 == 0 && offsetof(CtxDev, inflate_long_streams) % 8 == 0,
+                  offsetof(CtxDev, sha1_long_progs) % 8 == 0 && offsetof(CtxDev, inflate_long_streams) % 8 == 0 &&
+                  offsetof(CtxDev, deflate_long_streams) % 8 == 0 && offsetof(CtxDev, deflate_forms) % 8 == 0,
               "64-bit device words are 8-byte aligned");
 static_assert(offsetof(CtxDev, tr_route) == offsetof(CtxDev, tr_wide) + 4, "wide and the routes are zeroed together");
 // ... and the pinned words two of them are copied to, read without a host wait once the event has passed
@@ -170,7 +173,8 @@ struct sg_ctx {
   sg::PinBuf pin;
   // grow-only device staging for the host entry points' inputs / outputs (dstage_reserve)
   sg::DevBuf<char> dstage;
-  // sg_inflate_batch's outputs on their way to the host (grow-only from 16 MiB; sg_inflate.hip)
+  // sg_inflate_batch's outputs on their way to the host (grow-only from 16 MiB; sg_inflate.hip), and those of
+  // sg_deflate_batch, sg_db_serialize and sg_db_compact (sg_deflate.hip, sg_db.hip)
   sg::DevBuf<uint8_t> inflate_out;
   // first-owner table and its decreasing key floor; the key space is 2^32 - 1
   // (option owner_key_space lowers it, so tests reach the generation reset)
@@ -484,6 +488,30 @@ int inflate_offsets(sg_ctx* ctx, const uint32_t* d_olen, uint64_t* d_out_off, ui
 int inflate_write(sg_ctx* ctx, const uint8_t* d_in, const uint64_t* d_beg, const uint64_t* d_end, uint64_t n,
                   uint64_t nbytes, const uint64_t* d_sorted, const uint8_t* d_status, const uint64_t* d_out_off,
                   uint8_t* d_out, uint64_t cap);
+
+// Raw DEFLATE the other way (sg_deflate.hip; ctx lock held, the device
+// ensured), in the same shape.  deflate_count: the exact length and the form
+// (0 stored, 1 fixed, 2 dynamic) of every stream's encoding, from
+// deflate_ws(n) bytes of the workspace at ws_used; it also sets the context's
+// form counts and adds to "deflate_long_streams".  deflate_offsets: scan_counts
+// of the lengths (which the caller may have edited: a zero length is a stream
+// nobody wants).  deflate_write, with the workspace untouched since the count:
+// stream p into d_out[d_out_off[p] + shift[p], d_out_off[p + 1] + shift[p])
+// (d_shift null: no shift), clamped to cap, when d_out_off[n] + extra <= cap
+// (compared on the device).  n < 2^32; a stream's input is cut at
+// kDeflateMaxIn bytes, so that its length fits 32 bits (the host forms reject
+// longer ones: deflate_texts_ok).
+// "deflate_long_len" reads SG_DEFLATE_LONG.
+constexpr uint32_t kDeflateLong = SG_DEFLATE_LONG;
+constexpr uint64_t kDeflateMaxIn = (1ull << 32) - (1ull << 20);
+size_t deflate_ws(uint64_t n);
+int deflate_count(sg_ctx* ctx, const uint8_t* d_in, const uint64_t* d_beg, const uint64_t* d_end, uint64_t n,
+                  uint64_t nbytes, uint32_t* d_olen, uint8_t* d_form, size_t ws_used, const uint64_t** d_sorted);
+int deflate_offsets(sg_ctx* ctx, const uint32_t* d_olen, uint64_t* d_out_off, uint64_t n, size_t ws_used);
+int deflate_write(sg_ctx* ctx, const uint8_t* d_in, const uint64_t* d_beg, const uint64_t* d_end, uint64_t n,
+                  uint64_t nbytes, const uint64_t* d_sorted, const uint64_t* d_out_off, const uint64_t* d_shift,
+                  uint64_t extra, uint8_t* d_out, uint64_t cap);
+int deflate_texts_ok(const char* fn, const uint8_t* in, const uint64_t* in_off, size_t n);
 
 }  // namespace sg
 
