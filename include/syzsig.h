@@ -835,6 +835,87 @@ int sg_cover_lines_set(sg_cover_table* table, sg_set* cov, uint32_t base, uint64
 		       uint8_t* covered, uint8_t* file_seen, uint64_t* ncovered_frames, uint64_t* missing,
 		       size_t* nmissing);
 
+/* ---- cover report pages (syz-manager/cover.go:122-156, :198-217) ------------ */
+/* The rest of generateCoverHtml up to its template: the loop over fileSet's
+ * map (syz-manager/cover.go:122-156) reads every file of the report again on
+ * every request (parseFile, syz-manager/cover.go:198-217) and writes every
+ * line of it into a buffer, a listed line between one of two pairs of
+ * literals -- still under mgr.mu (httpCover, syz-manager/html.go:169-194).
+ * The sources depend on the tree alone, as the frames on vmlinux alone, so
+ * the caller reads them once into a table that stays on the device; a report
+ * is then one call from the cover to each file's Body and Coverage, the
+ * templateFile of cover.go:151-155.  coverTemplate and its execution, the
+ * prefix strip (cover.go:148-150) and the sort (cover.go:158) stay with the
+ * caller.
+ *
+ * sg_src_table_create: file f is the sg_cover_table's file id f; its bytes are
+ * bytes[off[f] .. off[f+1]).  have[f] == 0: the caller could not read it
+ * (parseFile's error, cover.go:199-202) and its range must be empty.  The
+ * table holds exactly parseFile's lines (cover.go:203-215): every stretch up
+ * to a '\n' is a line and passes, byte by byte, through the replacer of
+ * cover.go:203 ('>' "&gt;", '<' "&lt;", '&' "&amp;", '\t' eight spaces; no
+ * second pass over what it wrote); what follows the file's last '\n', when not
+ * empty, is one more line and is NOT escaped (cover.go:213-215 appends the raw
+ * bytes); '\r', NUL and bytes >= 0x80 pass unchanged; an empty file has no
+ * lines and "\n" one empty line.  Stored is the text with a '\n' behind every
+ * line, the raw fragment included (cover.go:144-145 appends one to every
+ * line): byte for byte the file's body when nothing is listed.  Checked on the
+ * host before the context is touched (SG_EINVAL, sg_last_error says what):
+ * null pointers, off not starting at 0 or decreasing, have[f] == 0 with a
+ * non-empty range, 2^32 or more bytes; after the count phase 2^32 or more
+ * stored bytes.  The table is immutable, belongs to `ctx` and must be
+ * destroyed before it.
+ *
+ * sg_src_table_counts: file f's lines are file_line_off[f] ..
+ * file_line_off[f+1] (nfiles + 1 entries) of the table's; totals = lines,
+ * stored bytes, raw bytes.  sg_src_table_export: line i's text is
+ * text[line_off[i] .. line_off[i+1] - 1) (lines + 1 offsets; the byte before
+ * line_off[i+1] is the '\n'), text has totals[1] bytes.
+ *
+ * sg_cover_pages: everything up to nmissing means what it means for
+ * sg_cover_lines and is checked the same way.  Then cover.go:123-147 runs for
+ * every file with a non-empty range (the keys of fileSet's map), in file-id
+ * order: the body is the file's lines in order, each followed by '\n'; a line
+ * whose 1-based number is in the file's list stands between
+ * "<span id='covered'>" and 20 bytes ("</span> ", a C comment of the word
+ * covered, '\n': the suffix carries the '\n'; cover.go:133-135) or between
+ * "<span id='uncovered'>" and "</span>\n" (cover.go:138-140).  Listed lines are > 0, distinct and ascending, so the
+ * loop's covered[0] walk (cover.go:131, :142) wraps every listed line <= the
+ * file's line count and silently drops one beyond it.  coverage[f] counts the
+ * covered lines actually wrapped (cover.go:136); a file with no lines gets an
+ * empty body and coverage 0.  File f's body is bodies[body_off[f] ..
+ * body_off[f+1]) (nfiles + 1 offsets); a file outside the report has an empty
+ * range.  *bad_file = the lowest id of a file of the report with have == 0,
+ * else UINT32_MAX; when there is one nothing is rendered (*nbytes = 0,
+ * body_off and coverage all 0), the return is still SG_OK and the line tables
+ * are valid (the reference fails the page at the first such file in map
+ * order, cover.go:124-127).  *nbytes is always the bodies' total; bodies
+ * (capacity cap) is written only when the total is <= cap, body_off and
+ * coverage always; bodies == NULL with cap > 0 is SG_EINVAL.  The bodies match
+ * the line tables of the same call, also when *nmissing > 0.  ncov == 0:
+ * all-empty outputs and SG_OK.  src and table must share a context and nfiles
+ * (SG_EINVAL).  The call makes no more waits than sg_cover_lines, but one when
+ * the context's output buffer has to grow for the bodies: body_off, coverage
+ * and the total come back with its counts, the bodies with its lines.  Counter "cover_pages_tile": the bytes of the bodies one workgroup of
+ * the copy writes.
+ *
+ * sg_cover_pages_set: the same for the members of `cov`, as
+ * sg_cover_lines_set. */
+typedef struct sg_src_table sg_src_table;
+int sg_src_table_create(sg_ctx* ctx, const uint8_t* have, const uint8_t* bytes, const uint64_t* off, uint32_t nfiles,
+			sg_src_table** out);
+void sg_src_table_destroy(sg_src_table* src);
+int sg_src_table_counts(sg_src_table* src, uint64_t* file_line_off, uint64_t totals[3]);
+int sg_src_table_export(sg_src_table* src, uint64_t* line_off, uint8_t* text);
+int sg_cover_pages(sg_cover_table* table, sg_src_table* src, const uint32_t* cov, size_t ncov, uint32_t base,
+		   uint64_t* file_off, uint32_t* lines, uint8_t* covered, uint8_t* file_seen, uint64_t* ncovered_frames,
+		   uint64_t* missing, size_t* nmissing, uint64_t* body_off, uint32_t* coverage, uint8_t* bodies,
+		   size_t cap, size_t* nbytes, uint32_t* bad_file);
+int sg_cover_pages_set(sg_cover_table* table, sg_src_table* src, sg_set* cov, uint32_t base, uint64_t* file_off,
+		       uint32_t* lines, uint8_t* covered, uint8_t* file_seen, uint64_t* ncovered_frames,
+		       uint64_t* missing, size_t* nmissing, uint64_t* body_off, uint32_t* coverage, uint8_t* bodies,
+		       size_t cap, size_t* nbytes, uint32_t* bad_file);
+
 /* ---- executor output ingest (pkg/ipc/ipc_linux.go:168-307) ---------------- */
 /* readOutCoverage over a batch of programs.  Program p's output region (the
  * layout executor/executor.h:369-427 writes) is out[out_off[p] ..

@@ -145,6 +145,14 @@ SIGNATURES = {
     "sg_cover_table_slots": (c_int, [c_void_p, P64]),
     "sg_cover_lines": (c_int, [c_void_p, P32, c_size_t, c_uint32, P64, P32, P8, P8, P64, P64, PSZ]),
     "sg_cover_lines_set": (c_int, [c_void_p, c_void_p, c_uint32, P64, P32, P8, P8, P64, P64, PSZ]),
+    "sg_src_table_create": (c_int, [c_void_p, P8, P8, P64, c_uint32, POINTER(c_void_p)]),
+    "sg_src_table_destroy": (None, [c_void_p]),
+    "sg_src_table_counts": (c_int, [c_void_p, P64, P64]),
+    "sg_src_table_export": (c_int, [c_void_p, P64, P8]),
+    "sg_cover_pages": (c_int, [c_void_p, c_void_p, P32, c_size_t, c_uint32, P64, P32, P8, P8, P64, P64, PSZ, P64, P32, P8,
+                               c_size_t, PSZ, P32]),
+    "sg_cover_pages_set": (c_int, [c_void_p, c_void_p, c_void_p, c_uint32, P64, P32, P8, P8, P64, P64, PSZ, P64, P32, P8,
+                                   c_size_t, PSZ, P32]),
     "sg_prio_table_create": (c_int, [c_void_p, c_uint32, c_uint32, PF, P8, POINTER(c_void_p)]),
     "sg_prio_table_destroy": (None, [c_void_p]),
     "sg_prio_table_clear": (c_int, [c_void_p]),

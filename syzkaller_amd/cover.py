@@ -653,15 +653,107 @@ def cover_lines(table, cov, base):
     return file_off, lines[:total], covered[:total], seen[:nf], ncf.value, missing[: nm.value]
 
 
+class SourceTable:
+    """sg_src_table: parseFile (syz-manager/cover.go:198-217) of every source file, once, on the device
+    (include/syzsig.h).  File f is the CoverTable's file id f and its bytes are bytes[off[f]:off[f+1]]; have[f] == 0
+    is a file that could not be read (its range empty).  Close it before its context."""
+
+    def __init__(self, have, bytes, off, ctx=None):
+        self.ctx = _ctx(ctx)
+        hv = np.ascontiguousarray(np.asarray(have, dtype=np.uint8).reshape(-1))
+        by = np.ascontiguousarray(np.asarray(bytes, dtype=np.uint8).reshape(-1) if isinstance(bytes, np.ndarray)
+                                  else np.frombuffer(bytes, dtype=np.uint8))  # (else: bytes-like)
+        of = _u64(off)
+        if of.size != hv.size + 1 or int(of[-1]) != by.size:
+            raise ValueError("SourceTable: array lengths do not agree")
+        self.nfiles = int(hv.size)
+        h = c_void_p()
+        call("sg_src_table_create", self.ctx.h, _p8(hv), _p8(by), _p64(of), self.nfiles, byref(h))
+        self.h = h
+
+    def close(self):
+        if self.h:
+            lib.sg_src_table_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def counts(self):
+        """(file_line_off, lines, stored bytes, raw bytes): file f's lines are file_line_off[f]:file_line_off[f+1]."""
+        flo, tot = np.zeros(self.nfiles + 1, dtype=U64), np.zeros(3, dtype=U64)
+        call("sg_src_table_counts", self.h, _p64(flo), _p64(tot))
+        return flo, int(tot[0]), int(tot[1]), int(tot[2])
+
+    def lines(self):
+        """parseFile's result per file: [[line, ...], ...] as bytes, without the stored '\\n'."""
+        flo, nlines, stored, _ = self.counts()
+        lo, text = np.zeros(nlines + 1, dtype=U64), np.zeros(max(stored, 1), dtype=np.uint8)
+        call("sg_src_table_export", self.h, _p64(lo), _p8(text))
+        t, lo = text[:stored].tobytes(), lo.tolist()
+        return [[t[lo[i]:lo[i + 1] - 1] for i in range(int(flo[f]), int(flo[f + 1]))] for f in range(self.nfiles)]
+
+
+_pages_buf = [np.zeros(1 << 20, dtype=np.uint8)]  # cover_pages' grow-only host buffer for the bodies
+
+
+def cover_pages(table, src, cov, base):
+    """cover_lines, then generateCoverHtml's loop over fileSet's map (syz-manager/cover.go:122-156) on a SourceTable,
+    in one call.  Returns cover_lines' tuple plus (body_off, bodies, coverage, bad_file): file f's Body is
+    bodies[body_off[f]:body_off[f+1]] and its Coverage coverage[f]; bad_file is the lowest file of the report that
+    could not be read (then nothing is rendered), else None.  The bodies land in a buffer that only grows (the
+    library is called a second time only when they did not fit it); `bodies` is a view of it, good until the next
+    call."""
+    nf = table.nfiles
+    file_off = np.zeros(nf + 1, dtype=U64)
+    lines = np.empty(max(table.nslots, 1), dtype=U32)
+    covered = np.empty(max(table.nslots, 1), dtype=np.uint8)
+    seen = np.zeros(max(nf, 1), dtype=np.uint8)
+    body_off, coverage = np.zeros(nf + 1, dtype=U64), np.zeros(max(nf, 1), dtype=U32)
+    ncf, nm, nb, bad = c_uint64(), c_size_t(), c_size_t(), ctypes.c_uint32()
+    is_set = isinstance(cov, SignalSet)
+    c = None if is_set else _u32(cov)
+    missing = np.empty(max(len(cov) if is_set else c.size, 1), dtype=U64)
+    for _ in range(2):
+        buf = _pages_buf[0]
+        outs = (_p64(file_off), _p32(lines), _p8(covered), _p8(seen), byref(ncf), _p64(missing), byref(nm),
+                _p64(body_off), _p32(coverage), _p8(buf), buf.size, byref(nb), byref(bad))
+        if is_set:
+            call("sg_cover_pages_set", table.h, src.h, cov.h, base, *outs)
+        else:
+            call("sg_cover_pages", table.h, src.h, _p32(c), c.size, base, *outs)
+        if nb.value <= buf.size:
+            break
+        _pages_buf[0] = np.zeros(max(2 * buf.size, nb.value), dtype=np.uint8)
+    total = int(file_off[nf])
+    return (file_off, lines[:total], covered[:total], seen[:nf], ncf.value, missing[: nm.value], body_off,
+            _pages_buf[0][: nb.value], coverage[:nf], None if bad.value == 0xFFFFFFFF else bad.value)
+
+
 class CoverReport:
     """The string-level mirror of generateCoverHtml up to fileSet.  symbolize(pcs) -> [(pc, func, file, line), ...]
     is the caller's addr2line (symbolizer.go: a PC's frames in `-afi` order, "??" and line <= 0 already dropped).
     The constructor symbolises all_pcs (initAllCover's call sites, cover.go:64-89) and interns the names;
     file_set(cov, base) returns {file: [(line, covered), ...]} as fileSet does.  Covered PCs the table does not
-    know are symbolised and the table rebuilt from the host copies, once per call."""
+    know are symbolised and the table rebuilt from the host copies, once per call.
 
-    def __init__(self, sym_start, sym_end, all_pcs, symbolize, ctx=None):
+    pages(cov, base) goes on to the sorted d.Files (cover.go:122-158): [(Name, Body, Coverage), ...].  read_file(name)
+    returns a source file's bytes, or None for one that cannot be read (parseFile's error); every file the table
+    names is read once, into a SourceTable built on first use and again whenever a rebuild added files.  Name is
+    the file without the common prefix, only when it is longer than the prefix (cover.go:148-150); the prefix is
+    the byte-wise common prefix of the files of the uncovered frames (file_seen bit 1: the second symbolize call's,
+    cover.go:117 and :358-372), "" when there are none.  For names that share no first byte the reference's
+    `prefix == ""` reset makes its result depend on frame order; the mirror's pinned choice is the true common
+    prefix "".  Order is templateFileArray.Less (cover.go:391-404): names starting with '.' last, otherwise
+    ascending; names are distinct, so the order is total."""
+
+    def __init__(self, sym_start, sym_end, all_pcs, symbolize, ctx=None, read_file=None):
         self.ctx = _ctx(ctx)
+        self.read_file = read_file
+        self.src = None
         self.sym_start, self.sym_end, self.all_pcs = _u64(sym_start), _u64(sym_end), _u64(all_pcs)
         self.symbolize = symbolize
         self.files, self.funcs = {}, {}  # name -> id
@@ -689,8 +781,23 @@ class CoverReport:
         self.table = CoverTable(self.sym_start, self.sym_end, self.all_pcs, tab, off, fr[:, 0], fr[:, 1], fr[:, 2],
                                 len(self.files), len(self.funcs), ctx=self.ctx)
         self.names = sorted(self.files, key=self.files.get)
+        if self.src is not None and self.src.nfiles != len(self.names):
+            self.src.close()
+            self.src = None
+
+    def _sources(self):
+        if self.src is None:
+            data = [self.read_file(name) if self.read_file else None for name in self.names]
+            off = np.zeros(len(data) + 1, dtype=U64)
+            off[1:] = np.cumsum([len(d) if d is not None else 0 for d in data])
+            self.src = SourceTable([d is not None for d in data], b"".join(d for d in data if d is not None), off,
+                                   ctx=self.ctx)
+        return self.src
 
     def close(self):
+        if self.src is not None:
+            self.src.close()
+            self.src = None
         if self.table is not None:
             self.table.close()
             self.table = None
@@ -713,6 +820,40 @@ class CoverReport:
             if b > a:
                 out[name] = [(int(ln), bool(c)) for ln, c in zip(lines[a:b], covered[a:b])]
         return out
+
+    def pages(self, cov, base):
+        if (len(cov) if isinstance(cov, SignalSet) else _u32(cov).size) == 0:
+            raise ValueError("No coverage data available")  # html.go:183
+        res = cover_pages(self.table, self._sources(), cov, base)
+        if res[5].size:
+            self._add(res[5])
+            self._build()
+            res = cover_pages(self.table, self._sources(), cov, base)
+            assert res[5].size == 0
+        file_off, _, _, seen, ncf, _, body_off, bodies, coverage, bad = res
+        if ncf == 0:
+            raise ValueError("coverage doesn't match to vmlinux: no frames (does not have debug info?)")  # cover.go:113
+        if bad is not None:
+            raise OSError(2, "cannot read a source file of the report", self.names[bad])  # cover.go:124-127
+        raw = [name.encode("utf-8", "surrogateescape") for name in self.names]
+        prefix = None
+        for f in np.flatnonzero(seen & 2).tolist():  # cover.go:358-372 over the uncovered frames
+            if prefix is None:
+                prefix = raw[f]
+            else:
+                i = 0
+                while i < len(prefix) and i < len(raw[f]) and prefix[i] == raw[f][i]:
+                    i += 1
+                prefix = prefix[:i]
+        prefix = prefix or b""
+        out = []
+        for f, name in enumerate(raw):
+            if file_off[f + 1] > file_off[f]:
+                if len(name) > len(prefix):  # cover.go:148-150
+                    name = name[len(prefix):]
+                out.append((name, bodies[int(body_off[f]):int(body_off[f + 1])].tobytes(), int(coverage[f])))
+        out.sort(key=lambda t: (t[0][:1] == b".", t[0]))  # cover.go:391-404 (Go compares strings byte-wise)
+        return [(name.decode("utf-8", "surrogateescape"), body, c) for name, body, c in out]
 
 
 # pkg/ipc/ipc_linux.go:168-307 status codes (include/syzsig.h SG_IPC_*)

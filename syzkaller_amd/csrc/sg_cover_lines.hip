@@ -35,29 +35,11 @@
 //
 // No kernel sorts: slot order is output order.  Header lines of inlined
 // helpers are hit from thousands of sites, so every OR tests the bit first.
+#include "sg_cover_lines.h"
 #include "sg_rank.h"
-#include "sg_report.h"
 
 #include <algorithm>
 #include <vector>
-
-struct sg_cover_table {
-  sg_ctx* ctx = nullptr;
-  sg::DevBuf<char> mem;  // the one device block everything below lives in
-  bool has_rep = false;  // symbols and call sites: the uncovered side exists
-  sg::RepTables rep{};
-  uint64_t nsym = 0, nall = 0, ntab = 0, nfr = 0, nslots = 0;
-  uint32_t nfiles = 0, nfuncs = 0;
-  uint64_t* tab = nullptr;  // [ntab]
-  sg::RadixIdx itab{};
-  uint32_t* site_row = nullptr;       // [nall] each call site's row of tab
-  uint32_t* frame_off = nullptr;      // [ntab + 1]
-  uint32_t* frame_slot = nullptr;     // [nfr]
-  uint32_t* frame_func = nullptr;     // [nfr]
-  uint32_t* frame_file = nullptr;     // [nfr]
-  uint32_t* slot_line = nullptr;      // [nslots]
-  uint32_t* file_slot_off = nullptr;  // [nfiles + 1]
-};
 
 namespace sg {
 
@@ -245,11 +227,10 @@ __global__ void k_cl_files(LinesArgs a) {
 }
 
 
-// Both report forms behind their argument checks (ctx lock held, the device
-// ensured): d_cov is device memory of the context (its staging buffer).
-static int cover_lines_body(sg_cover_table* t, const uint32_t* d_cov, uint64_t ncov, uint32_t base, uint64_t* file_off,
-                            uint32_t* lines, uint8_t* covered, uint8_t* file_seen, uint64_t* ncovered_frames,
-                            uint64_t* missing, size_t* nmissing) {
+// (sg_cover_lines.h)
+int cover_lines_body(sg_cover_table* t, const uint32_t* d_cov, uint64_t ncov, uint32_t base, uint64_t* file_off,
+                     uint32_t* lines, uint8_t* covered, uint8_t* file_seen, uint64_t* ncovered_frames,
+                     uint64_t* missing, size_t* nmissing, LinesTail* tail) {
   sg_ctx* ctx = t->ctx;
   const uint64_t nslots = t->nslots, nfiles = t->nfiles;
   const uint32_t nchunks = div_up(nslots, kSlotChunk);
@@ -264,12 +245,14 @@ static int cover_lines_body(sg_cover_table* t, const uint32_t* d_cov, uint64_t n
   const size_t o_ms = p.add(ncov * 8), o_cc = p.add((uint64_t)nchunks * 4), o_bs = p.add(((uint64_t)nchunks + 1) * 8),
                o_ol = p.add(nslots * 4), o_oc = p.add(nslots), o_of = p.add((nfiles + 1) * 8), o_os = p.add(nfiles);
   const size_t scan_off = p.total;
-  const size_t tail = std::max(scan_ws_bytes(nchunks), t->has_rep ? report_query_scan_bytes(t->rep, ncov, chunked) : 0);
+  const size_t scan_tail =
+      std::max(scan_ws_bytes(nchunks), t->has_rep ? report_query_scan_bytes(t->rep, ncov, chunked) : 0);
   if (p.overflow) {
     set_error("sg_cover_lines: a buffer plan of more than %d regions", WsPlan::kMaxRegions);
     return SG_EINVAL;
   }
-  int rc = ws_reserve(ctx, p.total + tail);
+  const size_t tail_off = align256(p.total + scan_tail);
+  int rc = ws_reserve(ctx, tail ? tail_off + tail->ws_bytes : p.total + scan_tail);
   if (rc) return rc;
   LinesArgs a{};
   a.cov = d_cov;
@@ -332,12 +315,15 @@ static int cover_lines_body(sg_cover_table* t, const uint32_t* d_cov, uint64_t n
     hipLaunchKernelGGL(k_cl_files, dim3(div_up(nfiles + 1, 256)), dim3(256), 0, ctx->stream, a);
   }
   SG_HIP(hipGetLastError());
+  if (tail && (rc = tail->queued(LinesDev{a.out_foff, a.out_lines, a.out_cov}, tail_off))) return rc;
   // one wait for the counts, then the results
   uint64_t cnt[2] = {0, 0};
   SG_HIP(hipMemcpyAsync(cnt, a.counters, 16, hipMemcpyDeviceToHost, ctx->stream));
   SG_HIP(hipMemcpyAsync(file_off, a.out_foff, (nfiles + 1) * 8, hipMemcpyDeviceToHost, ctx->stream));
   if (file_seen && nfiles) SG_HIP(hipMemcpyAsync(file_seen, a.out_fseen, nfiles, hipMemcpyDeviceToHost, ctx->stream));
   SG_HIP(hipStreamSynchronize(ctx->stream));
+  bool more = false;
+  if (tail && (rc = tail->counted(&more))) return rc;
   const uint64_t total = file_off[nfiles];
   if (total) {
     SG_HIP(hipMemcpyAsync(lines, a.out_lines, total * 4, hipMemcpyDeviceToHost, ctx->stream));
@@ -345,7 +331,7 @@ static int cover_lines_body(sg_cover_table* t, const uint32_t* d_cov, uint64_t n
   }
   std::vector<uint64_t> miss(cnt[1]);  // one entry per query that missed
   if (cnt[1]) SG_HIP(hipMemcpyAsync(miss.data(), a.missing, cnt[1] * 8, hipMemcpyDeviceToHost, ctx->stream));
-  if (total || cnt[1]) SG_HIP(hipStreamSynchronize(ctx->stream));
+  if (total || cnt[1] || more) SG_HIP(hipStreamSynchronize(ctx->stream));
   if (cnt[1]) {
     // sorted and de-duplicated only when there are any, on the host: the
     // caller is about to run addr2line over them
@@ -359,8 +345,8 @@ static int cover_lines_body(sg_cover_table* t, const uint32_t* d_cov, uint64_t n
   return SG_OK;
 }
 
-static int lines_args_ok(const char* fn, sg_cover_table* t, uint64_t* file_off, uint32_t* lines, uint8_t* covered,
-                         uint64_t* ncovered_frames, uint64_t* missing, size_t* nmissing) {
+int lines_args_ok(const char* fn, sg_cover_table* t, uint64_t* file_off, uint32_t* lines, uint8_t* covered,
+                  uint64_t* ncovered_frames, uint64_t* missing, size_t* nmissing) {
   if (!t || !file_off || !lines || !covered || !ncovered_frames || !missing || !nmissing) {
     set_error("%s: a null table or output", fn);
     return SG_EINVAL;
@@ -368,12 +354,34 @@ static int lines_args_ok(const char* fn, sg_cover_table* t, uint64_t* file_off, 
   return SG_OK;
 }
 
-static void lines_empty(sg_cover_table* t, uint64_t* file_off, uint8_t* file_seen, uint64_t* ncovered_frames,
-                        size_t* nmissing) {
+void lines_empty(sg_cover_table* t, uint64_t* file_off, uint8_t* file_seen, uint64_t* ncovered_frames,
+                 size_t* nmissing) {
   std::fill(file_off, file_off + (size_t)t->nfiles + 1, 0ull);
   if (file_seen) std::fill(file_seen, file_seen + t->nfiles, (uint8_t)0);
   *ncovered_frames = 0;
   *nmissing = 0;
+}
+
+// (sg_cover_lines.h)
+int lines_set_cover(const char* fn, sg_ctx* ctx, sg_set* cov, uint64_t* total) {
+  // the members, ascending (the reference's canonical cover order), into the
+  // staging buffer: nothing is uploaded.  The member count is a wait of its
+  // own; a set that outgrows the buffer is exported a second time.
+  int rc = dstage_reserve(ctx, 4);
+  if (rc) return rc;
+  *total = 0;
+  for (int pass = 0; pass < 2; pass++) {
+    rc = set_export_dev(cov, dstage_at<uint32_t>(ctx, 0), ctx->dstage.cap / 4, total);
+    if (rc) return rc;
+    if (*total * 4 <= ctx->dstage.cap) break;
+    rc = dstage_reserve(ctx, *total * 4);
+    if (rc) return rc;
+  }
+  if (*total >= 0xFFFFFFFFull) {
+    set_error("%s: too many PCs for one call", fn);
+    return SG_EINVAL;
+  }
+  return SG_OK;
 }
 
 }  // namespace sg
@@ -611,24 +619,10 @@ int sg_cover_lines_set(sg_cover_table* t, sg_set* cov, uint32_t base, uint64_t* 
   std::lock_guard<std::mutex> g(ctx->mu);
   rc = ensure_device(ctx);
   if (rc) return rc;
-  // the members, ascending (the reference's canonical cover order), into the
-  // staging buffer: nothing is uploaded.  The member count is a wait of its
-  // own; a set that outgrows the buffer is exported a second time.
-  rc = dstage_reserve(ctx, 4);
-  if (rc) return rc;
   uint64_t total = 0;
-  for (int pass = 0; pass < 2; pass++) {
-    rc = set_export_dev(cov, dstage_at<uint32_t>(ctx, 0), ctx->dstage.cap / 4, &total);
-    if (rc) return rc;
-    if (total * 4 <= ctx->dstage.cap) break;
-    rc = dstage_reserve(ctx, total * 4);
-    if (rc) return rc;
-  }
+  rc = lines_set_cover(fn, ctx, cov, &total);
+  if (rc) return rc;
   if (total == 0) return SG_OK;
-  if (total >= 0xFFFFFFFFull) {
-    set_error("%s: too many PCs for one call", fn);
-    return SG_EINVAL;
-  }
   return cover_lines_body(t, dstage_at<uint32_t>(ctx, 0), total, base, file_off, lines, covered, file_seen,
                           ncovered_frames, missing, nmissing);
 }

@@ -425,6 +425,7 @@ const Counter kCounters[] = {
     {"tinput_chunk", kConst, kTinChunk},          // values of new_k per LDS chunk of Intersection (sg_tinput.h)
     {"exec_comps_fast_cap", kConst, SG_EXEC_COMPS_FAST_CAP},  // distinct records a call may hold on the fast shape
     {"exec_cover_fast_cap", kConst, SG_EXEC_COVER_FAST_CAP},  // distinct PCs a call may hold on the fast shape
+    {"cover_pages_tile", kConst, kPagesTile},  // bytes of the bodies per workgroup of sg_cover_pages' copy
     {"cpu_quota_milli", kCalc, kCpuQuota},
     {"workspace_bytes", kCalc, kWsBytes},  // the workspace buffer's capacity (ws_reserve)
 };

@@ -395,6 +395,8 @@ constexpr uint32_t kPrioBandCells = 40960;  // u32 cells of a row band: the CU's
 constexpr uint32_t kPrioShort = 64;         // calls of a program on the band path; longer ones take k_prio_long
 // read by sg_ctx_counter as "sha1_long_len" (SG_SHA1_LONG)
 constexpr uint32_t kSha1Long = SG_SHA1_LONG;
+// read by sg_ctx_counter as "cover_pages_tile": bytes of the bodies a workgroup of k_pg_copy writes (sg_cover_pages.hip)
+constexpr uint32_t kPagesTile = 4096;
 // read by sg_ctx_counter as "triage_runs_sort_cap" and "tinput_chunk"
 constexpr uint32_t kTrSort = 8192;    // values the cover fold sorts in LDS (64 KiB of keys)
 constexpr uint32_t kTinChunk = 8192;  // values of a per LDS chunk of tin_intersect (32 KiB)
