@@ -606,7 +606,8 @@ __device__ __forceinline__ uint64_t ub64(const uint64_t* a, uint64_t n, uint64_t
 }
 
 // largest r in [lo, hi] with off[r] <= i (off non-decreasing), searched in
-// `off` (global or LDS pointer).
+// `off` (global or LDS pointer): among equal offsets the last one, and lo
+// itself when i is below off[lo] (off[lo] is never read).
 template <typename P>
 __device__ __forceinline__ uint64_t seg_search(P off, uint64_t lo, uint64_t hi, uint64_t i) {
   while (lo < hi) {
@@ -622,7 +623,9 @@ __device__ __forceinline__ uint64_t seg_search(P off, uint64_t lo, uint64_t hi, 
 // Inclusive wave64 scans through DPP: row shifts within the 16-lane rows,
 // then the row broadcasts of lanes 15 and 31 (no LDS-crossbar shuffles; the
 // per-tile scans of the partition and merge kernels run on one wave while
-// the others wait at a barrier).
+// the others wait at a barrier).  Both need the full wave: a lane that has
+// exited hands its neighbours 0 (add) or -1 (max) instead of its partial
+// result, so every caller keeps all 64 lanes to the call, idle ones with 0 / -1.
 __device__ __forceinline__ uint32_t wave_incl_add(uint32_t x) {
   x += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0x111, 0xF, 0xF, false);  // row_shr:1
   x += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0x112, 0xF, 0xF, false);  // row_shr:2

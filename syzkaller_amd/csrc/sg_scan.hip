@@ -80,12 +80,14 @@ __global__ void k_scan_total(uint64_t* out, uint64_t n, const uint64_t* tile_bas
 }
 
 size_t scan_ws_bytes(uint64_t n) {
+  // (a single count has a level too: its one tile's sum and base, and the sum
+  // the scan of that base writes behind them)
   size_t b = 0;
-  while (n > 1) {
+  do {
     uint64_t t = (n + kScanTile - 1) / kScanTile;
     b += 2 * ((t * 8 + 255) & ~255ull);
     n = t;
-  }
+  } while (n > 1);
   return b + 512;
 }
 

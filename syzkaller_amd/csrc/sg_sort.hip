@@ -194,9 +194,16 @@ size_t radix_sort_ws(uint64_t n) {
 
 // Sorts n keys of a (device) stably; b is scratch of n keys.  *sorted is a
 // or b, whichever holds the result.  Uses the workspace from ws_used on
-// (radix_sort_ws(n) bytes, reserved by the caller).  vary: the key bits that
-// may differ between keys (a superset is fine), or 0 to find them with one
-// reduction and a host sync.
+// (radix_sort_ws(n) bytes, reserved by the caller).  vary: the key bits to
+// sort by, or 0 to take the bits that differ between keys (one reduction and
+// a host sync).  The passes are the 8-bit windows at ctz(vary), ctz(vary) + 8,
+// .. in which vary has a bit, and the result is the stable order by those
+// windows, whole: a window's bits outside vary count too, so they are either
+// the same in every key or meant.  Every bit outside the windows travels as
+// payload: keys equal in the windows keep their order (sg_deflate.hip and
+// sg_inflate.hip sort by a class in bits 32..42 over an index in the low 32,
+// rank_group_first relies on the same).  An even number of passes leaves the
+// result in a, an odd one in b.
 int radix_sort_u64(sg_ctx* ctx, uint64_t* a, uint64_t* b, uint64_t n, size_t ws_used, uint64_t** sorted,
                    uint64_t vary) {
   *sorted = a;

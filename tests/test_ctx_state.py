@@ -45,7 +45,7 @@ COUNTERS = {
     "host_copy_bytes": 0, "host_copy_ns": 0, "host_wait_ns": 0, "host_copy_threads": 0,
     "m0_filter_used": 0, "m0_filter_fallback": 0, "m0_filter_survivors": 0,
     "m0_filter_queued_milli": (1 << 64) - 1, "m0_filter_halves_log": 0,
-    "flag_skip_used": 0, "flag_skip_full_blocks": 0,
+    "flag_skip_used": 0, "flag_skip_full_blocks": 0, "flag_skip_all_flagged": 0,
     "hints_candidates": 0, "exec_comps_general": 0, "exec_cover_general": 0,
     "merge_pairs_generic": 0, "merge_pairs_diff_small": 0, "merge_pairs_gap": 0, "merge_pairs_tile": 0,
     "canon_wave_lists": 0, "canon_block_lists": 0, "canon_big_segments": 0, "canon_merge_passes": 0,
@@ -54,8 +54,11 @@ COUNTERS = {
     "triage_runs_foreach": 0,
     "prio_bad_ids": 0, "sha1_long_progs": 0, "inflate_long_streams": 0,
     "sha1_long_len": _define("SG_SHA1_LONG"), "inflate_long_len": _define("SG_INFLATE_LONG"),
+    "deflate_long_streams": 0, "deflate_long_len": _define("SG_DEFLATE_LONG"),
+    "deflate_stored_streams": 0, "deflate_fixed_streams": 0, "deflate_dynamic_streams": 0,  # (the last call's: none)
     "prio_band_cells": 40960, "prio_short_len": 64, "triage_runs_sort_cap": 8192, "tinput_chunk": 8192,
     "exec_comps_fast_cap": _define("SG_EXEC_COMPS_FAST_CAP"), "exec_cover_fast_cap": _define("SG_EXEC_COVER_FAST_CAP"),
+    "cover_pages_tile": 4096,  # kPagesTile
     "cpu_quota_milli": None,
     "workspace_bytes": 0,  # (nothing is reserved before the first call that needs the workspace)
 }
@@ -70,6 +73,16 @@ def test_option_table_cpp(tmp_path):
     out = subprocess.run([exe], capture_output=True, text=True, timeout=60, check=True).stdout
     assert len(OPTIONS) == 16
     assert out.splitlines() == ["%d %s %d %d %d" % ((i,) + row) for i, row in enumerate(OPTIONS)]
+
+
+def test_counter_table_is_complete():
+    """COUNTERS holds every row of kCounters (sg_ctx.hip), and nothing else."""
+    src = open(os.path.join(ROOT, "syzkaller_amd", "csrc", "sg_ctx.hip")).read()
+    table = src[src.index("const Counter kCounters[] = {"):]
+    table = table[: table.index("\n};")]
+    rows = re.findall(r'^\s*\{"([a-z0-9_]+)",', table, flags=re.M)
+    assert len(rows) == len(set(rows)) == 52
+    assert set(rows) == set(COUNTERS)
 
 
 @pytest.fixture
@@ -120,7 +133,7 @@ def test_counters_on_a_fresh_context(fresh_ctx):
     from syzkaller_amd._lib import SG_EINVAL, SyzSigError
 
     c = fresh_ctx
-    assert len(COUNTERS) == 45
+    assert len(COUNTERS) == 52
     for name, want in COUNTERS.items():
         got = c.counter(name)
         if want is not None:
