@@ -1588,6 +1588,191 @@ int sg_db_serialize(sg_ctx* ctx, const uint8_t* keys, const uint64_t* key_off, c
  * with cap > 0. */
 int sg_db_compact(sg_db* db, uint8_t* out, size_t cap, size_t* nout);
 
+/* ---- cover report ingest: binutils text to the cover table's arrays ---------- */
+/* What stands between vmlinux and sg_cover_table_create: the reference scans
+ * all of `objdump -d --no-show-raw-insn vmlinux` for the __sanitizer_cov_trace_pc
+ * call sites (coveredPCs, syz-manager/cover.go:310-347) and sorts them
+ * (initAllCover, :64-89), and parses `nm -nS vmlinux` (symbolizer.ReadSymbols,
+ * pkg/symbolizer/nm.go:19-69) into the symbols that uncoveredPcsInFuncs
+ * flattens and sorts (cover.go:262-268).  Both are byte-parallel scans of a
+ * text; here each is one call over the whole text.
+ *
+ * Lines, pinned (bufio.Scanner / ScanLines, as for prog.CallSet above): the
+ * text is split at '\n'; the bytes after the last '\n' are a line only if there
+ * are any; one trailing '\r' is dropped from each line; empty lines are lines.
+ * The scanner's limit is bufio.MaxScanTokenSize: a line whose content -- the
+ * bytes before its '\n' or before the end of the text, the '\r' counted -- is
+ * SG_INGEST_MAX_LINE bytes or more makes the whole call fail as the
+ * reference's s.Err() does: status SG_INGEST_TOO_LONG, err_pos the byte offset
+ * of the first such line's start, a count of 0 and no other output.  That
+ * boundary is read, not run (Go is not needed to build or test this library).
+ *
+ * A hex field is strconv.ParseUint(field, 16, 64): at least one byte, every
+ * byte in [0-9a-fA-F] (no sign, no "0x", no '_', no blank), the value at most
+ * 2^64 - 1 -- judged by value, so any number of leading zeros is fine and a
+ * seventeenth significant digit is an error. */
+#define SG_INGEST_OK 0
+#define SG_INGEST_TOO_LONG 1
+#define SG_INGEST_MAX_LINE 65536
+#define SG_INGEST_MAX_NEEDLE 64
+
+/* coveredPCs (cover.go:310-347) and the sort of cover.go:78.  Of each line:
+ * pos is the first occurrence of `call` (call_len bytes); `func` must occur in
+ * ln[pos:] (it may overlap the call match); colon is the first ':' of the
+ * line; ln[:colon] must be a hex field as above (so a line that objdump
+ * indents with blanks is skipped).  A line that fails any step is skipped
+ * silently.  The reference's needles are "callq " and
+ * " <__sanitizer_cov_trace_pc>"; newer binutils print "call ".  pcs receives the
+ * PCs ascending, duplicates kept; *npcs is always their number and pcs is
+ * written only when it is <= cap.  nbytes / 2 + 1 always suffices as cap (a
+ * kept line is at least a digit and ':'; the needles may overlap the field).  SG_EINVAL, before the context is touched: a NULL
+ * ctx, npcs, status or err_pos; text NULL with nbytes > 0; pcs NULL with cap >
+ * 0; a NULL needle or a needle length outside 1..SG_INGEST_MAX_NEEDLE; 2^33
+ * bytes of text or more.  SG_ENODEV without a device.  Two waits (the count,
+ * the PCs), and one more inside the sort. */
+int sg_objdump_pcs(sg_ctx* ctx, const uint8_t* text, size_t nbytes, const uint8_t* call, size_t call_len,
+		   const uint8_t* func, size_t func_len, uint64_t* pcs, size_t cap, size_t* npcs, uint32_t* status,
+		   uint64_t* err_pos);
+/* Device form: d_text and d_pcs are device memory (the needles stay host
+ * memory), and the PCs stay resident; d_info (device, 3 words) receives
+ * {count, status, err_pos}.  The call waits once for the count, which sizes
+ * the sort; nothing else is read back. */
+int sg_objdump_pcs_dev(sg_ctx* ctx, const uint8_t* d_text, uint64_t nbytes, const uint8_t* call, size_t call_len,
+		       const uint8_t* func, size_t func_len, uint64_t* d_pcs, uint64_t cap, uint64_t* d_info);
+
+/* symbolizer.ReadSymbols (nm.go:19-69) and the flatten-and-sort of
+ * cover.go:262-268.  Of each line: sp1 is the first ' ', sp2 the next ' '
+ * after it; ln[sp2:] must start with " t " or " T " (which is also the
+ * reference's first test, that the line contains one of the two); ln[:sp1]
+ * and ln[sp1+1:sp2] must be hex fields as above, addr and size; name =
+ * ln[sp2+3:], which may be empty and may contain blanks.  A line that fails any
+ * step is skipped, so `0000000000401000 T _init` (no size column) is.
+ * Size = int(size+15)/16*16: the add wraps in 64 bits, the sum is taken as
+ * int64, the division truncates toward zero; end = addr + uint64(Size), wrapping.
+ *
+ * Symbol k, in text order: addr[k], size[k] (Size), and its name's bytes
+ * text[name_pos[k] .. name_pos[k] + name_len[k]).  sym_start / sym_end are the
+ * symbols in the order sg_cover_uncovered and sg_cover_table_create want,
+ * ascending by start, and order[j] is the text-order index of the symbol in
+ * sorted place j.  The reference flattens a map and sorts with the unstable
+ * sort.Sort, so its order among equal starts is undefined; here it is pinned
+ * as (start, text order).  Any of the seven arrays may be NULL (not wanted).
+ * *nsyms is always the number of symbols; the arrays are written only when
+ * it is <= cap.  nbytes / 6 + 1 always suffices as cap.  SG_EINVAL, before the
+ * context is touched: a NULL ctx, nsyms, status or err_pos; text NULL with
+ * nbytes > 0; 2^33 bytes of text or more.  SG_EINVAL after the count: 2^32 - 1
+ * symbols or more.  SG_ENODEV without a device.  Two waits. */
+int sg_nm_symbols(sg_ctx* ctx, const uint8_t* text, size_t nbytes, uint64_t* addr, int64_t* size, uint64_t* name_pos,
+		  uint32_t* name_len, uint64_t* sym_start, uint64_t* sym_end, uint32_t* order, size_t cap, size_t* nsyms,
+		  uint32_t* status, uint64_t* err_pos);
+/* Device form: every array is device memory, d_info as sg_objdump_pcs_dev's;
+ * one wait, for the count. */
+int sg_nm_symbols_dev(sg_ctx* ctx, const uint8_t* d_text, uint64_t nbytes, uint64_t* d_addr, int64_t* d_size,
+		      uint64_t* d_name_pos, uint32_t* d_name_len, uint64_t* d_sym_start, uint64_t* d_sym_end,
+		      uint32_t* d_order, uint64_t cap, uint64_t* d_info);
+
+/* symbolize and parse (pkg/symbolizer/symbolizer.go:95-191) over the whole
+ * output of `addr2line -afi` for nrec PCs (the reference's len(pcs): the record
+ * of its sentinel 0xffffffffffffffff, and anything behind the start of record
+ * nrec, is never looked at), with the interning that fileSet's string compares
+ * need (sg_cover_table_create: "equal strings MUST get equal ids").
+ *
+ * Lines as above.  The first line is record 0's PC line.  After it a record
+ * starts at a line with len > 3, ln[0] == '0' and ln[1] == 'x' met where a
+ * function line is expected; function and file lines alternate.  A PC line is
+ * strconv.ParseUint(line, 0, 64): "0x" / "0X" hex, "0b" binary, "0o" or a
+ * leading "0" octal, else decimal, '_' between digits as base 0 allows.  Of a
+ * file line colon is the LAST ':', the line number the digits that follow it
+ * (so ":588 (discriminator 3)" is 588) and file = ln[:colon].  A frame is
+ * dropped, its two lines consumed, when the digits are empty or overflow int
+ * (64 bits), fn or file is "" or "??", or line <= 0.  A record may have no
+ * frames.  The last record ends at the next start, at a "0x" line with a ':'
+ * where a function line is expected (the reference leaves parse there and never
+ * parses again), or at the end of the text.
+ *
+ * The whole call fails (status, and err_pos the byte offset of the failing
+ * line's start; the first failure in text order, no other output) on:
+ *   SG_A2L_EMPTY 1         no line at all (err_pos 0);
+ *   SG_A2L_BAD_PC 2        a PC line that does not parse -- the first line, or
+ *                          a "0x" line with a ':' where a function line is
+ *                          expected before the last record;
+ *   SG_A2L_NO_COLON 3      a file line without ':' (a record start met where a
+ *                          file line is expected is one);
+ *   SG_A2L_NO_FILE_LINE 4  the text ends behind a function line (err_pos: that
+ *                          line);
+ *   SG_A2L_TOO_LONG 5      a line of SG_INGEST_MAX_LINE bytes or more among the
+ *                          lines read;
+ *   SG_A2L_TOO_FEW 6       fewer than nrec records (err_pos nbytes; the
+ *                          reference would block on its pipe).
+ * The records are found in parallel: after line 0 the starts are the "0x"
+ * lines without ':' (in a text the reference parses, exactly those), a scan
+ * gives each line its record and its place in it, and place parity and shape
+ * turn into the failures above.
+ *
+ * rec_pc[r] is record r's PC; its kept frames are frame_off[r] ..
+ * frame_off[r+1] (nrec + 1 entries) of frame_file / frame_line / frame_func,
+ * in text order.  File and Func ids are dense in order of first occurrence
+ * among the kept frames, which is what setdefault(name, len(dict)) gives; id
+ * k's bytes are text[file_pos[k] .. + file_len[k]) (func_pos / func_len
+ * likewise), its first occurrence.  Names are hashed (FNV-1a, 64 bits; hash_bits,
+ * 1..64, 64 in production, masks the first round's hash so a test can force
+ * the path below: the results are the same at every value) and grouped by hash, and every member of a group is
+ * compared with the group's first BY BYTES; when any group holds two different
+ * names the whole column is grouped again under another seed of the full hash
+ * (at most 4 rounds, then SG_EHIP: never a wrong id, never a host fallback).
+ * info (6 words): {frames, nfiles, nfuncs, status, err_pos, extra rounds}.
+ * The frame and name arrays are written only when frames <= cap (names never
+ * outnumber frames).  SG_EINVAL, before the context is touched: a NULL ctx or
+ * info; text NULL with nbytes > 0; rec_pc or frame_off NULL; a frame or name
+ * array NULL with cap > 0; nrec >= 2^32 - 1; hash_bits outside 1..64; 2^33
+ * bytes of text or more.
+ * SG_EINVAL after the line count: 2^32 - 1 lines or more.  SG_ENODEV without a
+ * device.  A wait each for the line count, the frame count and every interning
+ * round. */
+#define SG_A2L_OK 0
+#define SG_A2L_EMPTY 1
+#define SG_A2L_BAD_PC 2
+#define SG_A2L_NO_COLON 3
+#define SG_A2L_NO_FILE_LINE 4
+#define SG_A2L_TOO_LONG 5
+#define SG_A2L_TOO_FEW 6
+int sg_addr2line_frames(sg_ctx* ctx, const uint8_t* text, size_t nbytes, size_t nrec, uint64_t* rec_pc,
+			uint64_t* frame_off, uint32_t* frame_file, int64_t* frame_line, uint32_t* frame_func, size_t cap,
+			uint64_t* file_pos, uint32_t* file_len, uint64_t* func_pos, uint32_t* func_len, uint32_t hash_bits,
+			uint64_t* info);
+/* Device form: every array and info are device memory; the same waits. */
+int sg_addr2line_frames_dev(sg_ctx* ctx, const uint8_t* d_text, uint64_t nbytes, uint64_t nrec, uint64_t* d_rec_pc,
+			    uint64_t* d_frame_off, uint32_t* d_frame_file, int64_t* d_frame_line, uint32_t* d_frame_func,
+			    uint64_t cap, uint64_t* d_file_pos, uint32_t* d_file_len, uint64_t* d_func_pos,
+			    uint32_t* d_func_len, uint32_t hash_bits, uint64_t* d_info);
+
+/* The cover table straight from the tools' text: sg_nm_symbols over nm_text,
+ * sg_addr2line_frames over a2l_text for nrec records, and the table that
+ * sg_cover_table_create would build from their arrays with tab_pcs = the
+ * records' PCs -- indistinguishable from it through sg_cover_lines and
+ * sg_cover_pages.  The records' PCs, frame_off and the frame arrays are never on
+ * the host: they go from the parse to the table on the device.  The symbols
+ * (a few MB of text) and all_pcs, the call sites (host memory; sg_objdump_pcs'
+ * result, which must be distinct), are host arrays, as the table's plan reads
+ * them there.  What sg_cover_table_create demands of the rest is checked on the
+ * device and reported as SG_EINVAL after the build's wait, with no table: the
+ * records' PCs strictly ascending, every call site among them, every line
+ * below 2^32.  The names come back as sg_addr2line_frames returns them, when
+ * the frames (which names never outnumber) are <= names_cap; with more, only
+ * the counts come back, *out stays NULL and the call is made again.
+ * info (8 words): sg_addr2line_frames' six, then sg_nm_symbols' status and
+ * err_pos; with either status set *out stays NULL and the call returns SG_OK.
+ * SG_EINVAL, before the context is touched: a NULL ctx, out or info; a text
+ * NULL with bytes; all_pcs NULL with nall > 0; a name array NULL with
+ * names_cap > 0; nrec >= 2^32 - 1; hash_bits outside 1..64; a text of 2^33
+ * bytes or more.  SG_EINVAL later: symbols or call sites out of order
+ * (host), 2^32 - 1 frames or more.  SG_ENODEV without a device.  The table
+ * belongs to ctx (sg_cover_lines rejects a set of another context as before). */
+int sg_cover_table_from_text(sg_ctx* ctx, const uint8_t* nm_text, size_t nm_bytes, const uint64_t* all_pcs, size_t nall,
+			     const uint8_t* a2l_text, size_t a2l_bytes, size_t nrec, uint32_t hash_bits, uint64_t* file_pos,
+			     uint32_t* file_len, uint64_t* func_pos, uint32_t* func_len, size_t names_cap, uint64_t* info,
+			     sg_cover_table** out);
+
 #ifdef __cplusplus
 }
 #endif

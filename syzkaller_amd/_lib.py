@@ -205,6 +205,19 @@ SIGNATURES = {
     "sg_deflate_batch_dev": (c_int, [c_void_p, c_void_p, c_void_p, c_uint64, c_uint64, c_void_p, c_void_p, c_uint64]),
     "sg_db_serialize": (c_int, [c_void_p, P8, P64, P64, P8, P64, c_size_t, c_int, P8, c_size_t, PSZ]),
     "sg_db_compact": (c_int, [c_void_p, P8, c_size_t, PSZ]),
+    "sg_objdump_pcs": (c_int, [c_void_p, P8, c_size_t, P8, c_size_t, P8, c_size_t, P64, c_size_t, PSZ, P32, P64]),
+    "sg_objdump_pcs_dev": (c_int, [c_void_p, c_void_p, c_uint64, P8, c_size_t, P8, c_size_t, c_void_p, c_uint64,
+                                   c_void_p]),
+    "sg_nm_symbols": (c_int, [c_void_p, P8, c_size_t, P64, POINTER(c_int64), P64, P32, P64, P64, P32, c_size_t, PSZ, P32,
+                              P64]),
+    "sg_nm_symbols_dev": (c_int, [c_void_p, c_void_p, c_uint64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                  c_void_p, c_void_p, c_uint64, c_void_p]),
+    "sg_addr2line_frames": (c_int, [c_void_p, P8, c_size_t, c_size_t, P64, P64, P32, POINTER(c_int64), P32, c_size_t, P64,
+                                    P32, P64, P32, c_uint32, P64]),
+    "sg_cover_table_from_text": (c_int, [c_void_p, P8, c_size_t, P64, c_size_t, P8, c_size_t, c_size_t, c_uint32, P64, P32,
+                                         P64, P32, c_size_t, P64, POINTER(c_void_p)]),
+    "sg_addr2line_frames_dev": (c_int, [c_void_p, c_void_p, c_uint64, c_uint64, c_void_p, c_void_p, c_void_p, c_void_p,
+                                        c_void_p, c_uint64, c_void_p, c_void_p, c_void_p, c_void_p, c_uint32, c_void_p]),
     "sg_ipc_parse": (c_int,[c_void_p, P32, P64, P64, P32, c_size_t, POINTER(c_int64), P8, POINTER(c_int32), P64, P32,
                              P64, P32]),
     "sg_ipc_parse_dev": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_uint64, c_uint64, c_void_p,

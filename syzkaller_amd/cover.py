@@ -594,6 +594,192 @@ def cover_uncovered(cov, base, sym_start, sym_end, all_pcs, ctx=None):
     return out[: n.value]
 
 
+INGEST_MAX_LINE = 65536  # bufio.MaxScanTokenSize (include/syzsig.h SG_INGEST_MAX_LINE)
+
+
+class LineTooLong(ValueError):
+    """bufio.Scanner's ErrTooLong for a tool's output: `pos` is the byte offset of the first line whose content
+    is INGEST_MAX_LINE bytes or more."""
+
+    def __init__(self, fn, pos):
+        super().__init__(f"{fn}: bufio.Scanner: token too long (the line at byte {pos})")
+        self.pos = pos
+
+
+def _text_u8(text):
+    if isinstance(text, np.ndarray):
+        return np.ascontiguousarray(text.astype(np.uint8, copy=False).reshape(-1))
+    return np.frombuffer(text, dtype=np.uint8)
+
+
+def objdump_pcs(text, call=b"callq ", func=b" <__sanitizer_cov_trace_pc>", ctx=None):
+    """coveredPCs (syz-manager/cover.go:310-347) over the bytes of `objdump -d --no-show-raw-insn vmlinux`, and
+    initAllCover's sort (:78): the call sites' PCs ascending, duplicates kept.  call / func are the two needles
+    (newer binutils print b"call ").  Raises LineTooLong where the reference returns the scanner's error."""
+    t = _text_u8(text)
+    nc, nf = np.frombuffer(bytes(call), dtype=np.uint8), np.frombuffer(bytes(func), dtype=np.uint8)
+    cap = t.size // 2 + 1  # (a kept line is at least a digit and ':': the needles may overlap the field)
+    pcs = np.empty(cap, dtype=U64)
+    n, st, pos = c_size_t(), ctypes.c_uint32(), c_uint64()
+    _lib.call("sg_objdump_pcs", _ctx(ctx).h, _p8(t), t.size, _p8(nc), nc.size, _p8(nf), nf.size, _p64(pcs), cap,
+              byref(n), byref(st), byref(pos))  # (`call` is the needle here)
+    if st.value:
+        raise LineTooLong("objdump_pcs", pos.value)
+    return pcs[: n.value]
+
+
+class NmSymbols:
+    """nm_symbols' result.  Symbol k in text order: addr[k], size[k] (rounded up to 16 as ReadSymbols does) and
+    name(k); sym_start / sym_end in the order cover_uncovered and CoverTable want (start, then text order), and
+    order[j] the text-order index of sorted place j."""
+
+    def __init__(self, text, addr, size, name_pos, name_len, sym_start, sym_end, order):
+        self.text = text
+        self.addr, self.size, self.name_pos, self.name_len = addr, size, name_pos, name_len
+        self.sym_start, self.sym_end, self.order = sym_start, sym_end, order
+
+    def __len__(self):
+        return int(self.addr.size)
+
+    def name(self, k):
+        p = int(self.name_pos[k])
+        return self.text[p:p + int(self.name_len[k])].tobytes()
+
+
+def nm_symbols(text, ctx=None):
+    """symbolizer.ReadSymbols (pkg/symbolizer/nm.go:19-69) over the bytes of `nm -nS vmlinux`, then the flatten and
+    sort of uncoveredPcsInFuncs (cover.go:262-268).  Raises LineTooLong as objdump_pcs does."""
+    t = _text_u8(text)
+    cap = t.size // 6 + 1
+    addr, npos, ss, se = (np.empty(cap, dtype=U64) for _ in range(4))
+    size = np.empty(cap, dtype=np.int64)
+    nlen, order = np.empty(cap, dtype=U32), np.empty(cap, dtype=U32)
+    n, st, pos = c_size_t(), ctypes.c_uint32(), c_uint64()
+    _lib.call("sg_nm_symbols", _ctx(ctx).h, _p8(t), t.size, _p64(addr), size.ctypes.data_as(ctypes.POINTER(c_int64)),
+              _p64(npos), _p32(nlen), _p64(ss), _p64(se), _p32(order), cap, byref(n), byref(st), byref(pos))
+    if st.value:
+        raise LineTooLong("nm_symbols", pos.value)
+    k = n.value
+    return NmSymbols(t, addr[:k], size[:k], npos[:k], nlen[:k], ss[:k], se[:k], order[:k])
+
+
+A2L_OK, A2L_EMPTY, A2L_BAD_PC, A2L_NO_COLON, A2L_NO_FILE_LINE, A2L_TOO_LONG, A2L_TOO_FEW = 0, 1, 2, 3, 4, 5, 6
+_A2L_WHAT = {A2L_EMPTY: "EOF", A2L_BAD_PC: "failed to parse pc in addr2line output",
+             A2L_NO_COLON: "failed to parse file:line in addr2line output",
+             A2L_NO_FILE_LINE: "failed to read file:line from addr2line: EOF",
+             A2L_TOO_LONG: "bufio.Scanner: token too long", A2L_TOO_FEW: "fewer records than PCs"}
+
+
+class Addr2lineError(ValueError):
+    """symbolize's error for a whole addr2line output: `status` (A2L_*, include/syzsig.h SG_A2L_*) and `pos`, the
+    byte offset of the failing line."""
+
+    def __init__(self, status, pos):
+        super().__init__(f"addr2line_frames: {_A2L_WHAT.get(status, status)} (byte {pos})")
+        self.status, self.pos = status, pos
+
+
+class Addr2lineFrames:
+    """addr2line_frames' result: rec_pc[r] and, for record r, frames frame_off[r]:frame_off[r+1] of frame_file /
+    frame_line / frame_func; file id k is file(k), func id k is func(k), ids in order of first occurrence."""
+
+    def __init__(self, text, rec_pc, frame_off, frame_file, frame_line, frame_func, spans, rounds):
+        self.text, self.rec_pc, self.frame_off = text, rec_pc, frame_off
+        self.frame_file, self.frame_line, self.frame_func = frame_file, frame_line, frame_func
+        self.file_pos, self.file_len, self.func_pos, self.func_len = spans
+        self.nfiles, self.nfuncs, self.rounds = int(self.file_pos.size), int(self.func_pos.size), rounds
+
+    def _names(self, pos, ln):
+        t = self.text.tobytes()
+        return [t[p:p + n] for p, n in zip(pos.tolist(), ln.tolist())]
+
+    def files(self):
+        return self._names(self.file_pos, self.file_len)
+
+    def funcs(self):
+        return self._names(self.func_pos, self.func_len)
+
+
+def addr2line_frames(text, nrec, hash_bits=64, ctx=None):
+    """symbolize / parse (pkg/symbolizer/symbolizer.go:95-191) over the bytes `addr2line -afi` wrote for nrec PCs
+    (and its sentinel), with File and Func interned on the device.  Raises Addr2lineError where the reference
+    returns an error.  hash_bits below 64 only forces the interning's other rounds (tests)."""
+    t = _text_u8(text)
+    nrec = int(nrec)
+    rec_pc, frame_off, info = np.zeros(max(nrec, 1), dtype=U64), np.zeros(nrec + 1, dtype=U64), np.zeros(6, dtype=U64)
+    cap = t.size // 32 + 1  # a guess; the call is made again with the count when the frames outnumber it
+    for _ in range(2):
+        ff, fu, fl_len, fn_len = (np.empty(cap, dtype=U32) for _ in range(4))
+        line = np.empty(cap, dtype=np.int64)
+        fl_pos, fn_pos = np.empty(cap, dtype=U64), np.empty(cap, dtype=U64)
+        _lib.call("sg_addr2line_frames", _ctx(ctx).h, _p8(t), t.size, nrec, _p64(rec_pc), _p64(frame_off), _p32(ff),
+                  line.ctypes.data_as(ctypes.POINTER(c_int64)), _p32(fu), cap, _p64(fl_pos), _p32(fl_len), _p64(fn_pos),
+                  _p32(fn_len), hash_bits, _p64(info))
+        nfr, nfiles, nfuncs, status, pos, rounds = (int(x) for x in info)
+        if nfr <= cap:
+            break
+        cap = nfr
+    if status:
+        raise Addr2lineError(status, pos)
+    return Addr2lineFrames(t, rec_pc[:nrec], frame_off, ff[:nfr], line[:nfr], fu[:nfr],
+                           (fl_pos[:nfiles], fl_len[:nfiles], fn_pos[:nfuncs], fn_len[:nfuncs]), rounds)
+
+
+_GO_SPACE = ("\t\n\v\f\r \u0085\u00a0\u1680\u2000\u2001\u2002\u2003\u2004\u2005\u2006\u2007\u2008\u2009\u200a"
+             "\u2028\u2029\u202f\u205f\u3000")  # unicode.IsSpace, which strings.Fields splits at
+
+
+def _parse_uint_0x(digits):
+    """strconv.ParseUint("0x" + digits, 0, 64), or None: base 0 lets '_' separate digits (and follow the prefix)."""
+    last = "0"
+    for c in digits:
+        if c in "0123456789abcdefABCDEF":
+            last = "0"
+        elif c == "_" and last == "0":
+            last = "_"
+        else:
+            return None
+    digits = digits.replace("_", "")
+    if last == "_" or not digits:
+        return None
+    v = int(digits, 16)
+    return v if v < 1 << 64 else None
+
+
+def vm_offset(readelf_text):
+    """getVmOffset (syz-manager/cover.go:219-254) over the bytes of `readelf -SW vmlinux`: the upper 32 bits that
+    every non-zero PROGBITS address shares.  Host only (a few KB of text).  ValueError where the reference returns
+    an error, and also where it panics (PROGBITS as a line's last field: pieces[i+1] is out of range).  The
+    reference never looks at its scanner's error, so a line of INGEST_MAX_LINE bytes or more ends the scan there
+    and what came before it counts."""
+    data = bytes(readelf_text)
+    addr, s = 0, 0
+    while s < len(data):
+        e = data.find(b"\n", s)
+        e = len(data) if e < 0 else e
+        if e - s >= INGEST_MAX_LINE:
+            break
+        ln = data[s:e - 1] if e > s and data[e - 1:e] == b"\r" else data[s:e]
+        s = e + 1
+        pieces = [p for p in ln.decode("utf-8", "replace").translate({ord(c): " " for c in _GO_SPACE}).split(" ") if p]
+        for i, p in enumerate(pieces):
+            if p != "PROGBITS":
+                continue
+            if i + 1 >= len(pieces):
+                raise ValueError("vm_offset: PROGBITS is the last field of a line (the reference panics)")
+            v = _parse_uint_0x(pieces[i + 1])
+            if v is None:
+                raise ValueError(f"failed to parse addr in readelf output: {pieces[i + 1]!r}")
+            if v == 0:
+                continue
+            v32 = v >> 32
+            if addr == 0:
+                addr = v32
+            if addr != v32:
+                raise ValueError("different section offsets in a single binary")
+    return addr
+
+
 class CoverTable:
     """sg_cover_table: the symbols, the call sites and the frames of every
     symbolised PC, on the device (include/syzsig.h).  The frames of tab_pcs[j]
@@ -612,10 +798,45 @@ class CoverTable:
         h = c_void_p()
         call("sg_cover_table_create", self.ctx.h, _p64(ss), _p64(se), ss.size, _p64(ap), ap.size, _p64(tp), tp.size,
              _p64(fo), _p32(ff), _p32(fl), _p32(fn), self.nfiles, self.nfuncs, byref(h))
+        self._adopt(h)
+
+    def _adopt(self, h):
         self.h = h
         n = c_uint64()
         call("sg_cover_table_slots", self.h, byref(n))
         self.nslots = n.value
+
+    @classmethod
+    def from_text(cls, nm_text, all_pcs, addr2line_text, nrec=None, hash_bits=64, ctx=None):
+        """The table from the tools' text in one call (sg_cover_table_from_text): `nm -nS` output, the call sites
+        (objdump_pcs' result: ascending, distinct) and what `addr2line -afi` wrote for nrec PCs that include them
+        (default: exactly the call sites).  The records' PCs and the frame arrays never leave the device.  Returns
+        (table, files, funcs), the names as bytes by id, ids in order of first occurrence."""
+        c = _ctx(ctx)
+        nm, at, ap = _text_u8(nm_text), _text_u8(addr2line_text), _u64(all_pcs)
+        nrec = ap.size if nrec is None else int(nrec)
+        cap = at.size // 32 + 1  # a guess; the call is made again with the count when the frames outnumber it
+        info, h = np.zeros(8, dtype=U64), c_void_p()
+        for _ in range(2):
+            fpos, upos = np.empty(cap, dtype=U64), np.empty(cap, dtype=U64)
+            flen, ulen = np.empty(cap, dtype=U32), np.empty(cap, dtype=U32)
+            call("sg_cover_table_from_text", c.h, _p8(nm), nm.size, _p64(ap), ap.size, _p8(at), at.size, nrec, hash_bits,
+                 _p64(fpos), _p32(flen), _p64(upos), _p32(ulen), cap, _p64(info), byref(h))
+            nfr, nfiles, nfuncs, status, pos, _, nm_status, nm_pos = (int(x) for x in info)
+            if nm_status:
+                raise LineTooLong("nm_symbols", nm_pos)
+            if status:
+                raise Addr2lineError(status, pos)
+            if nfr <= cap:
+                break
+            cap = nfr
+        self = cls.__new__(cls)
+        self.ctx, self.nfiles, self.nfuncs = c, nfiles, nfuncs
+        self._adopt(h)
+        t = at.tobytes()
+        files = [t[p:p + n] for p, n in zip(fpos[:nfiles].tolist(), flen[:nfiles].tolist())]
+        funcs = [t[p:p + n] for p, n in zip(upos[:nfuncs].tolist(), ulen[:nfuncs].tolist())]
+        return self, files, funcs
 
     def close(self):
         if self.h:
@@ -751,18 +972,53 @@ class CoverReport:
     ascending; names are distinct, so the order is total."""
 
     def __init__(self, sym_start, sym_end, all_pcs, symbolize, ctx=None, read_file=None):
+        self._init(sym_start, sym_end, all_pcs, ctx, read_file)
+        self.symbolize = symbolize
+        self.frames = {}                 # pc -> [(file id, line, func id), ...]
+        self._add(self.all_pcs)
+        self._build()
+
+    def _init(self, sym_start, sym_end, all_pcs, ctx, read_file):
         self.ctx = _ctx(ctx)
         self.read_file = read_file
         self.src = None
         self.sym_start, self.sym_end, self.all_pcs = _u64(sym_start), _u64(sym_end), _u64(all_pcs)
-        self.symbolize = symbolize
         self.files, self.funcs = {}, {}  # name -> id
-        self.frames = {}                 # pc -> [(file id, line, func id), ...]
         self.table = None
-        self._add(self.all_pcs)
+        self._tools = None               # from_tools: (nm text, addr2line); then the table comes from text
+
+    @classmethod
+    def from_tools(cls, nm_text, objdump_text, addr2line, read_file=None, ctx=None):
+        """The report from the tools' raw output: nm_text is `nm -nS vmlinux`'s, objdump_text `objdump -d
+        --no-show-raw-insn vmlinux`'s, and addr2line(pcs) -> bytes what `addr2line -afi -e vmlinux` writes for
+        those PCs and the sentinel 0xffffffffffffffff (symbolizer.go:122-131).  files, funcs, names and the table
+        are what the constructor reaches from the same tools through a symbolize callable; names are str (UTF-8,
+        undecodable bytes as surrogates).  Nothing here works per frame: the texts are parsed, the names interned
+        and the table built on the device (CoverTable.from_text), and only the distinct names come back.  `frames`
+        is made from the last addr2line output when somebody asks for it.  Covered PCs the table does not know
+        join the table's PCs and addr2line is asked again, for all of them."""
+        c = _ctx(ctx)
+        syms = nm_symbols(nm_text, ctx=c)
+        self = cls.__new__(cls)
+        self._init(syms.sym_start, syms.sym_end, objdump_pcs(objdump_text, ctx=c), c, read_file)
+        self.symbolize = None
+        self._tools = (nm_text, addr2line)
+        self._tab_pcs = self.all_pcs
         self._build()
+        return self
+
+    def __getattr__(self, name):
+        if name == "frames" and self.__dict__.get("_tools"):  # pc -> [(file id, line, func id), ...], on demand
+            fr = addr2line_frames(self._a2l_text, self._tab_pcs.size, ctx=self.ctx)
+            off = fr.frame_off.tolist()
+            rows = list(zip(fr.frame_file.tolist(), fr.frame_line.tolist(), fr.frame_func.tolist()))
+            return {pc: rows[off[r]:off[r + 1]] for r, pc in enumerate(fr.rec_pc.tolist())}
+        raise AttributeError(name)
 
     def _add(self, pcs):
+        if self._tools:
+            self._tab_pcs = np.union1d(self._tab_pcs, _u64(pcs))
+            return
         pcs = [int(pc) for pc in pcs]
         for pc in pcs:
             self.frames.setdefault(pc, [])
@@ -774,6 +1030,18 @@ class CoverReport:
     def _build(self):
         if self.table is not None:
             self.table.close()
+        if self._tools:
+            nm_text, addr2line = self._tools
+            self._a2l_text = addr2line(self._tab_pcs.tolist())
+            self.table, files, funcs = CoverTable.from_text(nm_text, self.all_pcs, self._a2l_text, self._tab_pcs.size,
+                                                            ctx=self.ctx)
+            self.names = [b.decode("utf-8", "surrogateescape") for b in files]
+            self.files = {name: k for k, name in enumerate(self.names)}
+            self.funcs = {b.decode("utf-8", "surrogateescape"): k for k, b in enumerate(funcs)}
+            if self.src is not None:  # (a rebuild numbers the files again)
+                self.src.close()
+                self.src = None
+            return
         tab = sorted(self.frames)
         off = np.zeros(len(tab) + 1, dtype=U64)
         off[1:] = np.cumsum([len(self.frames[pc]) for pc in tab])

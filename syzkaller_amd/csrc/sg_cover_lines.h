@@ -25,6 +25,35 @@ struct sg_cover_table {
 
 namespace sg {
 
+// Where a table's PCs and frames come from.  Host arrays, checked by sg_cover_table_create; or, with dev, device
+// arrays that lie in the context's workspace below dev->ws_base (sg_cover_ingest.hip leaves them there), checked on
+// the device.  vary: the bits in which the frames' file << 32 | line keys differ (0: all equal).
+struct CoverTableDev {
+  const uint64_t* tab;        // [ntab]
+  const uint64_t* frame_off;  // [ntab + 1]
+  const uint32_t* frame_file;
+  const int64_t* frame_line;
+  const uint32_t* frame_func;
+  size_t ws_base;
+};
+struct TableSrc {
+  const uint64_t* tab_pcs;
+  const uint64_t* frame_off;
+  const uint32_t *frame_file, *frame_line, *frame_func;
+  const CoverTableDev* dev;
+  uint64_t vary;
+};
+// (ctx lock held, the device ensured; the symbols and call sites are host arrays that sg_cover_table_create's rules
+// hold for.)  The workspace must hold ws_base + cover_table_build_ws(nfr) bytes already when src.dev is set: the
+// build does not move it.
+int table_build(sg_ctx* ctx, const char* fn, const uint64_t* sym_start, const uint64_t* sym_end, size_t nsym,
+                const uint64_t* all_pcs, size_t nall, size_t ntab, uint64_t tab_lo, uint64_t tab_hi, uint64_t nfr,
+                uint32_t nfiles, uint32_t nfuncs, const TableSrc& src, sg_cover_table** out);
+size_t cover_table_build_ws(uint64_t nfr);
+// what sg_cover_table_create asks of the symbols and the call sites (host arrays)
+int table_syms_ok(const char* fn, const uint64_t* sym_start, const uint64_t* sym_end, size_t nsym, const uint64_t* all_pcs,
+                  size_t nall);
+
 // A report's line tables as cover_lines_body leaves them in the workspace:
 // file f's lines are lines[file_off[f] .. file_off[f + 1]), ascending, cov
 // alongside; only file_off[nfiles] <= nslots entries are written.

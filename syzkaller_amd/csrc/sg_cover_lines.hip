@@ -86,6 +86,35 @@ __global__ void k_ct_site_row(const uint64_t* __restrict__ sites, uint64_t nall,
   if (s < nall) site_row[s] = (uint32_t)lb_idx(tab, ntab, itab, sites[s]);
 }
 
+// The device-resident sources of a table (cover_table_from_dev): what the host checks of sg_cover_table_create
+// for host arrays, here one flag word each, read after the build's one wait.  bad[0]: tab is not strictly
+// ascending; bad[1]: a call site is not in tab; bad[2]: a line is 0 or does not fit 32 bits, an id is out of range
+// or frame_off decreases or ends elsewhere than at nfr.
+__global__ void k_ct_dev_tab(const uint64_t* __restrict__ tab, uint64_t ntab, const uint64_t* __restrict__ sites,
+                             uint64_t nall, const uint64_t* __restrict__ off64, uint64_t nfr,
+                             uint32_t* __restrict__ off32, uint32_t* __restrict__ bad) {
+  const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < ntab && i && tab[i] <= tab[i - 1]) bad[0] = 1;
+  if (i <= ntab) {
+    const uint64_t o = off64[i];
+    off32[i] = (uint32_t)min(o, nfr);
+    if (o > nfr || (i == 0 && o != 0) || (i == ntab && o != nfr) || (i && o < off64[i - 1])) bad[2] = 1;
+  }
+  if (i < nall) {
+    const uint64_t j = sgd::lb64(tab, ntab, sites[i]);
+    if (j >= ntab || tab[j] != sites[i]) bad[1] = 1;
+  }
+}
+__global__ void k_ct_dev_frames(const int64_t* __restrict__ line64, const uint32_t* __restrict__ file,
+                                const uint32_t* __restrict__ func, uint64_t nfr, uint32_t nfiles, uint32_t nfuncs,
+                                uint32_t* __restrict__ line32, uint32_t* __restrict__ bad) {
+  const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= nfr) return;
+  const int64_t v = line64[i];
+  line32[i] = (uint32_t)v;
+  if (v <= 0 || v > 0xFFFFFFFFll || file[i] >= nfiles || func[i] >= nfuncs) bad[2] = 1;
+}
+
 // ---- the report -------------------------------------------------------------------
 struct LinesArgs {
   const uint32_t* cov;
@@ -401,20 +430,11 @@ int sg_cover_table_create(sg_ctx* ctx, const uint64_t* sym_start, const uint64_t
   }
   *out = nullptr;
   const uint64_t lim = 0xFFFFFFFFull;
-  if (nsym >= lim || nall >= lim || ntab >= lim || nfiles >= lim || nfuncs >= lim) {
+  if (ntab >= lim || nfiles >= lim || nfuncs >= lim) {
     set_error("%s: too many symbols, call sites, PCs, files or funcs for one table", fn);
     return SG_EINVAL;
   }
-  for (size_t s = 1; s < nsym; s++)
-    if (sym_start[s] < sym_start[s - 1] || sym_end[s] < sym_end[s - 1]) {
-      set_error("%s: symbols must be sorted by start with non-decreasing ends", fn);
-      return SG_EINVAL;
-    }
-  for (size_t j = 1; j < nall; j++)
-    if (all_pcs[j] <= all_pcs[j - 1]) {
-      set_error("%s: call-site PCs must be sorted and unique", fn);
-      return SG_EINVAL;
-    }
+  if (int rc0 = table_syms_ok(fn, sym_start, sym_end, nsym, all_pcs, nall)) return rc0;
   for (size_t j = 1; j < ntab; j++)
     if (tab_pcs[j] <= tab_pcs[j - 1]) {
       set_error("%s: table PCs must be sorted and unique", fn);
@@ -458,6 +478,44 @@ int sg_cover_table_create(sg_ctx* ctx, const uint64_t* sym_start, const uint64_t
   std::lock_guard<std::mutex> g(ctx->mu);
   int rc = ensure_device(ctx);
   if (rc) return rc;
+  const TableSrc src{tab_pcs, frame_off, frame_file, frame_line, frame_func, nullptr, k_and ^ k_or};
+  return table_build(ctx, fn, sym_start, sym_end, nsym, all_pcs, nall, ntab, ntab ? tab_pcs[0] : 0,
+                     ntab ? tab_pcs[ntab - 1] : 0, nfr, nfiles, nfuncs, src, out);
+}
+
+}  // extern "C"
+
+namespace sg {
+
+int table_syms_ok(const char* fn, const uint64_t* sym_start, const uint64_t* sym_end, size_t nsym, const uint64_t* all_pcs,
+                  size_t nall) {
+  if (nsym >= 0xFFFFFFFFull || nall >= 0xFFFFFFFFull) {
+    set_error("%s: too many symbols, call sites, PCs, files or funcs for one table", fn);
+    return SG_EINVAL;
+  }
+  for (size_t s = 1; s < nsym; s++)
+    if (sym_start[s] < sym_start[s - 1] || sym_end[s] < sym_end[s - 1]) {
+      set_error("%s: symbols must be sorted by start with non-decreasing ends", fn);
+      return SG_EINVAL;
+    }
+  for (size_t j = 1; j < nall; j++)
+    if (all_pcs[j] <= all_pcs[j - 1]) {
+      set_error("%s: call-site PCs must be sorted and unique", fn);
+      return SG_EINVAL;
+    }
+  return SG_OK;
+}
+
+// The table from checked arguments (ctx lock held, the device ensured).  With src.dev the table PCs and the frame
+// arrays are device memory and are checked there: SG_EINVAL after the one wait, no table.
+int table_build(sg_ctx* ctx, const char* fn, const uint64_t* sym_start, const uint64_t* sym_end, size_t nsym,
+                const uint64_t* all_pcs, size_t nall, size_t ntab, uint64_t tab_lo, uint64_t tab_hi, uint64_t nfr,
+                uint32_t nfiles, uint32_t nfuncs, const TableSrc& src, sg_cover_table** out) {
+  const CoverTableDev* dev = src.dev;
+  const uint64_t* tab_pcs = src.tab_pcs;
+  const uint64_t* frame_off = src.frame_off;
+  const uint32_t *frame_file = src.frame_file, *frame_line = src.frame_line, *frame_func = src.frame_func;
+  int rc = SG_OK;
   sg_cover_table* t = new sg_cover_table();
   t->ctx = ctx;
   t->has_rep = nsym && nall;
@@ -471,7 +529,7 @@ int sg_cover_table_create(sg_ctx* ctx, const uint64_t* sym_start, const uint64_t
   WsPlan bp;
   RepTablesOff to{};
   if (t->has_rep) report_tables_plan(bp, sym_start, sym_end, nsym, all_pcs, nall, report_chunkable(nall), t->rep, to);
-  if (ntab) radix_index_plan(ntab, tab_pcs[0], tab_pcs[ntab - 1], t->itab);
+  if (ntab) radix_index_plan(ntab, tab_lo, tab_hi, t->itab);
   const size_t o_tab = bp.add(ntab * 8), o_it = bp.add(ntab ? ((uint64_t)t->itab.nb + 1) * 4 : 4),
                o_row = bp.add(nall * 4), o_fo = bp.add(((uint64_t)ntab + 1) * 4), o_sl = bp.add(nfr * 4),
                o_fu = bp.add(nfr * 4), o_fi = bp.add(nfr * 4), o_ln = bp.add(nfr * 4),  // (nslots <= nfr)
@@ -492,8 +550,9 @@ int sg_cover_table_create(sg_ctx* ctx, const uint64_t* sym_start, const uint64_t
   t->frame_file = (uint32_t*)(b + o_fi);
   t->slot_line = (uint32_t*)(b + o_ln);
   t->file_slot_off = (uint32_t*)(b + o_fso);
-  std::vector<uint32_t> fo32(ntab + 1);  // (< 2^32 - 1 frames)
-  for (size_t j = 0; j <= ntab; j++) fo32[j] = (uint32_t)frame_off[j];
+  std::vector<uint32_t> fo32(dev ? 0 : ntab + 1);  // (< 2^32 - 1 frames)
+  for (size_t j = 0; j < fo32.size(); j++) fo32[j] = (uint32_t)frame_off[j];
+  uint32_t bad[4] = {0, 0, 0, 0};
   auto build = [&]() -> int {
     ScopedTimer tm(ctx, "cover_table_build");
     int rc = SG_OK;
@@ -503,10 +562,26 @@ int sg_cover_table_create(sg_ctx* ctx, const uint64_t* sym_start, const uint64_t
       if ((rc = upload(ctx, t->rep.pcs, all_pcs, nall * 8))) return rc;
       if ((rc = report_tables_build(ctx, t->rep, true))) return rc;
     }
-    if ((rc = upload(ctx, t->tab, tab_pcs, ntab * 8))) return rc;
-    if ((rc = upload(ctx, t->frame_off, fo32.data(), (ntab + 1) * 4))) return rc;
-    if ((rc = upload(ctx, t->frame_func, frame_func, nfr * 4))) return rc;
-    if ((rc = upload(ctx, t->frame_file, frame_file, nfr * 4))) return rc;
+    uint32_t* d_bad = nullptr;
+    if (dev) {  // (the sources lie in the workspace behind dev->ws_base, which cover_table_build_ws has made room for)
+      d_bad = (uint32_t*)t->site_row;  // (free until k_ct_site_row, or unused without call sites: a word per flag)
+      if (!t->has_rep) d_bad = t->file_slot_off;  // (written last)
+      SG_HIP(hipMemsetAsync(d_bad, 0, 16, ctx->stream));
+      if (ntab) SG_HIP(hipMemcpyAsync(t->tab, dev->tab, ntab * 8, hipMemcpyDeviceToDevice, ctx->stream));
+      if (nfr) {
+        SG_HIP(hipMemcpyAsync(t->frame_func, dev->frame_func, nfr * 4, hipMemcpyDeviceToDevice, ctx->stream));
+        SG_HIP(hipMemcpyAsync(t->frame_file, dev->frame_file, nfr * 4, hipMemcpyDeviceToDevice, ctx->stream));
+      }
+      hipLaunchKernelGGL(k_ct_dev_tab, dim3(div_up(std::max<uint64_t>(ntab + 1, nall), 256)), dim3(256), 0, ctx->stream,
+                         (const uint64_t*)t->tab, (uint64_t)ntab, (const uint64_t*)(t->has_rep ? t->rep.pcs : nullptr),
+                         (uint64_t)(t->has_rep ? nall : 0), dev->frame_off, nfr, t->frame_off, d_bad);
+      SG_HIP(hipMemcpyAsync(bad, d_bad, 16, hipMemcpyDeviceToHost, ctx->stream));  // (k_ct_dev_frames' flag: below)
+    } else {
+      if ((rc = upload(ctx, t->tab, tab_pcs, ntab * 8))) return rc;
+      if ((rc = upload(ctx, t->frame_off, fo32.data(), (ntab + 1) * 4))) return rc;
+      if ((rc = upload(ctx, t->frame_func, frame_func, nfr * 4))) return rc;
+      if ((rc = upload(ctx, t->frame_file, frame_file, nfr * 4))) return rc;
+    }
     if (ntab && (rc = radix_index_build(ctx, t->tab, ntab, t->itab))) return rc;
     if (t->has_rep)
       hipLaunchKernelGGL(k_ct_site_row, dim3(div_up(nall, 256)), dim3(256), 0, ctx->stream, t->rep.pcs, (uint64_t)nall,
@@ -516,17 +591,26 @@ int sg_cover_table_create(sg_ctx* ctx, const uint64_t* sym_start, const uint64_t
       // the slot table: sort the frames' (file << 32 | line) keys, keep the
       // distinct ones, rank every frame and every file's first key among them
       WsPlan p;
+      if (dev && dev->ws_base) p.add(dev->ws_base);  // (the sources, kept)
       const size_t o_ka = p.add(nfr * 8), o_kb = p.add(nfr * 8), o_li = p.add(nfr * 4), o_fl = p.add(nfr * 4),
-                   o_ps = p.add((nfr + 1) * 8), o_dk = p.add(nfr * 8);
+                   o_ps = p.add((nfr + 1) * 8), o_dk = p.add(nfr * 8), o_bad = p.add(16);
       if ((rc = ws_reserve(ctx, p.total + std::max(radix_sort_ws(nfr), scan_ws_bytes(nfr))))) return rc;
       uint64_t *ka = (uint64_t*)ws_at(ctx, o_ka), *kb = (uint64_t*)ws_at(ctx, o_kb), *pos = (uint64_t*)ws_at(ctx, o_ps),
                *dk = (uint64_t*)ws_at(ctx, o_dk), *sorted = nullptr;
       uint32_t *li = (uint32_t*)ws_at(ctx, o_li), *fl = (uint32_t*)ws_at(ctx, o_fl);
-      if ((rc = upload(ctx, li, frame_line, nfr * 4))) return rc;
       const dim3 fgrid(div_up(nfr, 256));
+      uint32_t* d_bad2 = (uint32_t*)ws_at(ctx, o_bad);
+      if (dev) {
+        SG_HIP(hipMemsetAsync(d_bad2, 0, 16, ctx->stream));
+        hipLaunchKernelGGL(k_ct_dev_frames, fgrid, dim3(256), 0, ctx->stream, dev->frame_line, (const uint32_t*)t->frame_file,
+                           (const uint32_t*)t->frame_func, nfr, nfiles, nfuncs, li, d_bad2);
+        SG_HIP(hipMemcpyAsync(&bad[3], d_bad2 + 2, 4, hipMemcpyDeviceToHost, ctx->stream));
+      } else if ((rc = upload(ctx, li, frame_line, nfr * 4))) {
+        return rc;
+      }
       hipLaunchKernelGGL(k_ct_keys, fgrid, dim3(256), 0, ctx->stream, t->frame_file, li, nfr, ka);
-      if (k_and != k_or) {  // (else every key equal: radix_sort_u64 reads vary == 0 as "find them")
-        if ((rc = radix_sort_u64(ctx, ka, kb, nfr, p.total, &sorted, k_and ^ k_or))) return rc;
+      if (src.vary) {  // (else every key equal: radix_sort_u64 reads vary == 0 as "find them")
+        if ((rc = radix_sort_u64(ctx, ka, kb, nfr, p.total, &sorted, src.vary))) return rc;
       } else {
         sorted = ka;
       }
@@ -544,6 +628,12 @@ int sg_cover_table_create(sg_ctx* ctx, const uint64_t* sym_start, const uint64_t
     SG_HIP(hipGetLastError());
     SG_HIP(hipStreamSynchronize(ctx->stream));  // (the host arrays are the caller's again)
     t->nslots = nslots;
+    if (bad[0] || bad[1] || bad[2] || bad[3]) {
+      set_error("%s: %s", fn, bad[0] ? "the records' PCs must be sorted and unique"
+                              : bad[1] ? "a call site has no record"
+                                       : "a frame has a line of 0 or of 2^32 or more, or an id or offset out of range");
+      return SG_EINVAL;
+    }
     return SG_OK;
   };
   rc = build();
@@ -555,6 +645,14 @@ int sg_cover_table_create(sg_ctx* ctx, const uint64_t* sym_start, const uint64_t
   *out = t;
   return SG_OK;
 }
+
+size_t cover_table_build_ws(uint64_t nfr) {
+  return 6 * align256(nfr * 8 + 8) + 256 + std::max(radix_sort_ws(nfr), scan_ws_bytes(nfr));
+}
+
+}  // namespace sg
+
+extern "C" {
 
 void sg_cover_table_destroy(sg_cover_table* t) {
   if (!t) return;
