@@ -1773,6 +1773,111 @@ int sg_cover_table_from_text(sg_ctx* ctx, const uint8_t* nm_text, size_t nm_byte
 			     uint32_t* file_len, uint64_t* func_pos, uint32_t* func_len, size_t names_cap, uint64_t* info,
 			     sg_cover_table** out);
 
+/* ---- pkg/report over a batch of console logs ---------------------------
+ * report.ContainsCrash (pkg/report/report.go:369-387), report.Parse up to
+ * extractDescription (:393-465) and report.ExtractConsoleOutput (:492-513)
+ * walk a log line by line and run, for every line, the header searches of
+ * matchOops (:515-531) and two regular expressions (:348-349).  Here each is
+ * one call over a batch of logs -- a crash store's log files -- as a CSR:
+ * `bytes`, off[nlogs + 1].  Positions are uint64 and relative to their log's
+ * start unless said otherwise.
+ *
+ * Lines, pinned (the loop of :370-376, not bufio.Scanner): a log is split at
+ * '\n'; the bytes after the last '\n' are a line only if there are any; empty
+ * lines are lines; '\r' stays part of the line; a line has no length limit;
+ * nothing matches across the end of a log into the next one.
+ *
+ * The oops table (:29-345) is fixed in the library, SG_CRASH_OOPSES headers in
+ * the reference's order: 0 "BUG:", 1 "WARNING:", 2 "INFO:", 3 "Unable to handle
+ * kernel paging request", 4 "general protection fault:", 5 "Kernel panic",
+ * 6 "kernel BUG", 7 "Kernel BUG", 8 "BUG kmalloc-", 9 "divide error:",
+ * 10 "invalid opcode:", 11 "unreferenced object", 12 "UBSAN:".  A line matches
+ * oops i when it contains header i -- `match` is the leftmost occurrence's
+ * offset in the line -- and no suppression of oops i matches anywhere in the
+ * line: "Boot_DEBUG:" for 0; "WARNING: /etc/ssh/moduli does not exist, using
+ * fixed modulus" for 1; "INFO: lockdep is turned off", "INFO: Stall ended
+ * before state dump start", "_INFO::" and `INFO: NMI handler .* took too long
+ * to run` for 2, the last holding exactly when some " took too long to run"
+ * starts at or behind the end of the leftmost "INFO: NMI handler ".  A
+ * suppression removes only its own oops.
+ *
+ * A console line is one where `^(?:<[0-9]+>)?\[ *[0-9]+\.[0-9]+\] ` matches at
+ * the start and which holds no match of ` \? +[a-zA-Z0-9_.]+\+0x[0-9a-f]+/
+ * [0-9a-f]+` or holds "<EOI>".  Its body runs from the end of that prefix to
+ * the line's end, less one trailing '\r'.
+ *
+ * Geometry the tests are cut to: the kernels read the batch in tiles of
+ * SG_CRASH_TILE bytes, each with the SG_CRASH_MAX_LITERAL - 1 bytes behind it;
+ * SG_CRASH_MAX_LITERAL is the longest literal (the sshd sentence).  stats
+ * (nullable, SG_CRASH_NSTATS words): {lines, console lines (sg_crash_parse),
+ * records (sg_crash_scan)} of the call, 0 where the call does not count it. */
+#define SG_CRASH_OOPSES 13
+#define SG_CRASH_TILE 4096
+#define SG_CRASH_MAX_LITERAL 60
+#define SG_CRASH_NSTATS 3
+
+/* The header search.  One record per (line, matching oops), ordered by (log,
+ * line, table order): rec_log, the line's start and end (the '\n' position or
+ * the log's length), rec_oops and rec_match.  contains[l] = 1 where log l has
+ * a record: ContainsCrash without ignores.  *nrec is always the number of
+ * records; the five arrays are written only when it is <= cap.  The batch's
+ * bytes always suffice as cap.  The caller's `ignores` depend on the line
+ * alone: it runs them over the few lines that have records and hands the
+ * ignored lines to sg_crash_parse.  SG_EINVAL, before the context is touched:
+ * a NULL ctx or nrec; contains NULL with nlogs > 0; a record array NULL with
+ * cap > 0; what sg_prog_hashes rejects of the CSR; 2^32 bytes or more.
+ * SG_ENODEV without a device.  Two waits (the line count, the record count)
+ * and a third for the records. */
+int sg_crash_scan(sg_ctx* ctx, const uint8_t* bytes, const uint64_t* off, size_t nlogs, uint8_t* contains,
+		  uint32_t* rec_log, uint64_t* rec_start, uint64_t* rec_end, uint32_t* rec_oops, uint64_t* rec_match,
+		  size_t cap, size_t* nrec, uint64_t* stats);
+/* Device form: every pointer is device memory, stream-ordered; *d_nrec is the
+ * count.  One wait, for the line count, which sizes the workspace.  The
+ * offsets follow sg_prog_hashes_dev's rule (clamped to nbytes; garbage gives
+ * garbage, never a read outside [d_bytes, d_bytes + nbytes)), and the batch
+ * ends at min(d_off[nlogs], nbytes). */
+int sg_crash_scan_dev(sg_ctx* ctx, const uint8_t* d_bytes, const uint64_t* d_off, uint64_t nlogs, uint64_t nbytes,
+		      uint8_t* d_contains, uint32_t* d_rec_log, uint64_t* d_rec_start, uint64_t* d_rec_end,
+		      uint32_t* d_rec_oops, uint64_t* d_rec_match, uint64_t cap, uint64_t* d_nrec, uint64_t* d_stats);
+
+/* Everything of Parse before extractDescription.  ign_off[nlogs + 1], ign_pos
+ * (NULL ign_off: none): the starts of the lines the caller's ignores match,
+ * ascending per log; a record whose line is listed does not exist.  Per log:
+ * oops (-1: none; then the other four are 0 and the log has no text), start =
+ * the start of the first line with a record, end = the end of the last such
+ * line, desc_pos / desc_len = output[pos + match : next] of the first line for
+ * its first oops in table order, which is also extractDescription's fallback
+ * (:554-564).  text_off[nlogs + 1] / text: the report text of :417-459.  With
+ * L0 the first line with a record: nothing when no console line stands at or
+ * after L0; else the bodies, each followed by '\n', of the last five console
+ * lines before L0, then of the console lines from L0 on that do not contain
+ * "Disabling lock debugging due to kernel taint", all of it up to but
+ * excluding the cut: the first console line at or after L0 whose rank among
+ * those is above 40, which contains "Kernel panic - not syncing" and not the
+ * taint sentence.  *ntext is always the text's bytes; text is written only
+ * when it is <= cap.  The batch's bytes always suffice as cap.  SG_EINVAL,
+ * before the context is touched: a NULL ctx, text_off or ntext; a per-log
+ * array NULL with nlogs > 0; text NULL with cap > 0; what sg_crash_scan
+ * rejects of the CSR; ignore offsets that are no CSR's, or places that do not
+ * ascend or lie outside their log.  SG_ENODEV without a device.  Three waits. */
+int sg_crash_parse(sg_ctx* ctx, const uint8_t* bytes, const uint64_t* off, size_t nlogs, const uint64_t* ign_off,
+		   const uint64_t* ign_pos, int32_t* oops, uint64_t* start, uint64_t* end, uint64_t* desc_pos,
+		   uint64_t* desc_len, uint64_t* text_off, uint8_t* text, size_t cap, size_t* ntext, uint64_t* stats);
+/* Device form, as sg_crash_scan_dev's: d_text_off[nlogs] is the total and
+ * d_text is written only when it is <= cap (compared on the device); the
+ * ignore list's nign places are device memory too, its offsets clamped. */
+int sg_crash_parse_dev(sg_ctx* ctx, const uint8_t* d_bytes, const uint64_t* d_off, uint64_t nlogs, uint64_t nbytes,
+		       const uint64_t* d_ign_off, const uint64_t* d_ign_pos, uint64_t nign, int32_t* d_oops,
+		       uint64_t* d_start, uint64_t* d_end, uint64_t* d_desc_pos, uint64_t* d_desc_len,
+		       uint64_t* d_text_off, uint8_t* d_text, uint64_t cap, uint64_t* d_stats);
+
+/* ExtractConsoleOutput: every console line's body and a '\n', per log.
+ * Counts, cap and SG_EINVAL as sg_crash_parse's. */
+int sg_console_output(sg_ctx* ctx, const uint8_t* bytes, const uint64_t* off, size_t nlogs, uint64_t* out_off,
+		      uint8_t* out, size_t cap, size_t* nout, uint64_t* stats);
+int sg_console_output_dev(sg_ctx* ctx, const uint8_t* d_bytes, const uint64_t* d_off, uint64_t nlogs, uint64_t nbytes,
+			  uint64_t* d_out_off, uint8_t* d_out, uint64_t cap, uint64_t* d_stats);
+
 #ifdef __cplusplus
 }
 #endif

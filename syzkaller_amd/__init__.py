@@ -12,7 +12,10 @@ and `syzkaller_amd.corpus` the corpus' identities (pkg/hash, the identity sets
 and hubSync's Add / Del), and `syzkaller_amd.hub` the hub's corpus (prog.CallSet,
 the name dictionary, addInputs, pendingInputs and purgeCorpus), and
 `syzkaller_amd.db` the corpus database (raw DEFLATE of every value both ways,
-db.Open and loadDB from the file's bytes, Save, Delete, Flush and compact).
+db.Open and loadDB from the file's bytes, Save, Delete, Flush and compact), and
+`syzkaller_amd.report` pkg/report over batches of console logs (ContainsCrash,
+Parse and ExtractConsoleOutput; imported by name, its functions carry the
+reference's names).
 """
 from ._lib import LIB_PATH, SyzSigError, lib  # noqa: F401  (fails loudly if the library is missing)
 

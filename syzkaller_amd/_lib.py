@@ -234,6 +234,17 @@ SIGNATURES = {
     "sg_hints_from_kcov": (c_int, [c_void_p, P64, P64, c_size_t, P64, P64, POINTER(c_int32), P64, P64, c_size_t]),
     "sg_hints_from_kcov_dev": (c_int, [c_void_p, c_void_p, c_void_p, c_uint64, c_uint64, c_void_p, c_void_p, c_uint64,
                                        c_void_p, c_void_p, c_void_p, c_uint64]),
+    "sg_crash_scan": (c_int, [c_void_p, P8, P64, c_size_t, P8, P32, P64, P64, P32, P64, c_size_t, PSZ, P64]),
+    "sg_crash_scan_dev": (c_int, [c_void_p, c_void_p, c_void_p, c_uint64, c_uint64, c_void_p, c_void_p, c_void_p, c_void_p,
+                                  c_void_p, c_void_p, c_uint64, c_void_p, c_void_p]),
+    "sg_crash_parse": (c_int, [c_void_p, P8, P64, c_size_t, P64, P64, PI32, P64, P64, P64, P64, P64, P8, c_size_t, PSZ,
+                               P64]),
+    "sg_crash_parse_dev": (c_int, [c_void_p, c_void_p, c_void_p, c_uint64, c_uint64, c_void_p, c_void_p, c_uint64,
+                                   c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_uint64,
+                                   c_void_p]),
+    "sg_console_output": (c_int, [c_void_p, P8, P64, c_size_t, P64, P8, c_size_t, PSZ, P64]),
+    "sg_console_output_dev": (c_int, [c_void_p, c_void_p, c_void_p, c_uint64, c_uint64, c_void_p, c_void_p, c_uint64,
+                                      c_void_p]),
 }
 
 
