@@ -84,7 +84,8 @@ int sg_ctx_kernel_time(sg_ctx* ctx, const char* name, double* ms, uint64_t* laun
  * "flag_skip_used" (bucket launches run in two phases), "flag_skip_full_blocks"
  * (fully queued 4096-record blocks the last of them found after its first phase),
  * "flag_skip_all_flagged" (those that found every block so and ran their second
- * phase without the owner map);
+ * phase without the owner map), "flag_skip_u16" (those whose pass 2 over the
+ * slices after the first window ran late, in 2-byte entries);
  * "hints_candidates" (the last sg_hints_replacers* call's (slot, pair)
  * matches, before deduplication); "exec_comps_general" (the calls the last
  * sg_exec_comps* call sent down its general path), "exec_comps_fast_cap"
@@ -148,7 +149,7 @@ int sg_ctx_counter(sg_ctx* ctx, const char* name, uint64_t* out);
  * forces one, for a test or a measurement, and no call reads the environment
  * (sg_ctx_create seeds "debug_part", "bucket_blocks", "prefix_pairs" and
  * "flag_skip" from SG_DEBUG_PART / SG_BUCKET_BLOCKS / SG_PREFIX_PAIRS /
- * SG_FLAG_SKIP, for the GPU scripts).
+ * SG_FLAG_SKIP, and "flag_skip_u16" from SG_FLAG_SKIP_U16, for the GPU scripts).
  * Keys (-1 = the regime's choice where it applies):
  *   "max_launch_records"   records per partitioned launch (0: 2^24)
  *   "owner_key_space"      Minimize's first-owner key space (0: 2^32 - 1; set
@@ -178,6 +179,11 @@ int sg_ctx_counter(sg_ctx* ctx, const char* name, uint64_t* out);
  *                          fully queued (-1 auto: after a partitioned slice that
  *                          queued most of its records; 1 always; 0 never)
  *   "flag_skip_split"      k, 1..8: the first launch takes 1 / 2^k of the bucket list
+ *   "flag_skip_u16"        a split launch of the flags path scatters pass 2 around its
+ *                          first launch: the slices of the first window before it, the
+ *                          others after the flag summary, in 2-byte entries when every
+ *                          record is flagged (-1 whenever the launch splits; 0 never:
+ *                          pass 2 whole, before the bucket stage; 1 with the split forced)
  * Unknown keys and out-of-range values return SG_EINVAL. */
 int sg_ctx_set_option(sg_ctx* ctx, const char* key, int64_t value);
 int sg_ctx_get_option(sg_ctx* ctx, const char* key, int64_t* out);

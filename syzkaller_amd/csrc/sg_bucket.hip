@@ -34,7 +34,10 @@ struct BucketArgs {
   const uint32_t* nlist;   // device: their number
   // the list window of a split launch (flag_skip): with A = *nlist >> win_shift,
   // win 1 takes entries [0, A), win 2 [A, *nlist), 0 all of them
+  // with a late pass 2 (P2Late, sg_part.h) and B = bounds[kLateList] >= A: win 3 takes [A, B), the 4-byte rest of
+  // the boundary slice, win 4 [B, *nlist), the slices scattered after the summary
   uint32_t win, win_shift;
+  const uint32_t* bounds;  // the launch's kTK words (win 3, 4)
   const uint32_t* fsum;    // nullable: bit per kFsRecs records of the launch, set: every flag of the block is set already
   // the second phase of a split launch: all-flagged iff *fs_cnt (the summary's full blocks) == fs_nblk (the
   // launch's blocks); then k_bucket_sets takes window 2 and counts itself in *fs_all, else k_bucket<.., kSkip>
@@ -228,6 +231,34 @@ __device__ __forceinline__ void bucket_pre_load(const BucketArgs& a, uint32_t b,
   }
 }
 
+// the list window [l0, l0 + nl) of the launch (BucketArgs::win)
+__device__ __forceinline__ void list_window(const BucketArgs& a, uint32_t& l0, uint32_t& nl) {
+  nl = *a.nlist;
+  l0 = 0;
+  if (!a.win) return;
+  const uint32_t na = nl >> a.win_shift;
+  if (a.win <= 2) {
+    l0 = a.win == 2 ? na : 0;
+    nl = a.win == 2 ? nl - na : na;
+  } else {
+    const uint32_t nb = a.bounds[kLateList];
+    l0 = a.win == 3 ? na : nb;
+    nl = a.win == 3 ? nb - na : nl - nb;
+  }
+}
+
+// The bounds of a late pass 2 (sg_part.h): D = the slice after the last bucket
+// of the list's first window (0: the window is empty); the list position of
+// slice D's first bucket (lpos: the non-empty flags' scan, lpos[kNumBuckets]
+// = the list's length) and the first chunk of slice D.
+__global__ void k_late_bounds(const uint32_t* __restrict__ lpos, const uint32_t* __restrict__ blist_b,
+                              const uint32_t* __restrict__ cfirst, uint32_t shift, uint32_t* __restrict__ tk) {
+  const uint32_t na = lpos[kNumBuckets] >> shift;
+  const uint32_t D = na ? (blist_b[na - 1] >> 8) + 1 : 0u;
+  tk[kLateList] = lpos[D << 8];
+  tk[kLateChunks] = cfirst[D];
+}
+
 // thread 0: bucket and descriptor of entry t of the list window [l0, l0 + nl)
 // (kNumBuckets: past the end)
 __device__ __forceinline__ uint32_t list_bucket(const BucketArgs& a, uint32_t t, uint32_t l0, uint32_t nl, uint4* q) {
@@ -354,12 +385,8 @@ __global__ __launch_bounds__(kBThreads) __attribute__((amdgpu_waves_per_eu(kBWav
   // list entries: blockIdx and gridDim + blockIdx first, then tickets from
   // 2 x gridDim.  Thread 0 takes each ticket a bucket before it resolves it and
   // resolves it a bucket before it is needed, so neither wait is exposed.
-  uint32_t nl = *a.nlist, l0 = 0;
-  if (a.win) {  // a split launch's window of the list
-    const uint32_t na = nl >> a.win_shift;
-    l0 = a.win == 2 ? na : 0;
-    nl = a.win == 2 ? nl - na : na;
-  }
+  uint32_t nl, l0;
+  list_window(a, l0, nl);  // a split launch's window of the list
   // (tickets are taken at every install, also past the list's end: waiting
   // for the list entry before taking the next would be another round trip)
   uint32_t pend_t = 0;  // thread 0: ticket taken, not yet resolved
@@ -768,25 +795,43 @@ __global__ __launch_bounds__(kBThreads) __attribute__((amdgpu_waves_per_eu(kBWav
 // write-back needs no slice in LDS but three times the LDS atomics: measured
 // slower, 1.58 against 1.37 ms per C2 bucket stage in alternated runs of one
 // job)
+// k16: the window's entries are the 2-byte ones of a late pass 2 (sg_part.h),
+// the 16-bit signal at byte 2 * position: a 16-B load holds 8 of them, rounds
+// start 8-aligned, and nothing is shifted away.
 constexpr int kSQ = 2;                           // 16-B loads per thread and round, each contiguous over the workgroup
-constexpr uint32_t kSQuad = kBThreads * 4;       // entries of one of them
-constexpr uint32_t kSRound = kSQuad * kSQ;
 struct SetsPre {  // a bucket's first loads, held in registers
   uint32_t msw[kWPT];
   uint32_t nsw[kWPT];
 };
 
-__device__ __forceinline__ uint32_t sets_pos(uint32_t base, int j) { return base + j * kSQuad + threadIdx.x * 4; }
+// entries of a 16-B load, of one of a round's kSQ loads over the workgroup, and of a round
+template <bool k16> constexpr uint32_t kSE = k16 ? 8 : 4;
+template <bool k16> constexpr uint32_t kSQuad = kBThreads * kSE<k16>;
+template <bool k16> constexpr uint32_t kSRound = kSQuad<k16> * kSQ;
 
-// (base 4-aligned; a quad is loaded when its first entry is below hi: the
-// padded pass-2 buffer covers the rest of it, as in bucket_round_load)
+template <bool k16>
+__device__ __forceinline__ uint32_t sets_pos(uint32_t base, int j) {
+  return base + j * kSQuad<k16> + threadIdx.x * kSE<k16>;
+}
+
+// (base aligned to a load; a load is issued when its first entry is below hi:
+// the padded pass-2 buffer covers the rest of it, as in bucket_round_load)
+template <bool k16>
 __device__ __forceinline__ void sets_round_load(const BucketArgs& a, uint32_t base, uint32_t hi, v4u32 (&x)[kSQ]) {
 #pragma unroll
   for (int j = 0; j < kSQ; j++) {
     x[j] = v4u32{0, 0, 0, 0};
-    const uint32_t p = sets_pos(base, j);
-    if (p < hi) x[j] = __builtin_nontemporal_load(reinterpret_cast<const v4u32*>(a.in + p));
+    const uint32_t p = sets_pos<k16>(base, j);
+    if (p < hi)
+      x[j] = __builtin_nontemporal_load(
+          reinterpret_cast<const v4u32*>(reinterpret_cast<const char*>(a.in) + (uint64_t)p * (k16 ? 2 : 4)));
   }
+}
+
+// entry u of a load: its slice word and bit
+template <bool k16>
+__device__ __forceinline__ uint32_t sets_sig(const v4u32& x, int u) {
+  return k16 ? (x[u >> 1] >> (16 * (u & 1))) & 0xFFFFu : x[u] >> 16;
 }
 
 __device__ __forceinline__ void sets_pre_load(const BucketArgs& a, uint32_t b, SetsPre& P) {
@@ -802,19 +847,17 @@ __device__ __forceinline__ void sets_pre_load(const BucketArgs& a, uint32_t b, S
   }
 }
 
+template <bool k16>
 __global__ __launch_bounds__(kBThreads) __attribute__((amdgpu_waves_per_eu(8))) void k_bucket_sets(BucketArgs a) {
   if (*a.fs_cnt != a.fs_nblk) return;  // some record is not flagged yet: k_bucket<.., kSkip> has this window
   __shared__ alignas(16) uint32_t mslice[kBucketWords];
   __shared__ alignas(16) uint32_t nbits[kBucketWords];
   __shared__ uint32_t sh_b[2];
   __shared__ uint4 sh_q[2];
+  constexpr uint32_t kE = kSE<k16>;
   const int tid = threadIdx.x;
-  uint32_t nl = *a.nlist, l0 = 0;
-  if (a.win) {
-    const uint32_t na = nl >> a.win_shift;
-    l0 = a.win == 2 ? na : 0;
-    nl = a.win == 2 ? nl - na : na;
-  }
+  uint32_t nl, l0;
+  list_window(a, l0, nl);
   // list entries and tickets as in k_bucket
   uint32_t pend_t = 0;
   if (tid == 0) {
@@ -824,7 +867,7 @@ __global__ __launch_bounds__(kBThreads) __attribute__((amdgpu_waves_per_eu(8))) 
     sh_b[1] = list_bucket(a, gridDim.x + blockIdx.x, l0, nl, &q1);
     sh_q[1] = q1;
     pend_t = take_ticket(a.ticket);
-    if (blockIdx.x == 0) atomicAdd(a.fs_all, 1u);  // "flag_skip_all_flagged"
+    if (blockIdx.x == 0 && a.fs_all) atomicAdd(a.fs_all, 1u);  // "flag_skip_all_flagged" (once per split launch)
   }
   __syncthreads();
   uint32_t b = uni(sh_b[0]), b1 = uni(sh_b[1]);
@@ -832,7 +875,7 @@ __global__ __launch_bounds__(kBThreads) __attribute__((amdgpu_waves_per_eu(8))) 
   if (b >= kNumBuckets) return;
   v4u32 x[kSQ], y[kSQ];
   SetsPre P;
-  sets_round_load(a, q.x & ~3u, q.y, x);
+  sets_round_load<k16>(a, q.x & ~(kE - 1), q.y, x);
   sets_pre_load(a, b, P);
   // the bucket's words kWPT tid .. + kWPT - 1: mwords | owords into the slice (read back at the bucket's end),
   // newSignal's held in registers
@@ -857,24 +900,26 @@ __global__ __launch_bounds__(kBThreads) __attribute__((amdgpu_waves_per_eu(8))) 
       pend_b = list_bucket(a, 2 * gridDim.x + pend_t, l0, nl, &pend_q);
       pend_t = take_ticket(a.ticket);
     }
-    for (uint32_t base = lo & ~3u;;) {
+    for (uint32_t base = lo & ~(kE - 1);;) {
       // the next round in flight: this bucket's, or the next bucket's first with its words
-      const uint32_t next = base + kSRound;
+      const uint32_t next = base + kSRound<k16>;
       const bool last = next >= hi;
-      if (!last || b1 < kNumBuckets) sets_round_load(a, last ? q1.x & ~3u : next, last ? q1.y : hi, y);
+      if (!last || b1 < kNumBuckets) sets_round_load<k16>(a, last ? q1.x & ~(kE - 1) : next, last ? q1.y : hi, y);
       if (last && b1 < kNumBuckets) sets_pre_load(a, b1, P);
 #pragma unroll
-      for (int j = 0; j < kSQ; j++) {  // a quad at a time: its LDS reads issued before the first use
-        uint32_t mw[4];
+      for (int j = 0; j < kSQ; j++)  // four entries at a time: their LDS reads issued before the first use
 #pragma unroll
-        for (int u = 0; u < 4; u++) mw[u] = mslice[x[j][u] >> 21];
+        for (int h = 0; h < (int)kE; h += 4) {
+          uint32_t mw[4];
 #pragma unroll
-        for (int u = 0; u < 4; u++) {
-          const uint32_t i = sets_pos(base, j) + u, v = x[j][u];
-          const uint32_t bit = 1u << ((v >> 16) & 31);
-          if (i >= lo && i < hi && !(mw[u] & bit)) atomicOr(&nbits[v >> 21], bit);
+          for (int u = 0; u < 4; u++) mw[u] = mslice[sets_sig<k16>(x[j], h + u) >> 5];
+#pragma unroll
+          for (int u = 0; u < 4; u++) {
+            const uint32_t i = sets_pos<k16>(base, j) + h + u, v = sets_sig<k16>(x[j], h + u);
+            const uint32_t bit = 1u << (v & 31);
+            if (i >= lo && i < hi && !(mw[u] & bit)) atomicOr(&nbits[v >> 5], bit);
+          }
         }
-      }
       // (after the last round too: then the next bucket's first round, if there is one)
 #pragma unroll
       for (int j = 0; j < kSQ; j++) x[j] = y[j];
@@ -1041,10 +1086,21 @@ static bool fs_split(sg_ctx* ctx) {
   return ctx->m0f_queued >= kFsQueued;
 }
 
+// The flags path's bucket stage for this launch: 0 one launch, 1 split, 2
+// split with a late pass 2 (P2Late, sg_part.h; late_ok: the caller can run
+// pass 2 in parts).  Option flag_skip_u16: -1 late whenever the launch splits,
+// 0 never, 1 late with the split forced.
+int buckets_split(sg_ctx* ctx, const BucketPlan& bp, const uint8_t* d_rec_new, bool late_ok) {
+  if (ctx->debug_part || !d_rec_new || bp.nrec > kMaxLaunchRecords) return 0;
+  const int u = late_ok ? ctx->fs_u16_opt : 0;
+  if (u > 0) return 2;
+  return fs_split(ctx) ? (u ? 2 : 1) : 0;
+}
+
 // The bucket stage: the bucket kernels over the partition's buckets (bp as
 // partition_pass1 rebased it): flags and set updates, or (emit) the candidate pairs.
 int buckets_one(sg_ctx* ctx, const BucketPlan& bp, uint32_t* mwords, uint32_t* nwords, uint8_t* d_rec_new,
-                const EmitArgs* emit, const uint32_t* owords) {
+                const EmitArgs* emit, const uint32_t* owords, int split_mode) {
   const uint64_t nrec = bp.nrec;
   const uint32_t* gcount = bp.at<uint32_t>(ctx, kCB) + bp.ng;  // device: number of pass-2 chunks
   uint4* bdesc = bp.at<uint4>(ctx, kBD);
@@ -1086,8 +1142,9 @@ int buckets_one(sg_ctx* ctx, const BucketPlan& bp, uint32_t* mwords, uint32_t* n
   // The flags path in two launches (option flag_skip): the first 1 / 2^k of
   // the bucket list with every flag stored, the record-flag summary, then the
   // rest of the list without the stores that the summary shows to rewrite a 1.
-  const bool split = !emit && !dbg && d_rec_new && nrec <= kMaxLaunchRecords && fs_split(ctx);
-  uint32_t* fsum = ba.ticket + 4;
+  if (split_mode < 0) split_mode = emit ? 0 : buckets_split(ctx, bp, d_rec_new, false);
+  const bool split = split_mode != 0, late = split_mode == 2;
+  uint32_t* fsum = ba.ticket + kTkWords;
   uint32_t* fcnt = &ctx->dev.p->fs_full_blocks;
   if (split) {
     int rc = ctx->fs_ev.create(hipEventDisableTiming);
@@ -1095,7 +1152,7 @@ int buckets_one(sg_ctx* ctx, const BucketPlan& bp, uint32_t* mwords, uint32_t* n
     if (rc) return rc;
     SG_HIP(hipMemsetAsync(fcnt, 0, 4, ctx->stream));
   }
-  SG_HIP(hipMemsetAsync(ba.ticket, 0, split ? 16 + kFsWords * 4 : 4, ctx->stream));
+  SG_HIP(hipMemsetAsync(ba.ticket, 0, split ? (kTkWords + kFsWords) * 4 : 4, ctx->stream));
   SG_HIP(hipMemsetAsync(nspill, 0, 4, ctx->stream));
   ba.blist_b = bp.at<uint32_t>(ctx, kLB);
   ba.blist_q = bp.at<uint4>(ctx, kLQ);
@@ -1105,11 +1162,28 @@ int buckets_one(sg_ctx* ctx, const BucketPlan& bp, uint32_t* mwords, uint32_t* n
     if (split) {
       ba.win = 1;
       ba.win_shift = (uint32_t)ctx->opt[kOptFlagSkipSplit];
+      ba.bounds = ba.ticket;
+    }
+    P2Late pl{1, false, ba.ticket, fcnt, (uint32_t)div_up(nrec, kFsRecs), &ctx->dev.p->fs_u16};
+    if (late) {
+      // the first window's slices scattered now, in 4-byte entries (the other chunks after the summary)
+      hipLaunchKernelGGL(k_late_bounds, dim3(1), dim3(1), 0, ctx->stream, (const uint32_t*)bp.at<uint32_t>(ctx, kBP),
+                         ba.blist_b, (const uint32_t*)bp.at<uint32_t>(ctx, kCF), ba.win_shift, ba.ticket);
+      int rc = partition_pass2_windows(ctx, bp, ba.ticket);
+      if (!rc) rc = partition_pass2_scatter(ctx, bp, &pl);
+      if (rc) return rc;
     }
     auto kb = emit  ? (emit->gcur ? k_bucket<false, 2> : k_bucket<false, 1>)
               : dbg ? k_bucket<true, 0>
                     : k_bucket<false, 0>;
     hipLaunchKernelGGL(kb, dim3(bgrid), dim3(kBThreads), 0, ctx->stream, ba);
+    if (late) {
+      // The 2-byte entries of an all-flagged launch land at byte 2 * position, over the 4-byte entries of other
+      // buckets: whatever still reads those runs first.  The first window's spilled buckets now (their flags
+      // also reach the summary), leaving an empty spill list to the second phase ...
+      hipLaunchKernelGGL(k_bucket_direct<false>, dim3(512), dim3(kDThreads), 0, ctx->stream, ba);
+      SG_HIP(hipMemsetAsync(nspill, 0, 4, ctx->stream));
+    }
     if (split) {
       hipLaunchKernelGGL(k_flag_summary, dim3(div_up(div_up(nrec, kFsRecs), 4)), dim3(256), 0, ctx->stream,
                          (const uint8_t*)d_rec_new, (uint32_t)nrec, fsum, fcnt);
@@ -1123,20 +1197,42 @@ int buckets_one(sg_ctx* ctx, const BucketPlan& bp, uint32_t* mwords, uint32_t* n
       ba.fs_cnt = fcnt;
       ba.fs_nblk = (uint32_t)div_up(nrec, kFsRecs);
       ba.fs_all = &ctx->dev.p->fs_all_flagged;
-      hipLaunchKernelGGL((k_bucket<false, 0, true>), dim3(bgrid), dim3(kBThreads), 0, ctx->stream, ba);
       BucketArgs bs = ba;
       bs.ticket = ba.ticket + 1;
-      uint32_t sgrid = persistent_grid(ctx, (const void*)k_bucket_sets, kBThreads);
+      uint32_t sgrid = persistent_grid(ctx, (const void*)k_bucket_sets<false>, kBThreads);
       if (cap_blocks > 0 && (uint64_t)cap_blocks < sgrid) sgrid = (uint32_t)cap_blocks;
-      hipLaunchKernelGGL(k_bucket_sets, dim3(sgrid), dim3(kBThreads), 0, ctx->stream, bs);
+      if (late) {
+        // ... and, all-flagged, the rest of the boundary slice, 4-byte entries of the first scatter (empty when
+        // every bucket is non-empty).  Then the second window's slices in both forms of the scatter.
+        bs.win = 3;
+        hipLaunchKernelGGL(k_bucket_sets<false>, dim3(sgrid), dim3(kBThreads), 0, ctx->stream, bs);
+        pl.win = 2;
+        int rc = partition_pass2_scatter(ctx, bp, &pl);
+        pl.u16 = true;
+        if (!rc) rc = partition_pass2_scatter(ctx, bp, &pl);
+        if (rc) return rc;
+      }
+      hipLaunchKernelGGL((k_bucket<false, 0, true>), dim3(bgrid), dim3(kBThreads), 0, ctx->stream, ba);
+      if (late) {  // all-flagged: the late slices, 2-byte entries, with a ticket of their own
+        bs.win = 4;
+        bs.ticket = ba.ticket + 2;
+        bs.fs_all = nullptr;  // (the launch is counted once, by the window-3 launch)
+        uint32_t ugrid = persistent_grid(ctx, (const void*)k_bucket_sets<true>, kBThreads);
+        if (cap_blocks > 0 && (uint64_t)cap_blocks < ugrid) ugrid = (uint32_t)cap_blocks;
+        hipLaunchKernelGGL(k_bucket_sets<true>, dim3(ugrid), dim3(kBThreads), 0, ctx->stream, bs);
+      } else {
+        hipLaunchKernelGGL(k_bucket_sets<false>, dim3(sgrid), dim3(kBThreads), 0, ctx->stream, bs);
+      }
     }
   }
   if (split) {
-    // (both words: the last launch's full blocks and the context's all-flagged launches so far)
+    // (three words: the last launch's full blocks, and the context's all-flagged and 2-byte launches so far)
     static_assert(offsetof(CtxDev, fs_all_flagged) == offsetof(CtxDev, fs_full_blocks) + 4 &&
-                      offsetof(CtxPinned, fs_all_flagged) == offsetof(CtxPinned, fs_full_blocks) + 4,
-                  "the two words travel in one copy");
-    SG_HIP(hipMemcpyAsync(&ctx->pinned.p->fs_full_blocks, fcnt, 8, hipMemcpyDeviceToHost, ctx->stream));
+                      offsetof(CtxDev, fs_u16) == offsetof(CtxDev, fs_full_blocks) + 8 &&
+                      offsetof(CtxPinned, fs_all_flagged) == offsetof(CtxPinned, fs_full_blocks) + 4 &&
+                      offsetof(CtxPinned, fs_u16) == offsetof(CtxPinned, fs_full_blocks) + 8,
+                  "the three words travel in one copy");
+    SG_HIP(hipMemcpyAsync(&ctx->pinned.p->fs_full_blocks, fcnt, 12, hipMemcpyDeviceToHost, ctx->stream));
     SG_HIP(hipEventRecord(ctx->fs_ev, ctx->stream));
     ctx->fs_pending = true;
     ctx->fs_used++;

@@ -198,9 +198,16 @@ int sg_ctx_create(int device, sg_ctx** out) {
   c->debug_part = getenv("SG_DEBUG_PART") != nullptr;
   {
     static const struct { const char* name; int opt; int64_t lo, hi; } kSeed[] = {
-        {"SG_BUCKET_BLOCKS", kOptBucketBlocks, INT64_MIN, INT64_MAX}, {"SG_FLAG_SKIP", kOptFlagSkip, -1, 1}};
+        {"SG_BUCKET_BLOCKS", kOptBucketBlocks, INT64_MIN, INT64_MAX}, {"SG_FLAG_SKIP", kOptFlagSkip, -1, 1},
+        {"SG_FLAG_SKIP_U16", -1, -1, 1}};  // (opt -1: flag_skip_u16, which is no row of sg_opts.h)
     for (const auto& s : kSeed)
-      if (const char* e = getenv(s.name)) c->opt[s.opt] = std::min(std::max<int64_t>(strtoll(e, nullptr, 10), s.lo), s.hi);
+      if (const char* e = getenv(s.name)) {
+        const int64_t v = std::min(std::max<int64_t>(strtoll(e, nullptr, 10), s.lo), s.hi);
+        if (s.opt >= 0)
+          c->opt[s.opt] = v;
+        else
+          c->fs_u16_opt = (int)v;
+      }
   }
   if (const char* e = getenv("SG_PREFIX_PAIRS")) c->opt[kOptPrefixPairs] = strtoll(e, nullptr, 10) != 0;
   c->cpu_quota = host_cpu_quota();
@@ -319,6 +326,14 @@ int sg_ctx_set_option(sg_ctx* ctx, const char* key, int64_t value) {
     ctx->debug_part = value != 0;
     return SG_OK;
   }
+  if (!strcmp(key, "flag_skip_u16")) {  // the split launch's late pass 2 (sg_ctx::fs_u16_opt)
+    if (value < -1 || value > 1) {
+      set_error("sg_ctx_set_option: flag_skip_u16 in -1..1");
+      return SG_EINVAL;
+    }
+    ctx->fs_u16_opt = (int)value;
+    return SG_OK;
+  }
   for (int i = 0; i < kOptCount; i++) {  // the range-checked ones (sg_opts.h)
     const SgOptRow& o = kSgOpts[i];
     if (strcmp(key, o.name)) continue;
@@ -348,6 +363,10 @@ int sg_ctx_get_option(sg_ctx* ctx, const char* key, int64_t* out) {
     *out = ctx->debug_part;
     return SG_OK;
   }
+  if (!strcmp(key, "flag_skip_u16")) {
+    *out = ctx->fs_u16_opt;
+    return SG_OK;
+  }
   for (int i = 0; i < kOptCount; i++)
     if (!strcmp(key, kSgOpts[i].name)) {
       *out = ctx->opt[i];
@@ -363,7 +382,7 @@ int sg_ctx_get_option(sg_ctx* ctx, const char* key, int64_t* out) {
 namespace {
 typedef uint64_t Quad[4];
 enum CtrKind { kHost, kHost4, kDev32, kDev64, kConst, kCalc };
-enum CtrCalc : uint64_t { kOwnerFloor, kM0Queued, kM0Logh, kCpuQuota, kFsFullBlocks, kFsAllFlagged, kWsBytes };
+enum CtrCalc : uint64_t { kOwnerFloor, kM0Queued, kM0Logh, kCpuQuota, kFsFullBlocks, kFsAllFlagged, kFsU16, kWsBytes };
 #define SG_DEV(field) offsetof(CtxDev, field)
 struct Counter {
   const char* name;
@@ -431,11 +450,12 @@ const Counter kCounters[] = {
 };
 
 int counter_calc(sg_ctx* ctx, uint64_t which, uint64_t* out) {
-  if ((which == kFsFullBlocks || which == kFsAllFlagged) && ctx->fs_pending) {  // (the last split launch's words may still be on their way)
+  if ((which == kFsFullBlocks || which == kFsAllFlagged || which == kFsU16) && ctx->fs_pending) {  // (the last split launch's words may still be on their way)
     SG_HIP(hipEventSynchronize(ctx->fs_ev));
     ctx->fs_pending = false;
     ctx->fs_full_blocks = ctx->pinned.p->fs_full_blocks;
     ctx->fs_all_flagged = ctx->pinned.p->fs_all_flagged;
+    ctx->fs_u16 = ctx->pinned.p->fs_u16;
   }
   switch (which) {
     case kOwnerFloor: *out = ctx->owner.p ? ctx->owner_floor : ctx->owner_key_space; break;
@@ -444,6 +464,7 @@ int counter_calc(sg_ctx* ctx, uint64_t which, uint64_t* out) {
     case kCpuQuota: *out = (uint64_t)(ctx->cpu_quota * 1000.0 + 0.5); break;
     case kFsFullBlocks: *out = ctx->fs_full_blocks; break;
     case kFsAllFlagged: *out = ctx->fs_all_flagged; break;
+    case kFsU16: *out = ctx->fs_u16; break;
     case kWsBytes: *out = ctx->ws.cap; break;
   }
   return SG_OK;
@@ -453,6 +474,8 @@ int counter_calc(sg_ctx* ctx, uint64_t which, uint64_t* out) {
 extern "C" int sg_ctx_counter(sg_ctx* ctx, const char* name, uint64_t* out) {
   if (!ctx || !name || !out) return SG_EINVAL;
   std::lock_guard<std::mutex> g(ctx->mu);
+  // split launches whose window-2 pass 2 ran in 2-byte entries: read with the two flag_skip words above
+  if (!strcmp(name, "flag_skip_u16")) return counter_calc(ctx, kFsU16, out);
   for (const Counter& c : kCounters) {
     if (strcmp(name, c.name)) continue;
     if (c.kind == kCalc) return counter_calc(ctx, c.arg, out);

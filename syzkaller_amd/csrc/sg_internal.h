@@ -92,6 +92,7 @@ struct CtxDev {
   uint32_t m0f_queued;      // queued records of the last counted partitioned slice (sg_m0filter.hip)
   uint32_t fs_full_blocks;  // full record blocks of the last split bucket launch (sg_bucket.hip)
   uint32_t fs_all_flagged;  // ... and the split launches whose second phase ran map-free (cumulative; copied with it)
+  uint32_t fs_u16;          // ... and those whose window-2 pass 2 wrote 2-byte entries (cumulative; same copy)
   uint32_t owned_big;       // "owned_big_records": zeroed by an ordered-output call, added to by each slice's launch
   uint32_t tr_wide;         // "triage_runs_wide", and the cover fold's routes after it (zeroed together)
   uint32_t tr_route[kTrRoutes];
@@ -109,6 +110,7 @@ struct CtxPinned {
   uint32_t m0f_queued;      // behind sg_ctx::m0f_ev
   uint32_t fs_full_blocks;  // behind sg_ctx::fs_ev
   uint32_t fs_all_flagged;  // likewise (one copy)
+  uint32_t fs_u16;          // likewise
 };
 }  // namespace sg
 
@@ -144,7 +146,10 @@ struct sg_ctx {
   // of the last one (counted on the device, read through pinned once fs_ev
   // has passed), with the launches so far whose second phase ran map-free
   // (every record flagged by the first; the device's running count, same copy)
-  uint64_t fs_used = 0, fs_full_blocks = 0, fs_all_flagged = 0;
+  uint64_t fs_used = 0, fs_full_blocks = 0, fs_all_flagged = 0, fs_u16 = 0;
+  // option flag_skip_u16: a split launch's pass 2 over the second window after the summary, in 2-byte entries when
+  // every record is flagged (-1 whenever the launch splits, 0 never, 1 with the split forced; sg_part_triage.hip)
+  int fs_u16_opt = -1;
   sg::Event fs_ev;
   bool fs_pending = false;
   int m0f_logh = 0;  // auto: the index in 2^m0f_logh parts per slice (raised when a slice's index overflows)

@@ -9,7 +9,7 @@
 // environment on a call; sg_ctx_create seeds the diagnostics ones (debug_part,
 // bucket_blocks, prefix_pairs, flag_skip) from SG_DEBUG_PART /
 // SG_BUCKET_BLOCKS / SG_PREFIX_PAIRS / SG_FLAG_SKIP for the GPU scripts.
-// (max_launch_records, owner_key_space and debug_part are no ranges: sg_ctx.hip)
+// (max_launch_records, owner_key_space, debug_part and flag_skip_u16 are no rows here: sg_ctx.hip)
 enum SgOpt : int {
   kOptBucketBlocks = 0, kOptPrefixPairs, kOptFoldMap, kOptMinimizeFilter, kOptMinimizeFilterRanks, kOptReportDirect,
   kOptRpcEncodeElems, kOptRpcDecodeBlocks, kOptHostSlice, kOptHostCopyThreads, kOptM0Filter, kOptM0Halves,

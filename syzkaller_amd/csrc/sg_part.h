@@ -135,7 +135,7 @@ enum Region : int {
   kCD, kDT,            // per pass-2 block: chunk descriptor, tile range
   kBD, kGB,            // buckets: descriptors {lo, hi, c0, nch}, group boundaries [bucket][group]
   kH2, kO2, kV2,       // pass 2: histogram [byte][chunk], its scan, entries
-  kSP, kTK,            // spilled buckets (count, list); four ticket words (a split launch's phases: 0, 1 and, map-free, 2) + record-flag summary
+  kSP, kTK,            // spilled buckets (count, list); four ticket words (a split launch's phases: 0, 1 and, map-free, 2, 3), the late pass 2's bounds (kLate*) + record-flag summary
   kBN, kBP,            // bucket non-empty flags, their scan ([kNumBuckets] = the list's length)
   kLB, kLQ,            // the non-empty buckets in bucket order, and their descriptors
   kSC, kKM,            // scan32's block sums; trace batches' kept-entry words
@@ -143,6 +143,41 @@ enum Region : int {
 };
 static_assert(kRegions <= sizeof(WsPlan::off) / sizeof(size_t), "the plan's regions fit WsPlan");
 
+// A split launch whose pass 2 runs late (option flag_skip_u16; the flags
+// path of bucket_triage_one alone).  The first window of the bucket list is
+// its first *nlist >> k entries, as in every split launch; pass 2 works per
+// (slice, group) chunk, so the partition's boundary is rounded up to the
+// slice: with D the slice after the window's last bucket (0: the window is
+// empty), the chunks of slices < D are scattered before the first bucket
+// launch, in 4-byte entries, those of slices >= D after the flag summary --
+// in 2-byte entries, the 16-bit signal alone, when every record is flagged
+// (k_p2_scatter16, k_bucket_sets<true>), else in 4-byte entries
+// (k_p2_scatter, k_bucket<.., kSkip>).  A 2-byte entry stands at byte
+// 2 * position of the pass-2 buffer, so the bucket descriptors serve both
+// widths.  The rest of slice D - 1 past the first window is in 4-byte entries
+// either way (k_bucket_sets<false> over it).  With every bucket non-empty (a
+// C2 batch) D = 256 >> k and that rest is empty.
+// The two device words that say where the boundary lies, after the four
+// tickets of kTK: the list position of slice D's first bucket, and the number
+// of chunks of the slices < D (k_late_bounds, sg_bucket.hip).
+enum : uint32_t { kLateList = 4, kLateChunks = 5, kTkWords = 8 };
+struct P2Late {
+  int win;                 // 1: the chunks of slices < D, 2: the others
+  bool u16;                // win 2: the 2-byte form
+  const uint32_t* bounds;  // the launch's kTK words
+  const uint32_t* fs_cnt;  // win 2: the summary's full blocks against the launch's: all-flagged iff equal
+  uint32_t fs_nblk;
+  uint32_t* fs_u16;        // "flag_skip_u16"
+};
+
+// A BucketPlan's pass-2 output (kV2) holds 4-byte entries, (t & 0xFFFF) << 16
+// | record-in-group, for every caller that keeps or reuses a partition: the
+// two-phase protocol and the pipelined loop (sg_prefix.hip), the ordered
+// outputs, the emitting bucket forms, the M0-filter regime's fallback and the
+// trace entry's front stage run partition_pass2 whole, before any flag exists.
+// Only a late pass 2 (P2Late) leaves 2-byte entries there, and only in a
+// window that k_bucket_sets<true> then reads: nothing else sees them, and an
+// all-flagged window cannot spill, so k_bucket_direct reads 4-byte entries.
 struct BucketPlan {
   uint64_t n, nrec, nA, nB, T, NG, ng, gmax;
   WsPlan p;         // offsets from the plan's start, indexed by Region
@@ -163,11 +198,22 @@ struct BucketPlan {
 int partition_pass1(sg_ctx* ctx, const uint32_t* d_vals, const uint64_t* d_off, size_t ws_base, bool reserved,
                     BucketPlan& bp, bool trace, bool plane);
 int partition_pass2(sg_ctx* ctx, const BucketPlan& bp, bool plane = true);
+// pass 2 in its parts, for a late pass 2: the chunk tables, byte histogram and
+// scan; the bucket tables and list (they need the scan alone); the chunk
+// descriptors again, the blocks of each window contiguous; one window's scatter
+int partition_pass2_tables(sg_ctx* ctx, const BucketPlan& bp, bool plane);
+int partition_pass2_buckets(sg_ctx* ctx, const BucketPlan& bp);
+int partition_pass2_windows(sg_ctx* ctx, const BucketPlan& bp, const uint32_t* bounds);
+int partition_pass2_scatter(sg_ctx* ctx, const BucketPlan& bp, const P2Late* late);
 int partition_one(sg_ctx* ctx, const uint32_t* d_vals, const uint64_t* d_off, size_t ws_base, bool reserved,
                   BucketPlan& bp, bool trace = false);
 // sg_bucket.hip
+// split: -1 by the regime, else buckets_split's answer for this launch; 2 = pass 2 stopped after
+// partition_pass2_buckets, and the scatters run here, around the first bucket launch
 int buckets_one(sg_ctx* ctx, const BucketPlan& bp, uint32_t* mwords, uint32_t* nwords, uint8_t* d_rec_new,
-                const EmitArgs* emit, const uint32_t* owords = nullptr);
+                const EmitArgs* emit, const uint32_t* owords = nullptr, int split = -1);
+// the flags path's bucket stage for this launch: 0 one launch, 1 split, 2 split with a late pass 2
+int buckets_split(sg_ctx* ctx, const BucketPlan& bp, const uint8_t* d_rec_new, bool late_ok);
 // sg_m0filter.hip: the filter over pass 1's output, and its regime
 int m0_filter(sg_ctx* ctx, const BucketPlan& bp, uint32_t* mwords, uint32_t* nwords, uint8_t* d_rec_new, bool* done);
 bool m0f_try(sg_ctx* ctx);

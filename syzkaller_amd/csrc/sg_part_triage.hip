@@ -35,8 +35,16 @@ int bucket_triage_one(sg_ctx* ctx, uint32_t* mwords, uint32_t* nwords, const uin
     rc = m0_filter(ctx, bp, mwords, nwords, d_rec_new, &done);
     if (rc || done) return rc;
   }
-  rc = partition_pass2(ctx, bp, !filter);
-  if (!rc) rc = buckets_one(ctx, bp, mwords, nwords, d_rec_new, nullptr);
+  // a split bucket stage scatters pass 2 around its first launch (P2Late, sg_part.h); not after a filter that
+  // overflowed nor for a trace batch, and every other regime runs pass 2 whole
+  const int split = buckets_split(ctx, bp, d_rec_new, !filter && !trace);
+  if (split == 2) {
+    rc = partition_pass2_tables(ctx, bp, true);
+    if (!rc) rc = partition_pass2_buckets(ctx, bp);
+  } else {
+    rc = partition_pass2(ctx, bp, !filter);
+  }
+  if (!rc) rc = buckets_one(ctx, bp, mwords, nwords, d_rec_new, nullptr, nullptr, split);
   if (!rc) rc = m0f_note_partitioned(ctx, d_rec_new, nrec);
   return rc;
 }

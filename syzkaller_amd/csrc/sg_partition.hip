@@ -128,15 +128,21 @@ __global__ void k_chunk_list(const uint32_t* __restrict__ goff1, uint32_t T, uin
 // slice-group, chunk} of chunk xcd_tile(bid, G) for bid < G, empty past G;
 // dtile = the pass-1 tiles [first, last + 1) whose runs the chunk holds.
 // Lets the pass-2 kernels start their data loads after one load.
+// With `bounds` (a late pass 2, sg_part.h): blocks [0, G1) take the chunks
+// [0, G1) of the first window's slices and blocks [G1, G) the others, each
+// window's chunks spread over the XCDs as the whole list is without it.
 __global__ void k_chunk_desc(const uint32_t* __restrict__ cstart, const uint32_t* __restrict__ cgov,
                              const uint32_t* __restrict__ gcount, uint64_t gmax, const uint32_t* __restrict__ goff1,
-                             uint32_t T, uint32_t NG, const uint32_t* __restrict__ gt, uint4* __restrict__ desc,
+                             uint32_t T, uint32_t NG, const uint32_t* __restrict__ gt,
+                             const uint32_t* __restrict__ bounds, uint4* __restrict__ desc,
                              uint2* __restrict__ dtile) {
   const uint64_t bid = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (bid >= gmax) return;
   const uint32_t G = *gcount;
   if (bid < G) {
-    const uint32_t c = xcd_tile((uint32_t)bid, G), s0 = cstart[c], s1 = cstart[c + 1], j = cgov[c];
+    const uint32_t G1 = bounds ? min(bounds[kLateChunks], G) : 0u;
+    const uint32_t c = bid < G1 ? xcd_tile((uint32_t)bid, G1) : G1 + xcd_tile((uint32_t)bid - G1, G - G1);
+    const uint32_t s0 = cstart[c], s1 = cstart[c + 1], j = cgov[c];
     const uint32_t* row = goff1 + (uint64_t)(j / NG) * T;
     const uint32_t lo = gt[j % NG], hi = gt[j % NG + 1];
     desc[bid] = make_uint4(s0, s1, j, c);
@@ -704,6 +710,14 @@ struct P2Args {
   const uint32_t* goff2;   // scanned [byte][chunk]
   const uint32_t* hist2;   // [byte][chunk] counts
   uint32_t* out;           // (s & 0xFFFF) << 16 | record_in_group
+  // a late pass 2 (P2Late, sg_part.h): win 1 = blocks [0, G1), win 2 = blocks [G1, ..) and only in its case of the
+  // summary (4-byte entries: some record not flagged; k_p2_scatter16: all flagged); win 0 = every block
+  uint32_t win;
+  const uint32_t* bounds;
+  const uint32_t* fs_cnt;
+  uint32_t fs_nblk;
+  uint32_t* fs_u16;
+  const uint32_t* cstart;  // chunk starts (k_p2_scatter16 takes chunks by their number)
 };
 
 // One chunk; kFull: the chunk holds kPT entries (most do), so no entry is
@@ -782,6 +796,10 @@ __global__ __launch_bounds__(kPThreads) __attribute__((amdgpu_waves_per_eu(8, 8)
   __shared__ uint32_t cnt[256];
   __shared__ uint32_t gbase[256];
   __shared__ SegLds<uint16_t> L;
+  if (a.win) {
+    if (a.win == 2 && *a.fs_cnt == a.fs_nblk) return;  // all-flagged: k_p2_scatter16 has this window
+    if ((blockIdx.x < a.bounds[kLateChunks]) != (a.win == 1)) return;
+  }
   const uint4 dsc = a.desc[blockIdx.x];
   const uint2 dt = a.dtile[blockIdx.x];
   const uint32_t s0 = dsc.x, s1 = dsc.y;
@@ -790,6 +808,104 @@ __global__ __launch_bounds__(kPThreads) __attribute__((amdgpu_waves_per_eu(8, 8)
     p2_chunk<true>(a, stage, cnt, gbase, L, s0, s1, dsc.z, dsc.w, dt);
   else
     p2_chunk<false>(a, stage, cnt, gbase, L, s0, s1, dsc.z, dsc.w, dt);
+}
+
+// The second window of a late pass 2 when every record is flagged (P2Late,
+// sg_part.h): what is left of the launch is the set update, which uses no
+// record, so an entry is its 16-bit signal (b3 b0) alone, a u16 at byte
+// 2 * position of the same output buffer.  Same chunks, byte histogram, scan
+// and digit runs as k_p2_scatter; no segments, no tile records.  The staging
+// is 2 bytes per entry (32 KiB), and the write-out packs two entries per lane:
+// a half-wave store covers 64 consecutive entries, 128 B, where a u16 per
+// lane would issue the 4-byte form's stores for half their bytes (the
+// scatters are bound by the instructions they issue).  A run's first and last
+// entry, when it starts or ends at an odd position, go out as single u16
+// stores: the other half of that word is a neighbouring run's.
+// A block takes two consecutive chunks: the runs are laid out [byte][chunk],
+// so chunk c + 1's run of a digit follows chunk c's, and the two go out as one
+// run (two 64-entry runs of 2 bytes: 256 B, the 4-byte form's run length; a
+// lone 128-B run pays as many partial lines as a 256-B one).  stage, cnt and
+// gbase hold the first chunk's, then the second's (counts zero without one).
+__device__ __forceinline__ void tile_write16(const uint16_t* stage, const uint32_t* cnt, const uint32_t* gbase,
+                                             uint16_t* __restrict__ out, int tid) {
+  const int hw = tid >> 5, hl = tid & 31;
+  for (int d = hw; d < 256; d += kPThreads / 32) {
+    // the output positions [g0, gm) of the first chunk's run and [gm, g1) of the second's, from its slot bs on
+    const uint32_t gb = gbase[d], g0 = gb + (d ? cnt[d - 1] : 0u), gm = gb + cnt[d];
+    const uint32_t bs = d ? cnt[256 + d - 1] : 0u, g1 = gm + (cnt[256 + d] - bs);
+    const uint32_t ob = (uint32_t)kPT + bs - gm;  // second chunk: position p is stage[p + ob]
+    for (uint32_t q = (g0 >> 1) + hl; 2 * q < g1; q += 32) {  // the pair of positions 2 q, 2 q + 1
+      const uint32_t p0 = 2 * q, p1 = p0 + 1;
+      const bool v0 = p0 >= g0, v1 = p1 < g1;  // (p0 < g1 holds; neither for an empty run at an odd position)
+      const uint32_t x0 = v0 ? stage[p0 < gm ? p0 - gb : p0 + ob] : 0u;
+      const uint32_t x1 = v1 ? stage[p1 < gm ? p1 - gb : p1 + ob] : 0u;
+      if (v0 && v1)
+        *reinterpret_cast<uint32_t*>(out + p0) = x0 | (x1 << 16);
+      else if (v0)
+        out[p0] = (uint16_t)x0;
+      else if (v1)
+        out[p1] = (uint16_t)x1;
+    }
+  }
+}
+
+// one chunk ranked and staged (ends without a barrier)
+template <bool kFull>
+__device__ __forceinline__ void p2_chunk16(const P2Args& a, uint16_t* stage, uint32_t* cnt, uint32_t* gbase,
+                                           uint32_t s0, uint32_t s1, uint32_t c) {
+  const int tid = threadIdx.x, w = tid >> 6, lane = tid & 63;
+  const uint32_t G2 = *a.g2;
+  const uint32_t ebase = s0 + w * kPerWave;
+  uint32_t sv[kSteps];
+  uint32_t vmask = kFull ? (1u << kSteps) - 1 : 0u;
+#pragma unroll
+  for (int k = 0; k < kSteps; k++) {
+    const uint32_t e = ebase + k * 64 + lane;
+    if (kFull) {
+      sv[k] = a.in[e];
+    } else {
+      const bool ok = e < s1;
+      sv[k] = ok ? a.in[e] : 0u;
+      vmask |= (ok ? 1u : 0u) << k;
+    }
+  }
+  for (int f = tid; f < 256; f += kPThreads) {
+    gbase[f] = a.goff2[(uint64_t)f * G2 + c];
+    cnt[f] = a.hist2[(uint64_t)f * G2 + c];
+  }
+  __syncthreads();
+  uint32_t pos[kSteps];
+  tile_rank(sv, [](uint32_t v) { return v >> 24; }, vmask, cnt, gbase, pos);
+#pragma unroll
+  for (int k = 0; k < kSteps; k++)
+    if ((vmask >> k) & 1u) stage[pos[k]] = (uint16_t)(sv[k] >> 8);
+}
+
+// (the grid is half the host's chunk bound, rounded up)
+__global__ __launch_bounds__(kPThreads) __attribute__((amdgpu_waves_per_eu(8, 8))) void k_p2_scatter16(P2Args a) {
+  __shared__ uint16_t stage[2 * kPT];
+  __shared__ uint32_t cnt[2 * 256];
+  __shared__ uint32_t gbase[2 * 256];
+  if (*a.fs_cnt != a.fs_nblk) return;  // some record is not flagged yet: k_p2_scatter has this window
+  if (blockIdx.x == 0 && threadIdx.x == 0) atomicAdd(a.fs_u16, 1u);  // "flag_skip_u16"
+  const uint32_t G = *a.g2, G1 = min(a.bounds[kLateChunks], G), np = (G - G1 + 1) >> 1;  // chunk pairs of the window
+  if (blockIdx.x >= np) return;
+  const uint32_t c0 = G1 + 2 * xcd_tile(blockIdx.x, np);
+#pragma unroll
+  for (int h = 0; h < 2; h++) {
+    const uint32_t c = c0 + h;
+    if (c < G) {  // (block-uniform)
+      const uint32_t s0 = a.cstart[c], s1 = a.cstart[c + 1];
+      if (s1 - s0 == (uint32_t)kPT)
+        p2_chunk16<true>(a, stage + h * kPT, cnt + h * 256, gbase + h * 256, s0, s1, c);
+      else
+        p2_chunk16<false>(a, stage + h * kPT, cnt + h * 256, gbase + h * 256, s0, s1, c);
+    } else if (threadIdx.x < 256) {
+      cnt[256 + threadIdx.x] = 0;
+    }
+  }
+  __syncthreads();
+  tile_write16(stage, cnt, gbase, reinterpret_cast<uint16_t*>(a.out), threadIdx.x);
 }
 
 // --------------------------------------------------------- bucket tables ---
@@ -1011,7 +1127,7 @@ BucketPlan::BucketPlan(uint64_t n_, uint64_t nrec_) : n(n_), nrec(nrec_) {
       gmax * 16, gmax * 8,
       nb * 16, nb * NG * 4,
       256 * gmax * 4, (256 * gmax + 1) * 4, n * 4 + 64,  // (the bucket kernel's 16-B loads may read past the end)
-      (nb + 1) * 4, 16 + kFsWords * 4,
+      (nb + 1) * 4, (kTkWords + kFsWords) * 4,
       nb * 4, (nb + 1) * 4,
       nb * 4, nb * 16,
       scan32_ws(256 * (gmax > T ? gmax : T)), T * (kPT / 8),
@@ -1086,7 +1202,7 @@ int partition_pass1(sg_ctx* ctx, const uint32_t* d_vals, const uint64_t* d_off, 
   return SG_OK;
 }
 
-int partition_pass2(sg_ctx* ctx, const BucketPlan& bp, bool plane) {
+int partition_pass2_tables(sg_ctx* ctx, const BucketPlan& bp, bool plane) {
   const uint32_t* gt = bp.at<uint32_t>(ctx, kGT);
   const uint32_t* goff1 = bp.at<uint32_t>(ctx, kO1);
   uint32_t* v1 = bp.at<uint32_t>(ctx, kV1);
@@ -1098,12 +1214,9 @@ int partition_pass2(sg_ctx* ctx, const BucketPlan& bp, bool plane) {
   uint32_t* cfirst = bp.at<uint32_t>(ctx, kCF);
   uint4* cdesc = bp.at<uint4>(ctx, kCD);
   uint2* dtile = bp.at<uint2>(ctx, kDT);
-  uint4* bdesc = bp.at<uint4>(ctx, kBD);
   uint32_t* hist2 = bp.at<uint32_t>(ctx, kH2);
   uint32_t* goff2 = bp.at<uint32_t>(ctx, kO2);
   uint32_t* scr = bp.at<uint32_t>(ctx, kSC);
-  uint32_t* bnz = bp.at<uint32_t>(ctx, kBN);
-  uint32_t* blpos = bp.at<uint32_t>(ctx, kBP);
   const uint32_t T = (uint32_t)bp.T, G = (uint32_t)bp.gmax, NG = (uint32_t)bp.NG;
   const uint32_t* gcount = cbase + bp.ng;  // device: number of pass-2 chunks
   if (!plane) {
@@ -1119,29 +1232,82 @@ int partition_pass2(sg_ctx* ctx, const BucketPlan& bp, bool plane) {
   hipLaunchKernelGGL(k_chunk_list, dim3(div_up((bp.ng > bp.gmax ? bp.ng : bp.gmax) + 1, 256)), dim3(256), 0,
                      ctx->stream, goff1, T, NG, gt, bp.ng, (const uint32_t*)cbase, bp.gmax, cstart, cgov, cfirst);
   hipLaunchKernelGGL(k_chunk_desc, dim3(div_up(bp.gmax, 256)), dim3(256), 0, ctx->stream, (const uint32_t*)cstart,
-                     (const uint32_t*)cgov, gcount, bp.gmax, goff1, T, NG, gt, cdesc, dtile);
+                     (const uint32_t*)cgov, gcount, bp.gmax, goff1, T, NG, gt, (const uint32_t*)nullptr, cdesc, dtile);
   {
     ScopedTimer tm(ctx, "p2_hist");
     hipLaunchKernelGGL(k_hist_bytes, dim3(G), dim3(kHBThreads), 0, ctx->stream, (const uint8_t*)b1,
                        (const uint4*)cdesc, gcount, hist2);
   }
-  rc = scan32(ctx, hist2, goff2, 256 * bp.gmax, scr, gcount, 256);
-  if (rc) return rc;
-  P2Args a2{v1, cdesc, dtile, gcount, goff1, bp.at<uint32_t>(ctx, kTR), T, NG, goff2, hist2, bp.at<uint32_t>(ctx, kV2)};
+  return scan32(ctx, hist2, goff2, 256 * bp.gmax, scr, gcount, 256);
+}
+
+// The chunk descriptors again, each window's blocks contiguous (k_chunk_desc).
+int partition_pass2_windows(sg_ctx* ctx, const BucketPlan& bp, const uint32_t* bounds) {
+  const uint32_t* cbase = bp.at<uint32_t>(ctx, kCB);
+  hipLaunchKernelGGL(k_chunk_desc, dim3(div_up(bp.gmax, 256)), dim3(256), 0, ctx->stream,
+                     (const uint32_t*)bp.at<uint32_t>(ctx, kCS), (const uint32_t*)bp.at<uint32_t>(ctx, kCG),
+                     cbase + bp.ng, bp.gmax, (const uint32_t*)bp.at<uint32_t>(ctx, kO1), (uint32_t)bp.T,
+                     (uint32_t)bp.NG, (const uint32_t*)bp.at<uint32_t>(ctx, kGT), bounds, bp.at<uint4>(ctx, kCD),
+                     bp.at<uint2>(ctx, kDT));
+  SG_HIP(hipGetLastError());
+  return SG_OK;
+}
+
+// The scatter over every chunk, or over one window of a late pass 2 in one of
+// its forms (the grid is the host's bound either way: the blocks outside the
+// window, and every block of the form that is not the launch's case, return
+// at once).
+int partition_pass2_scatter(sg_ctx* ctx, const BucketPlan& bp, const P2Late* late) {
+  const uint32_t* cbase = bp.at<uint32_t>(ctx, kCB);
+  P2Args a2{bp.at<uint32_t>(ctx, kV1), bp.at<uint4>(ctx, kCD), bp.at<uint2>(ctx, kDT), cbase + bp.ng,
+            bp.at<uint32_t>(ctx, kO1), bp.at<uint32_t>(ctx, kTR), (uint32_t)bp.T, (uint32_t)bp.NG,
+            bp.at<uint32_t>(ctx, kO2), bp.at<uint32_t>(ctx, kH2), bp.at<uint32_t>(ctx, kV2),
+            0, nullptr, nullptr, 0, nullptr, bp.at<uint32_t>(ctx, kCS)};
+  if (late) {
+    a2.win = (uint32_t)late->win;
+    a2.bounds = late->bounds;
+    a2.fs_cnt = late->fs_cnt;
+    a2.fs_nblk = late->fs_nblk;
+    a2.fs_u16 = late->fs_u16;
+  }
   {
     ScopedTimer tm(ctx, "p2_scatter");
-    hipLaunchKernelGGL(k_p2_scatter, dim3(G), dim3(kPThreads), 0, ctx->stream, a2);
+    if (late && late->u16)
+      hipLaunchKernelGGL(k_p2_scatter16, dim3((uint32_t)(bp.gmax / 2 + 1)), dim3(kPThreads), 0, ctx->stream, a2);
+    else
+      hipLaunchKernelGGL(k_p2_scatter, dim3((uint32_t)bp.gmax), dim3(kPThreads), 0, ctx->stream, a2);
   }
+  SG_HIP(hipGetLastError());
+  return SG_OK;
+}
+
+int partition_pass2_buckets(sg_ctx* ctx, const BucketPlan& bp) {
+  uint32_t* cbase = bp.at<uint32_t>(ctx, kCB);
+  uint32_t* cfirst = bp.at<uint32_t>(ctx, kCF);
+  uint4* bdesc = bp.at<uint4>(ctx, kBD);
+  uint32_t* goff2 = bp.at<uint32_t>(ctx, kO2);
+  uint32_t* scr = bp.at<uint32_t>(ctx, kSC);
+  uint32_t* bnz = bp.at<uint32_t>(ctx, kBN);
+  uint32_t* blpos = bp.at<uint32_t>(ctx, kBP);
+  const uint32_t NG = (uint32_t)bp.NG;
+  const uint32_t* gcount = cbase + bp.ng;
   hipLaunchKernelGGL(k_bucket_desc, dim3(kNumBuckets / 256), dim3(256), 0, ctx->stream, (const uint32_t*)goff2,
                      gcount, (const uint32_t*)cfirst, bdesc, bnz);
   hipLaunchKernelGGL(k_bucket_groups, dim3(div_up((uint64_t)kNumBuckets * NG, 256)), dim3(256), 0, ctx->stream,
                      (const uint32_t*)goff2, gcount, (const uint32_t*)cbase, NG, bp.at<uint32_t>(ctx, kGB));
-  rc = scan32(ctx, bnz, blpos, kNumBuckets, scr);
+  const int rc = scan32(ctx, bnz, blpos, kNumBuckets, scr);
   if (rc) return rc;
   hipLaunchKernelGGL(k_bucket_compact, dim3(kNumBuckets / 256), dim3(256), 0, ctx->stream, (const uint4*)bdesc,
                      (const uint32_t*)blpos, bp.at<uint32_t>(ctx, kLB), bp.at<uint4>(ctx, kLQ));
   SG_HIP(hipGetLastError());
   return SG_OK;
+}
+
+int partition_pass2(sg_ctx* ctx, const BucketPlan& bp, bool plane) {
+  int rc = partition_pass2_tables(ctx, bp, plane);
+  if (!rc) rc = partition_pass2_scatter(ctx, bp, nullptr);
+  if (!rc) rc = partition_pass2_buckets(ctx, bp);
+  return rc;
 }
 
 int partition_one(sg_ctx* ctx, const uint32_t* d_vals, const uint64_t* d_off, size_t ws_base, bool reserved,
