@@ -6,15 +6,8 @@
 // (:83-110).
 //
 // The scan.  A program is cut into tiles of kCsTile << shift bytes; a wave
-// takes a tile and owns the lines that START in it: it walks 64 bytes a step
-// (four steps' loads in flight), ballots the three byte classes '\n', '(' and
-// '=' into 64-bit masks and moves from line to line with scalar bit operations
-// on them.  The state it carries from step to step is the issue's: in a line or
-// not, the line's start, the first '(' and the first '=' seen.  A line that
-// leaves the tile is walked to its end by its owner (the next tile's wave skips
-// it: it starts at the first '\n' at or after its tile's last-but-one byte), so
-// no wave waits for another and nothing is carried between waves.  A walk stops
-// SG_CALLSET_MAX_LINE bytes into a line: that line is too long whatever follows.
+// takes a tile and walks the lines that start in it with sgd::walk_lines
+// (sg_linewalk.h), the classes '(' and '=', the limit SG_CALLSET_MAX_LINE.
 // Tiles, not programs, are the unit of work, so a 1 MiB program is 4096 waves'
 // work and an empty one nobody's.  shift is 0 for offsets that do not decrease;
 // the device form's garbage offsets may make programs overlap, and then the
@@ -27,16 +20,17 @@
 // call lines and atomicMin's a program's first failure, by text position, into
 // perr[program]; scan_counts; k_cs_status gives each program its status and its
 // lines; scan_counts again gives line_off; k_cs_scan<true> walks the tiles again
-// and writes the spans, 64 lines a store; k_nt_lookup, a lane per line, hashes
-// the name (FNV-1a, 64 bits), probes the dictionary, compares the stored hash
-// and then always the bytes.  The text is read twice (plus, per line, its first
-// and last byte and the walk past the tile's end).  The only atomics are the
-// min on perr and the adds of k_cs_lens; no output cursor.
+// and writes the spans, 64 lines a store (sgd::LineGroup); k_nt_lookup, a lane
+// per line, hashes the name (FNV-1a, 64 bits), probes the dictionary, compares
+// the stored hash and then always the bytes.  The text is read twice (plus,
+// per line, its first and last byte and the walk past the tile's end).  The
+// only atomics are the min on perr and the adds of k_cs_lens; no output cursor.
 //
 // Every index is checked before it is used as an address, every probe loop is
 // bounded by the slot count, and each program's range is clamped to the buffer
 // as sg_prog_hashes_dev clamps it.
 #include "sg_internal.h"
+#include "sg_linewalk.h"
 
 #include <algorithm>
 #include <cstring>
@@ -168,6 +162,12 @@ __device__ __forceinline__ uint32_t cs_classify(const uint8_t* bytes, uint64_t s
   return kLnCall;
 }
 
+// what a call line gives: its name's span
+struct CsName {
+  uint64_t pos;
+  uint32_t len;
+};
+
 template <bool kEmit>
 __global__ __launch_bounds__(kCsBlock) void k_cs_scan(CsArgs a) {
   const uint32_t lane = threadIdx.x & 63;
@@ -192,114 +192,42 @@ __global__ __launch_bounds__(kCsBlock) void k_cs_scan(CsArgs a) {
       continue;
     }
     const uint64_t te = min(a1, tb + (1ull << sh));
-    // the lines that start in [tb, te): at a0, or behind a '\n' at tb - 1 .. te - 2
-    bool in_line = t == 0, have_b = false, have_q = false, done = false;
-    uint64_t s = a0, b = 0, q = 0;
-    uint64_t cb = t == 0 ? a0 : tb - 1;
-    uint32_t ncall = 0;
-    // the second walk: where this tile's lines go, and up to 64 of them held a lane each
-    uint64_t obase = 0, oend = 0, my_pos = 0;
-    uint32_t my_len = 0;
+    // the second walk: where this tile's lines go
+    uint64_t obase = 0, oend = 0;
     if (kEmit) {
       obase = a.line_off[p] + (a.cpos[g] - a.cpos[min((uint64_t)a.tile_off[p], a.tile_bound)]);
       oend = min((uint64_t)a.line_off[p + 1], a.cap);
     }
-    auto line_end = [&](uint64_t e) {
-      uint64_t np = 0;
-      uint32_t nlen = 0;
-      const uint32_t kind = cs_classify(a.bytes, s, e, have_b, b, have_q, q, np, nlen);
-      if (kind == kLnCall) {
-        if (kEmit) {
-          if (lane == (ncall & 63)) {
-            my_pos = np;
-            my_len = nlen;
-          }
-          if ((ncall & 63) == 63) {  // 64 lines held: one store
-            const uint64_t o = obase + (ncall - 63) + lane;
-            if (o < oend) {
-              a.name_pos[o] = my_pos;
-              a.name_len[o] = my_len;
-            }
-          }
-        }
-        ncall++;
-      } else if (!kEmit && kind != kLnSkip && lane == 0) {
-        atomicMin(&a.perr[p], (unsigned long long)(((s - a0) << 3) | kind));
+    sgd::LineGroup<CsName> calls;
+    auto store = [&](uint32_t i0, const CsName& nm) {
+      const uint64_t o = obase + i0 + lane;
+      if (o < oend) {
+        a.name_pos[o] = nm.pos;
+        a.name_len[o] = nm.len;
       }
-      in_line = false;
     };
-    while (!done) {
-      uint32_t c[4];
-#pragma unroll
-      for (uint32_t k = 0; k < 4; k++) {
-        const uint64_t pos = cb + 64 * k + lane;
-        c[k] = pos < a1 ? a.bytes[pos] : 0u;
-      }
-#pragma unroll
-      for (uint32_t k = 0; k < 4; k++) {
-        if (done) break;
-        const uint64_t base = cb + 64 * k;
-        if (base >= a1) {  // (an open line always ends in the step that holds the program's end)
-          if (in_line) line_end(a1);
-          done = true;
-          break;
-        }
-        const uint64_t nl = __ballot(c[k] == '\n'), lp = __ballot(c[k] == '('), eq = __ballot(c[k] == '=');
-        uint32_t bit = 0;
-        while (true) {
-          if (!in_line) {  // the next '\n' that a line of this tile starts behind
-            if (bit >= 64) break;
-            const uint64_t m = nl & (~0ull << bit);
-            if (!m) break;
-            const uint32_t i = (uint32_t)__builtin_ctzll(m);
-            if (base + i + 1 >= te) {
-              done = true;
-              break;
-            }
-            s = base + i + 1;
-            in_line = true;
-            have_b = have_q = false;
-            bit = i + 1;
+    sgd::walk_lines<2>(
+        a.bytes, a0, a1, tb, te, SG_CALLSET_MAX_LINE, lane,
+        [](uint32_t c, uint64_t* m) {
+          m[0] = __ballot(c == '(');
+          m[1] = __ballot(c == '=');
+        },
+        [&](uint64_t s, uint64_t e, const bool* have, const uint64_t* first) {
+          CsName nm{};
+          const uint32_t kind = cs_classify(a.bytes, s, e, have[0], first[0], have[1], first[1], nm.pos, nm.len);
+          if (kind == kLnCall) {
+            if (kEmit)
+              calls.add(lane, nm, store);
+            else
+              calls.count();
+          } else if (!kEmit && kind != kLnSkip && lane == 0) {
+            atomicMin(&a.perr[p], (unsigned long long)(((s - a0) << 3) | kind));
           }
-          if (bit >= 64) break;
-          const uint64_t from = ~0ull << bit, nlm = nl & from;
-          const uint32_t endi = nlm ? (uint32_t)__builtin_ctzll(nlm) : 64u;
-          const uint64_t reg = endi < 64 ? from & ((1ull << endi) - 1) : from;
-          if (!have_b && (lp & reg)) {
-            b = base + (uint32_t)__builtin_ctzll(lp & reg);
-            have_b = true;
-          }
-          if (!have_q && (eq & reg)) {
-            q = base + (uint32_t)__builtin_ctzll(eq & reg);
-            have_q = true;
-          }
-          if (endi < 64) {
-            line_end(base + endi);
-            bit = endi;  // (that '\n' may start the next line)
-            continue;
-          }
-          if (base + 64 >= a1) {
-            line_end(a1);
-            done = true;
-          } else if (base + 64 - s >= SG_CALLSET_MAX_LINE) {
-            line_end(base + 64);  // too long already, wherever it ends
-          }
-          break;
-        }
-        if (!in_line && base + 65 >= te) done = true;
-      }
-      cb += 256;
-    }
-    if (kEmit) {
-      const uint32_t held = ncall & 63;
-      const uint64_t o = obase + (ncall - held) + lane;
-      if (lane < held && o < oend) {
-        a.name_pos[o] = my_pos;
-        a.name_len[o] = my_len;
-      }
-    } else if (lane == 0) {
-      a.cnt[g] = ncall;
-    }
+        });
+    if (kEmit)
+      calls.flush(lane, store);
+    else if (lane == 0)
+      a.cnt[g] = calls.n;
   }
 }
 

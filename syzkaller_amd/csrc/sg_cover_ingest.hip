@@ -7,7 +7,9 @@
 // and sg_cover_table_from_text, which hands the parsed frames to the table
 // build of sg_cover_lines.hip where they lie, on the device.
 //
-// The scan is sg_call_set.hip's, over one text.  The text is cut into tiles of
+// The scan is sg_call_set.hip's (now sgd::walk_lines of sg_linewalk.h), over one
+// text, in a copy of its own: on the shared walk a2l_lines measured a quarter
+// slower (profiles/README.md).  The text is cut into tiles of
 // kCiTile bytes; a wave takes a share of consecutive tiles and owns the lines
 // that START in each: it walks 64 bytes a step (four steps' loads in flight),
 // ballots '\n' and the one byte class its parser is keyed on into 64-bit masks

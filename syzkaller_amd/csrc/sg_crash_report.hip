@@ -45,6 +45,7 @@
 // cap, the device forms' offsets through csr_range.  Every loop is bounded by
 // a line's length or halves an interval.
 #include "sg_internal.h"
+#include "sg_linewalk.h"
 #include "sg_rank.h"
 
 #include <algorithm>
@@ -243,27 +244,6 @@ __global__ __launch_bounds__(kCrBlock) void k_cr_flags(CrArgs a) {
   }
 }
 
-// ---- the whole wave on one line --------------------------------------------------------------------------------
-__device__ __forceinline__ uint64_t bcast64(uint64_t v, uint32_t src) {
-  return (uint64_t)__shfl((unsigned long long)v, (int)src);
-}
-__device__ __forceinline__ bool cr_lit_at(const uint8_t* t, uint32_t j, uint64_t p, uint64_t e) {
-  const uint32_t len = d_lits[j].len;
-  if (p > e || e - p < len) return false;
-  for (uint32_t k = 0; k < len && k < 64; k++)
-    if (t[p + k] != (uint8_t)d_lits[j].b[k]) return false;
-  return true;
-}
-// The leftmost place of literal j in [from, e), or e.  All 64 lanes, the same arguments.
-__device__ __forceinline__ uint64_t wave_leftmost(const uint8_t* t, uint32_t j, uint64_t from, uint64_t e, uint32_t lane) {
-  const uint32_t len = d_lits[j].len;
-  for (uint64_t p0 = from; p0 < e && e - p0 >= len; p0 += 64) {
-    const uint64_t m = __ballot(cr_lit_at(t, j, p0 + lane, e));
-    if (m) return p0 + (uint32_t)__builtin_ctzll(m);
-  }
-  return e;
-}
-
 // consoleOutputRe at a line's start: `^(?:<[0-9]+>)?\[ *[0-9]+\.[0-9]+\] `; *body the place behind it
 __device__ bool cr_prefix(const uint8_t* t, uint64_t s, uint64_t e, uint64_t* body) {
   uint64_t q = s;
@@ -315,10 +295,10 @@ __global__ __launch_bounds__(kCrBlock) void k_cr_line(CrArgs a) {
   bool nmi = (live & 4u) && (f & (1u << kLitNmiA)) && (f & (1u << kLitNmiB));
   for (uint64_t m = __ballot(nmi); m; m &= m - 1) {
     const uint32_t src = (uint32_t)__builtin_ctzll(m);
-    const uint64_t ls = bcast64(s, src), le = bcast64(e, src);
-    const uint64_t at = wave_leftmost(a.text, kLitNmiA, ls, le, lane);
+    const uint64_t ls = sgd::wave_bcast64(s, src), le = sgd::wave_bcast64(e, src);
+    const uint64_t at = sgd::wave_find_needle(a.text, d_lits[kLitNmiA], ls, le, lane);
     bool supp = false;
-    if (at < le) supp = wave_leftmost(a.text, kLitNmiB, at + d_lits[kLitNmiA].len, le, lane) < le;
+    if (at < le) supp = sgd::wave_find_needle(a.text, d_lits[kLitNmiB], at + d_lits[kLitNmiA].len, le, lane) < le;
     if (lane == src && supp) live &= ~4u;
   }
   uint64_t l = 0;
@@ -424,14 +404,14 @@ __global__ __launch_bounds__(kCrBlock) void k_cr_records(CrArgs a, CrRecs r) {
   }
   for (uint64_t m = __ballot(live != 0); m; m &= m - 1) {
     const uint32_t src = (uint32_t)__builtin_ctzll(m);
-    const uint64_t ls = bcast64(s, src), le = bcast64(e, src);
-    uint64_t at = bcast64(o, src);
+    const uint64_t ls = sgd::wave_bcast64(s, src), le = sgd::wave_bcast64(e, src);
+    uint64_t at = sgd::wave_bcast64(o, src);
     const uint64_t l = cr_log_of(a, ls);
     const uint64_t base = a.off[l];
     if (lane == 0) r.contains[l] = 1;
     for (uint32_t lv = (uint32_t)__shfl((int)live, (int)src); lv; lv &= lv - 1, at++) {
       const uint32_t j = (uint32_t)__builtin_ctz(lv);
-      const uint64_t p = wave_leftmost(a.text, j, ls, le, lane);
+      const uint64_t p = sgd::wave_find_needle(a.text, d_lits[j], ls, le, lane);
       if (lane != 0 || total > r.cap || at >= r.cap) continue;
       r.log[at] = (uint32_t)l;
       r.start[at] = ls - base;
@@ -473,11 +453,11 @@ __global__ __launch_bounds__(kCrBlock) void k_cr_logs(CrArgs a, CrLogs r) {
   if (!kBounds) return;
   for (uint64_t m = __ballot(in && l0 < a.nlines); m; m &= m - 1) {
     const uint32_t src = (uint32_t)__builtin_ctzll(m);
-    const uint64_t gl = bcast64(l, src), fl = bcast64(l0, src);
+    const uint64_t gl = sgd::wave_bcast64(l, src), fl = sgd::wave_bcast64(l0, src);
     const uint64_t ls = a.lstart[fl], le = cr_content(a.text, ls, a.lstart[fl + 1]);
     const uint32_t lv = a.word[fl] & kOopsMask;
     const uint32_t j = lv ? (uint32_t)__builtin_ctz(lv) : 0u;  // (a first record line has a live oops)
-    const uint64_t p = wave_leftmost(a.text, j, ls, le, lane);
+    const uint64_t p = sgd::wave_find_needle(a.text, d_lits[j], ls, le, lane);
     if (lane != 0) continue;
     const uint64_t base = a.off[gl];
     const uint64_t ll = min((uint64_t)a.last[gl], a.nlines);
@@ -520,7 +500,7 @@ __global__ __launch_bounds__(kCrBlock) void k_cr_copy(CrArgs a, uint8_t* out, ui
       else
         hi = mid - 1;
     }
-    const uint64_t lsrc = bcast64(src, lo), llen = bcast64(len, lo), lo0 = s_o[w][lo];
+    const uint64_t lsrc = sgd::wave_bcast64(src, lo), llen = sgd::wave_bcast64(len, lo), lo0 = s_o[w][lo];
     if (o >= o1 || o >= cap) continue;
     const uint64_t k = o - lo0;
     const uint64_t p = lsrc + k;

@@ -3,7 +3,8 @@ tests/hub_state_cases.py do not reach -- the 64-lines-a-store groups of a dense 
 longer than a tile, a wave with more than one tile, wide tiles of the device form, and the long-line limit at
 every place of a step.
 
-What is restated here from sg_call_set.hip, and nothing else of it:
+What is restated here from sg_call_set.hip and from the walk it runs (sgd::walk_lines and sgd::LineGroup of
+sg_linewalk.h), and nothing else of them:
   a tile is TILE << shift bytes of a program, counted from the program's start, and owns the lines that start
       in it;
   tile_bound = nbytes // TILE + 1 + nprogs, nwaves = min(tile_bound rounded up to 4, MAX_WAVES), a wave's share

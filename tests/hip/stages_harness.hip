@@ -1,7 +1,7 @@
 // stages_harness.hip -- test-only entry points over the stages every feature of
 // libsyzsig.so is built from: scan_counts, radix_sort_u64, radix_pass_runs, the
-// distinct-and-rank stages and the device helpers of sg_internal.h
-// (tests/test_stages.py).  Built as syzkaller_amd/libsgstages_test.so and
+// distinct-and-rank stages, the device helpers of sg_internal.h and the line
+// walk of sg_linewalk.h (tests/test_stages.py).  Built as syzkaller_amd/libsgstages_test.so and
 // linked against libsyzsig.so: the sg:: functions called here are that
 // library's own, the sgd:: helpers are the header's.  Nothing here is part of
 // the product ABI.
@@ -15,8 +15,10 @@
 // guards inside the context's workspace.  Bit 0 is the workspace's lower guard,
 // bit 1 its upper one, bits 2.. the buffers' in the order each call states.
 #include "csrc/sg_internal.h"
+#include "csrc/sg_linewalk.h"
 #include "csrc/sg_rank.h"
 
+#include <algorithm>
 #include <cstring>
 #include <vector>
 
@@ -150,6 +152,74 @@ __global__ __launch_bounds__(64) void k_t_wave_add(const uint32_t* in, uint32_t*
 __global__ __launch_bounds__(64) void k_t_wave_max(const int* in, int* out) {
   const uint64_t i = (uint64_t)blockIdx.x * 64 + threadIdx.x;
   out[i] = sgd::wave_incl_max(in[i]);
+}
+
+// sgd::walk_lines and sgd::LineGroup as the text scans use them: four waves a workgroup, a wave on a share of
+// consecutive tiles of 1 << tile_log bytes over the segments of a CSR, the classes the first kClasses (0, 1 or 2)
+// of the bytes cls[0] and cls[1].
+// A tile's lines go through the store group into its per_tile records of {s, e, met, first0, first1} (met: bit k
+// says class k was met; the first of a class not met is written as 0), their number into cnt.
+struct WalkArgs {
+  const uint8_t* text;
+  uint64_t nbytes;
+  const uint64_t* off;       // [nseg + 1]
+  const uint64_t* tile_off;  // [nseg + 1]
+  uint64_t nseg, ntiles, max_line;
+  uint32_t tile_log, nwaves, per_tile;
+  uint32_t cls[2];
+  uint32_t* cnt;  // [ntiles]
+  uint64_t* rec;  // [ntiles * per_tile * 5]
+};
+struct WalkRec {
+  uint64_t s, e, met, first[2];
+};
+template <uint32_t kClasses>
+__global__ __launch_bounds__(256) void k_t_walk(WalkArgs a) {
+  const uint32_t lane = threadIdx.x & 63;
+  const uint64_t wave = (uint64_t)blockIdx.x * 4 + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const uint64_t per = (a.ntiles + a.nwaves - 1) / a.nwaves;
+  const uint64_t gend = min(a.ntiles, (wave + 1) * per);
+  for (uint64_t g = wave * per; g < gend; g++) {
+    const uint64_t p = sgd::seg_search(a.tile_off, (uint64_t)0, a.nseg - 1, g);
+    uint64_t a0, a1;
+    sgd::csr_range(a.off, p, a.nbytes, a0, a1);
+    const uint64_t t = g - a.tile_off[p];
+    const uint64_t tb = a0 + (t << a.tile_log);
+    if (tb >= a1 || t > (a.nbytes >> a.tile_log)) {  // (never for a tile count made from the same offsets)
+      if (lane == 0) a.cnt[g] = 0;
+      continue;
+    }
+    const uint64_t te = min(a1, tb + (1ull << a.tile_log));
+    sgd::LineGroup<WalkRec> lines;
+    auto store = [&](uint32_t i0, const WalkRec& r) {
+      const uint32_t i = i0 + lane;
+      if (i >= a.per_tile) return;
+      uint64_t* o = a.rec + (g * a.per_tile + i) * 5;
+      o[0] = r.s;
+      o[1] = r.e;
+      o[2] = r.met;
+      o[3] = r.first[0];
+      o[4] = r.first[1];
+    };
+    sgd::walk_lines<kClasses>(
+        a.text, a0, a1, tb, te, a.max_line, lane,
+        [&](uint32_t c, uint64_t* m) {
+#pragma unroll
+          for (uint32_t k = 0; k < kClasses; k++) m[k] = __ballot(c == a.cls[k]);
+        },
+        [&](uint64_t s, uint64_t e, const bool* have, const uint64_t* first) {
+          WalkRec r{s, e, 0, {0, 0}};
+#pragma unroll
+          for (uint32_t k = 0; k < kClasses; k++)
+            if (have[k]) {
+              r.met |= 1ull << k;
+              r.first[k] = first[k];
+            }
+          lines.add(lane, r, store);
+        });
+    lines.flush(lane, store);
+    if (lane == 0) a.cnt[g] = lines.n;
+  }
 }
 
 // The RankWs of ng values behind the workspace's lower guard: rank_ws's regions, then the sort's and the scan's
@@ -489,6 +559,60 @@ int sgt_wave_max(sg_ctx* ctx, const int32_t* in, uint64_t rows, int32_t* out, ui
   SGT_RC(dout.download(ctx, out));
   SGT_RC(di.check(ctx, 2, broken));
   return dout.check(ctx, 4, broken);
+}
+
+// sgd::walk_lines over the segments off [nseg + 1] (nseg >= 1, clamped as csr_range clamps them) of text [nbytes],
+// by nwaves waves (a multiple of 4) with the first nclasses (0, 1 or 2) of the class bytes: cnt [ntiles] the lines that start in each tile, rec [ntiles * per_tile * 5]
+// their records, ntiles the segments' tiles of 1 << tile_log bytes (tile_log 6 .. 20) in segment order.
+// Guards: text, off, tile_off, cnt, rec.
+int sgt_walk_lines(sg_ctx* ctx, const uint8_t* text, uint64_t nbytes, const uint64_t* off, uint64_t nseg,
+                   uint32_t tile_log, uint64_t max_line, uint32_t nclasses, uint32_t cls0, uint32_t cls1, uint32_t nwaves,
+                   uint64_t ntiles, uint32_t per_tile, uint32_t* cnt, uint64_t* rec, uint32_t* broken) {
+  if (!ctx || !broken || !off || !nseg || !ntiles || !per_tile || !nwaves || nwaves % 4 || tile_log < 6 || tile_log > 20 ||
+      nclasses > 2)
+    return SG_EINVAL;
+  std::vector<uint64_t> tile_off(nseg + 1, 0);
+  for (uint64_t p = 0; p < nseg; p++) {
+    const uint64_t a0 = std::min(off[p], nbytes), a1 = std::min(std::max(off[p + 1], a0), nbytes);
+    tile_off[p + 1] = tile_off[p] + ((a1 - a0 + ((1ull << tile_log) - 1)) >> tile_log);
+  }
+  if (tile_off[nseg] != ntiles) return SG_EINVAL;  // (the harness's own bounds check: cnt and rec hold ntiles)
+  Locked l(ctx);
+  *broken = 0;
+  SGT_RC(ensure_device(ctx));
+  Guarded dtext, doff, dtile, dcnt, drec;
+  SGT_RC(dtext.alloc(ctx, nbytes, text));
+  SGT_RC(doff.alloc(ctx, (nseg + 1) * 8, off));
+  SGT_RC(dtile.alloc(ctx, (nseg + 1) * 8, tile_off.data()));
+  SGT_RC(dcnt.alloc(ctx, ntiles * 4));
+  SGT_RC(drec.alloc(ctx, ntiles * per_tile * 40));
+  WalkArgs a{};
+  a.text = dtext.p<uint8_t>();
+  a.nbytes = nbytes;
+  a.off = doff.p<uint64_t>();
+  a.tile_off = dtile.p<uint64_t>();
+  a.nseg = nseg;
+  a.ntiles = ntiles;
+  a.max_line = max_line;
+  a.tile_log = tile_log;
+  a.nwaves = nwaves;
+  a.per_tile = per_tile;
+  a.cls[0] = cls0;
+  a.cls[1] = cls1;
+  a.cnt = dcnt.p<uint32_t>();
+  a.rec = drec.p<uint64_t>();
+  const dim3 grid(nwaves / 4), block(256);
+  if (nclasses == 0) hipLaunchKernelGGL(k_t_walk<0>, grid, block, 0, ctx->stream, a);
+  if (nclasses == 1) hipLaunchKernelGGL(k_t_walk<1>, grid, block, 0, ctx->stream, a);
+  if (nclasses == 2) hipLaunchKernelGGL(k_t_walk<2>, grid, block, 0, ctx->stream, a);
+  SGT_RC(sync_check(ctx));
+  SGT_RC(dcnt.download(ctx, cnt));
+  SGT_RC(drec.download(ctx, rec));
+  SGT_RC(dtext.check(ctx, 2, broken));
+  SGT_RC(doff.check(ctx, 4, broken));
+  SGT_RC(dtile.check(ctx, 6, broken));
+  SGT_RC(dcnt.check(ctx, 8, broken));
+  return drec.check(ctx, 10, broken);
 }
 
 }  // extern "C"

@@ -1,6 +1,6 @@
 """Cases of tests/test_stages.py: inputs for the stages every feature shares (scan_counts, radix_sort_u64,
-radix_pass_runs, the distinct-and-rank stages, the device helpers of sg_internal.h), each at the edge it is named
-for, with the numpy references they are compared to.
+radix_pass_runs, the distinct-and-rank stages, the device helpers of sg_internal.h, the line walk of
+sg_linewalk.h), each at the edge it is named for, with the numpy references they are compared to.
 
 What is restated here from the stages, and nothing else of them:
   the scan works in tiles of SCAN_TILE counts, and a level of tile sums is scanned in turn while it has more than
@@ -9,7 +9,9 @@ What is restated here from the stages, and nothing else of them:
   the sort's windows: 8-bit digits from ctz(vary) upwards in steps of 8, a window kept when vary has a bit in it
       (sort_windows); the result is the stable order by the kept windows, most significant last-sorted, and every
       other bit of a key travels with it as payload (window_key, sort_reference);
-  csr_range's clamp (csr_range).
+  csr_range's clamp (csr_range);
+  the line walk reads WALK_STEP bytes a step and WALK_LOAD bytes a load, from its segment's start in the head tile
+      and from one byte before its tile in every other (walk_origin), and stores WALK_GROUP lines at a time.
 The CPU tests of test_stages.py show that each case is where it claims to be; the expected values are numpy's."""
 import numpy as np
 
@@ -385,3 +387,161 @@ def wave_max_rows():
     rows = [one, rng.integers(-1, 1 << 31, size=(16, 64)).astype(np.int32),
             rng.integers(-1, 4, size=(8, 64)).astype(np.int32), np.full((1, 64), -1, np.int32)]
     return np.concatenate(rows)
+
+
+# ---- the line walk (sg_linewalk.h) ----------------------------------------------------------
+WALK_STEP = 64
+WALK_LOAD = 256
+WALK_GROUP = 64
+WALK_MAX_LINE = 192
+WALK_NO_LIMIT = 1 << 20
+WALK_TILE_LOGS = (6, 8)
+WALK_CLS = (ord("("), ord("="))
+NL = 10
+
+
+def walk_tile_off(off, nbytes, tile_log):
+    """[nseg + 1]: the first tile of each segment, in segment order."""
+    out = [0]
+    for p in range(len(off) - 1):
+        a0, a1 = csr_range(off, p, nbytes)
+        out.append(out[-1] + ((a1 - a0 + (1 << tile_log) - 1) >> tile_log))
+    return out
+
+
+def walk_origin(a0, s, tile_log):
+    """Where the wave that owns a line starting at s begins to read: its steps and loads count from there."""
+    t = (s - a0) >> tile_log
+    return a0 if t == 0 else a0 + (t << tile_log) - 1
+
+
+def walk_record(text, s, e, cls):
+    """(s, e, met, first0, first1) of the line [s, e): the classes met in it and the leftmost place of each."""
+    met, first = 0, [0, 0]
+    for k, c in enumerate(cls):     # (one or no class: the others are never met)
+        at = text.find(bytes([c]), s, e)
+        if at >= 0:
+            met |= 1 << k
+            first[k] = at
+    return (s, e, met, first[0], first[1])
+
+
+def walk_reference(text, off, tile_log, cls):
+    """Per tile, the records of the lines that start in it: each segment split at '\n', a trailing fragment without
+    '\n' a line, nothing behind a final '\n', a line in the tile that holds its first byte.  No limit here."""
+    tile_off = walk_tile_off(off, len(text), tile_log)
+    tiles = [[] for _ in range(tile_off[-1])]
+    for p in range(len(off) - 1):
+        a0, a1 = csr_range(off, p, len(text))
+        s = a0
+        while s < a1:
+            e = text.find(b"\n", s, a1)
+            e = a1 if e < 0 else e
+            tiles[tile_off[p] + ((s - a0) >> tile_log)].append(walk_record(text, s, e, cls))
+            s = e + 1
+    return tiles
+
+
+def walk_case(segs, tile_log, max_line=WALK_MAX_LINE, cls=WALK_CLS, nwaves=0, per_tile=80):
+    """(text, off, tile_log, max_line, cls, nwaves, per_tile) over the segments, back to back; nwaves 0: a wave a
+    tile."""
+    text = b"".join(segs)
+    off = [0]
+    for g in segs:
+        off.append(off[-1] + len(g))
+    ntiles = walk_tile_off(off, len(text), tile_log)[-1]
+    return text, off, tile_log, max_line, cls, nwaves or (max(ntiles, 1) + 3) // 4 * 4, per_tile
+
+
+WALK_OWNER_SHIFTS = (-3, -2, -1, 0, 1)   # the '\n' at te + d: the next line starts at te - 2 .. te + 2
+
+
+def walk_ownership_segs(tile_log):
+    """For the tile edge te behind the head tile and the one behind the second tile, a '\n' at te - 3 .. te + 1 in
+    a segment of three tiles and a bit; then the segment's own end: a final '\n', and a last line of one byte."""
+    tile = 1 << tile_log
+    segs = []
+    for edge in (1, 2):
+        for d in WALK_OWNER_SHIFTS:
+            g = bytearray(b"o" * (3 * tile + 5))
+            g[edge * tile + d] = NL
+            segs.append(bytes(g))
+    segs.append(b"p" * (tile - 1) + b"\n")          # nothing follows the final '\n', the tile's last byte
+    segs.append(b"p" * (tile - 2) + b"\nq")         # a line that is the tile's and the segment's last byte
+    segs.append(b"p" * (tile - 1) + b"\nq")         # the same behind the tile edge: the second tile's
+    segs.append(b"p" * tile + b"\n")                # a final '\n' alone in the second tile: it owns nothing
+    return segs
+
+
+def walk_span_segs():
+    """Lines over three tiles and more of 64 bytes, from the head tile and from a later one, with and without a
+    last '\n'; SPAN_LONG of them also leave the owner's first load."""
+    segs = []
+    for lead in (b"", b"k" * 70 + b"\n"):
+        for n in (150, WALK_MAX_LINE - 1, 300, 600):
+            body = b"s" * 20 + b"(" + b"s" * (n - 41) + b"=" + b"s" * 19
+            segs.append(lead + body + b"\nt\n")
+            segs.append(lead + body)
+    return segs
+
+
+WALK_CLASS_EDGES = (64, 128, 256, 320, 512)
+
+
+def walk_class_segs():
+    """The hand-written rules, then for every edge E and d in -2 .. 1 a line [E + d - 90, E + d + 40) with '(' at
+    E + d and '=' one further, between two lines of filler."""
+    segs = [
+        b"(abc\n=abc\n", b"abc(\nabc=\n", b"(\n=\n", b"abc(", b"abc=",
+        b"a(b\nccc\n", b"a=b\nccc\n",                   # the previous line's class is not carried over
+        b"aaa\n(b\n", b"aaa\n=b\n", b"\n(=\n",         # a class behind the line's '\n' in the same step is not its
+        b"a(b=c\n", b"a=b(c\n", b"a((b(=c==\n", b"==((\n",
+    ]
+    for edge in WALK_CLASS_EDGES:
+        for d in (-2, -1, 0, 1):
+            at = edge + d
+            s = at - 90
+            lead = bytearray(b"f" * s)               # lines of 100 bytes, the last one up to the '\n' at s - 1
+            lead[s - 1::-100] = b"\n" * len(lead[s - 1::-100])
+            segs.append(bytes(lead) + b"c" * 90 + b"(=" + b"c" * 38 + b"\n" + b"g" * 9)
+    return segs
+
+
+def walk_segment_segs(tile_log):
+    """Lengths 0, 1, tile - 1, tile, tile + 1 (the first leaves every later start odd), with and without '\n's; only
+    "\n"; "\n\n\n"; and a segment without '\n' or class byte between neighbours that begin and end with them."""
+    tile = 1 << tile_log
+    segs = [b"u"]
+    for n in (0, 1, tile - 1, tile, tile + 1):
+        segs.append(b"v" * n)
+        segs.append((b"w(\n=" * tile)[:n])
+    segs += [b"\n", b"\n\n\n", b"(=\n", b"xxxx", b"\n(=", b"(=\n", b"", b"yy", b"\n"]
+    return segs
+
+
+def walk_limit_segs(max_line=WALK_MAX_LINE):
+    """Lines of max_line - 1, max_line and max_line + 1 bytes from each of the 64 places of a step, a '(' early and
+    a '=' as the last byte, and a short line behind each."""
+    segs = []
+    for n in (max_line - 1, max_line, max_line + 1):
+        for o in range(WALK_STEP):
+            lead = b"z" * (o - 1) + b"\n" if o else b""
+            segs.append(lead + b"L" * 5 + b"(" + b"L" * (n - 7) + b"=" + b"\nt(\n")
+    return segs
+
+
+WALK_DENSE_COUNTS = (63, 64, 65, 128, 129)
+WALK_FEW_WAVES = (4, 8, 12)   # against 188 tiles of 64 bytes and 75 of 256 (walk_class_segs + walk_dense_segs)
+
+
+def walk_dense_segs():
+    """Tiles of 256 bytes in which n lines start: n - 1 empty ones (129 lines of a byte of content and its '\\n'
+    do not start in 256 bytes, so a line here is its '\\n' alone, s == e) and one that runs to the segment's end
+    in the next tile; as the head tile, and behind a tile of one line.  The records differ in s only, which is
+    what "written once, in order" is read from."""
+    segs = []
+    for n in WALK_DENSE_COUNTS:
+        dense = b"\n" * (n - 1) + b"d" * (256 - (n - 1)) + b"d" * 10
+        segs.append(dense)
+        segs.append(b"h" * 255 + b"\n" + dense)
+    return segs

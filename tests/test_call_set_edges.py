@@ -1,7 +1,7 @@
-"""The CallSet scan (sg_call_set.hip) at the edges of its walk: tiles dense enough for the 64-lines-a-store
-groups, every byte class on both sides of a tile boundary, lines longer than a tile, a batch of more tiles than
-waves, the wide tiles the device form takes for overlapping programs, and the long-line limit at the places of
-a 64-byte step.
+"""The CallSet scan (sg_call_set.hip, over the walk of sg_linewalk.h) at the edges of its walk: tiles dense
+enough for the 64-lines-a-store groups, every byte class on both sides of a tile boundary, lines longer than a
+tile, a batch of more tiles than waves, the wide tiles the device form takes for overlapping programs, and the
+long-line limit at the places of a 64-byte step.
 
 tests/call_set_cases.py builds each family and restates the few constants a case sits on.  The CPU tests below
 assert on each case the property it relies on (lines per tile, positions met, tile totals and a wave's share,
@@ -45,7 +45,9 @@ def test_restated_constants_are_the_kernel_file_s():
     assert "return nbytes / kCsTile + 1 + nprogs;" in src                       # tile_bound
     assert "std::min<uint64_t>((pl.bound + 3) & ~3ull, kCsMaxWaves)" in src      # nwaves
     assert "(total + a.nwaves - 1) / a.nwaves" in src                            # per
-    assert "(ncall & 63) == 63" in src and S.GROUP == 64
+    walk = open(os.path.join(ROOT, "syzkaller_amd", "csrc", "sg_linewalk.h")).read()   # the store group is the walk's
+    assert "sgd::LineGroup<CsName> calls;" in src and "kLineGroup = %d;" % S.GROUP in walk
+    assert "(n & (kLineGroup - 1)) == kLineGroup - 1" in walk and S.GROUP == 64
     assert "while (k + 1 < kCsShifts && sums[k] + nprogs > bound) k++;" in src   # pick_shift
     assert S.MAX_LINE == OR.MAX_LINE
     # the helper: call lines by the tile they start in, a name behind `rN = ` counted where its line starts

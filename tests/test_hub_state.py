@@ -64,7 +64,7 @@ def test_header_binding_and_library():
         assert callable(getattr(H.HubState, m)), m
     assert callable(SigSet.remove)
     assert H.CALLSET_MAX_LINE == K.MAX_LINE == OR.MAX_LINE and H.CALLSET_ERRORS == OR.ERRORS and H.NAME_UNKNOWN == UNK
-    for f in ("sg_call_set.hip", "sg_hub_state.hip"):
+    for f in ("sg_call_set.hip", "sg_hub_state.hip", "sg_linewalk.h"):
         unit = open(os.path.join(ROOT, "syzkaller_amd", "csrc", f)).read()
         assert "getenv" not in unit, f
 

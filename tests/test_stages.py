@@ -1,7 +1,8 @@
 """The stages every feature shares, each run alone through the test-only harness library
 (tests/hip/stages_harness.hip, built as syzkaller_amd/libsgstages_test.so and linked against libsyzsig.so) and
 compared, exactly, with numpy: scan_counts, radix_sort_u64, radix_pass_runs, the distinct-and-rank stages of
-sg_rank.hip and the device helpers of sg_internal.h.  Every buffer a stage is given, and its share of the
+sg_rank.hip, the device helpers of sg_internal.h and the line walk of sg_linewalk.h (against a plain Python
+restatement of "split at '\\n'").  Every buffer a stage is given, and its share of the
 workspace (its *_ws bound, at an offset of the test's choosing), lies between two guards, and every test asserts
 that the guards are intact.  The CPU tests show that the library is there and that each case of
 tests/stages_cases.py is where it claims to be."""
@@ -40,6 +41,8 @@ SGT = {
     "sgt_seg_search": (c_int, [c_void_p, P64, c_uint32, P64, c_uint64, P64, P64, P32]),
     "sgt_wave_add": (c_int, [c_void_p, P32, c_uint64, P32, P32]),
     "sgt_wave_max": (c_int, [c_void_p, PI32, c_uint64, PI32, P32]),
+    "sgt_walk_lines": (c_int, [c_void_p, P8, c_uint64, P64, c_uint64, c_uint32, c_uint64, c_uint32, c_uint32, c_uint32,
+                               c_uint32, c_uint64, c_uint32, P32, P64, P32]),
 }
 _PTR = {np.dtype(np.uint8): P8, np.dtype(np.uint32): P32, np.dtype(np.uint64): P64, np.dtype(np.int32): PI32}
 _harness = None
@@ -290,6 +293,103 @@ def test_helper_cases_are_where_they_claim():
     assert (mx[-1] == -1).all()
 
 
+def _walk_lines(segs, tile_log):
+    """[(segment, a0, tile in the segment, record)] of every line of the case over segs, no limit."""
+    text, off = K.walk_case(segs, tile_log)[:2]
+    tile_off = K.walk_tile_off(off, len(text), tile_log)
+    out = []
+    for g, lines in enumerate(K.walk_reference(text, off, tile_log, K.WALK_CLS)):
+        p = max(i for i in range(len(segs)) if tile_off[i] <= g and off[i] < off[i + 1])
+        out += [(p, off[p], g - tile_off[p], r) for r in lines]
+    return text, out
+
+
+def test_walk_cases_are_where_they_claim():
+    hdr = open(os.path.join(ROOT, "syzkaller_amd", "csrc", "sg_linewalk.h")).read()
+    assert "kWalkStep = %d;" % K.WALK_STEP in hdr and "kWalkLoad = %d;" % (K.WALK_LOAD // K.WALK_STEP) in hdr
+    assert "kLineGroup = %d;" % K.WALK_GROUP in hdr and "cb += kWalkLoad * kWalkStep;" in hdr
+    # the restatement, by hand: two segments, the second from an odd place; a line is its first byte's tile's
+    text = b"ab(\n\n=" + b"x" * 70 + b"\nq"
+    ref = K.walk_reference(text, [0, 5, len(text)], 6, K.WALK_CLS)
+    assert ref == [[(0, 3, 1, 2, 0), (4, 4, 0, 0, 0)], [(5, 76, 2, 0, 5)], [(77, 78, 0, 0, 0)]]
+    assert K.walk_tile_off([0, 5, len(text)], len(text), 6) == [0, 1, 3]
+    assert K.walk_origin(5, 5, 6) == 5 and K.walk_origin(5, 68, 6) == 5 and K.walk_origin(5, 69, 6) == 68
+    for tile_log in K.WALK_TILE_LOGS:
+        tile = 1 << tile_log
+        # ownership: the line behind a '\n' at te + d starts at te + d + 1 and is the tile's that holds that byte
+        segs = K.walk_ownership_segs(tile_log)
+        _, lines = _walk_lines(segs, tile_log)
+        k = 0
+        for edge in (1, 2):
+            owners = []
+            for d in K.WALK_OWNER_SHIFTS:
+                mine = [(t, r) for p, a0, t, r in lines if p == k]
+                assert len(mine) == 2 and mine[1][1][0] - off_of(segs, k) == edge * tile + d + 1
+                owners.append(mine[1][0])
+                k += 1
+            assert owners == [edge - 1, edge - 1, edge, edge, edge]
+        tail = [[(t, r[1] - r[0]) for p, a0, t, r in lines if p == k + i] for i in range(4)]
+        assert tail == [[(0, tile - 1)], [(0, tile - 2), (0, 1)], [(0, tile - 1), (1, 1)], [(0, tile)]]
+        # segments: the lengths, odd starts, empty lines
+        segs = K.walk_segment_segs(tile_log)
+        assert {0, 1, tile - 1, tile, tile + 1} <= {len(g) for g in segs} and b"\n" in segs and b"\n\n\n" in segs
+        text, lines = _walk_lines(segs, tile_log)
+        assert sum(a0 % 2 for p, a0, t, r in lines) > len(lines) // 3
+        assert sum(r[0] == r[1] for p, a0, t, r in lines) >= 5
+        at = segs.index(b"xxxx")
+        assert segs[at - 1][-1:] == b"\n" and segs[at - 1][-2:-1] == b"=" and segs[at + 1][:2] == b"\n("
+        assert [r[1:] for p, a0, t, r in lines if p == at] == [(off_of(segs, at) + 4, 0, 0, 0)]
+    # spans, a tile a step: three tiles and more, and SPAN lines that leave the owner's first load
+    text, lines = _walk_lines(K.walk_span_segs(), 6)
+    long = [(p, a0, t, r) for p, a0, t, r in lines if r[1] - r[0] >= 150]
+    assert len(long) == 16 and all((r[1] - 1 - a0) // 64 - t >= 2 for p, a0, t, r in long)
+    past = [r for p, a0, t, r in long if r[1] - K.walk_origin(a0, r[0], 6) > K.WALK_LOAD]
+    assert len(past) >= 8 and {t > 0 for p, a0, t, r in long} == {False, True}
+    assert sum(text[r[1]:r[1] + 1] == b"\n" for p, a0, t, r in long) == 8     # the others end with their segment
+    assert all(r[2] == 3 for p, a0, t, r in long)
+    assert {r[1] - r[0] for p, a0, t, r in long} == {150, K.WALK_MAX_LINE - 1, 300, 600}
+    # classes: each one on both sides of a step's and of a load's edge, counted from where its owner reads
+    for tile_log in K.WALK_TILE_LOGS:
+        text, lines = _walk_lines(K.walk_class_segs(), tile_log)
+        assert all(r[1] - r[0] < K.WALK_MAX_LINE for p, a0, t, r in lines)
+        for k in (0, 1):
+            rel = {r[3 + k] - K.walk_origin(a0, r[0], tile_log) for p, a0, t, r in lines if r[2] >> k & 1}
+            assert {K.WALK_STEP - 1, 0} <= {x % K.WALK_STEP for x in rel}
+            if tile_log == 8:     # (at 6 a line below the limit ends inside its owner's first load)
+                assert {K.WALK_LOAD - 1, K.WALK_LOAD} <= rel
+            first = {r[3 + k] - r[0] for p, a0, t, r in lines if r[2] >> k & 1}
+            last = {r[1] - 1 - r[3 + k] for p, a0, t, r in lines if r[2] >> k & 1}
+            assert 0 in first and 0 in last
+        assert {r[2] for p, a0, t, r in lines} == {0, 1, 2, 3}
+        assert any(r[2] == 3 and r[3] < r[4] for p, a0, t, r in lines) and any(r[2] == 3 and r[3] > r[4] for p, a0, t, r in lines)
+    # the limit: every place of a step, on both sides
+    for tile_log in K.WALK_TILE_LOGS:
+        text, lines = _walk_lines(K.walk_limit_segs(), tile_log)
+        for n in (K.WALK_MAX_LINE - 1, K.WALK_MAX_LINE, K.WALK_MAX_LINE + 1):
+            places = {(r[0] - K.walk_origin(a0, r[0], tile_log)) % K.WALK_STEP for p, a0, t, r in lines if r[1] - r[0] == n}
+            assert places == set(range(K.WALK_STEP)), (tile_log, n)
+    # the store group
+    text, lines = _walk_lines(K.walk_dense_segs(), 8)
+    per = {}
+    for p, a0, t, r in lines:
+        per[(p, t)] = per.get((p, t), 0) + 1
+    assert [per[(2 * i, 0)] for i in range(5)] == [per[(2 * i + 1, 1)] for i in range(5)] == list(K.WALK_DENSE_COUNTS)
+    assert K.WALK_GROUP == 64 and all((p, 1 + p % 2) not in per for p in range(10))
+    # a wave's share: several tiles each; with and without a shorter last share; with and without idle waves
+    shares = []
+    for nwaves in K.WALK_FEW_WAVES:
+        for case in walk_share_cases(nwaves):
+            ntiles = len(K.walk_reference(case[0], case[1], case[2], case[4]))
+            per = (ntiles + nwaves - 1) // nwaves
+            assert per >= 2 and case[5] == nwaves
+            shares.append((ntiles % per != 0, (nwaves - 1) * per >= ntiles))
+    assert {a for a, _ in shares} == {b for _, b in shares} == {False, True}
+
+
+def off_of(segs, k):
+    return sum(len(g) for g in segs[:k])
+
+
 # ---- GPU: scan_counts ---------------------------------------------------------------
 def gpu_scan(ctx, counts, ws_used):
     out = np.full(counts.size + 1, 0x1111111111111111, np.uint64)
@@ -504,6 +604,94 @@ def test_rank_group_first(ctx):
         assert np.array_equal(first, wfirst), name
         absent = np.setdiff1d(np.arange(ngroups), g)
         assert (first[absent] == 0).all(), name                              # groups without members keep 0
+
+
+# ---- GPU: the line walk ----------------------------------------------------------------------
+FILL64 = np.uint64(0xEEEEEEEEEEEEEEEE)
+
+
+def check_walk(ctx, case, nclasses=2):
+    """One harness call against the restatement: every tile's count and records, exactly; of a line of max_line
+    bytes or more one record with the true start and max_line <= e - s <= the true length, its classes those of
+    [s, e), and none for its remainder; nothing written behind a tile's records.  With nclasses below 2 the walk is
+    the one of fewer classes, and the classes left out are never met."""
+    text, off, tile_log, max_line, cls, nwaves, per_tile = case
+    cls2, cls = cls, cls[:nclasses]
+    want = K.walk_reference(text, off, tile_log, cls)
+    ntiles = len(want)
+    assert ntiles and max(len(w) for w in want) <= per_tile
+    cnt = np.full(ntiles, 0xFFFFFFFF, np.uint32)
+    rec = np.zeros((ntiles, per_tile, 5), np.uint64)
+    t8 = np.frombuffer(text, np.uint8).copy()
+    o64 = np.array(off, np.uint64)
+    run("sgt_walk_lines", ctx, ptr(t8) if t8.size else None, t8.size, ptr(o64), len(off) - 1, tile_log, max_line, nclasses,
+        cls2[0], cls2[1], nwaves, ntiles, per_tile, ptr(cnt), ptr(rec))
+    assert cnt.tolist() == [len(w) for w in want]
+    for g, lines in enumerate(want):
+        got = [tuple(r) for r in rec[g, :len(lines)].tolist()]
+        for k, (s, e, _, _, _) in enumerate(lines):
+            if e - s >= max_line:
+                assert got[k][0] == s and max_line <= got[k][1] - s <= e - s, (g, k, got[k], s, e)
+                e = got[k][1]
+            assert got[k] == K.walk_record(text, s, e, cls), (g, k)
+        assert (rec[g, len(lines):] == FILL64).all(), g
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("tile_log", K.WALK_TILE_LOGS)
+def test_walk_lines_ownership_and_segments(ctx, tile_log):
+    check_walk(ctx, K.walk_case(K.walk_ownership_segs(tile_log), tile_log))
+    check_walk(ctx, K.walk_case(K.walk_segment_segs(tile_log), tile_log))
+    check_walk(ctx, K.walk_case([b""] * 3 + [b"r"], tile_log))
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("tile_log", K.WALK_TILE_LOGS)
+def test_walk_lines_classes(ctx, tile_log):
+    segs = K.walk_class_segs()
+    check_walk(ctx, K.walk_case(segs, tile_log))
+    check_walk(ctx, K.walk_case(segs, tile_log, cls=K.WALK_CLS[::-1]))
+    check_walk(ctx, K.walk_case(segs, tile_log), nclasses=1)
+    check_walk(ctx, K.walk_case(segs, tile_log), nclasses=0)
+    # a class byte of 0: what is read behind a segment's end, or behind the text's, is no byte of any class
+    zero = [g.replace(b"(", b"\0") for g in segs] + [b"nothing", b"\0"]
+    check_walk(ctx, K.walk_case(zero, tile_log, cls=(0, K.WALK_CLS[1])))
+
+
+@pytest.mark.gpu
+def test_walk_lines_spans(ctx):
+    segs = K.walk_span_segs()
+    check_walk(ctx, K.walk_case(segs, 6))
+    check_walk(ctx, K.walk_case(segs, 6, max_line=K.WALK_NO_LIMIT))
+    check_walk(ctx, K.walk_case(segs, 8, max_line=K.WALK_NO_LIMIT))
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("tile_log", K.WALK_TILE_LOGS)
+def test_walk_lines_limit_at_step_positions(ctx, tile_log):
+    check_walk(ctx, K.walk_case(K.walk_limit_segs(), tile_log))
+    check_walk(ctx, K.walk_case(K.walk_limit_segs(), tile_log), nclasses=0)
+
+
+@pytest.mark.gpu
+def test_walk_lines_store_group(ctx):
+    check_walk(ctx, K.walk_case(K.walk_dense_segs(), 8, per_tile=130))
+    check_walk(ctx, K.walk_case(K.walk_dense_segs(), 6))
+    check_walk(ctx, K.walk_case(K.walk_dense_segs(), 8, per_tile=130), nclasses=0)
+
+
+def walk_share_cases(nwaves):
+    return [K.walk_case(K.walk_class_segs() + K.walk_dense_segs(), tile_log, nwaves=nwaves, per_tile=130)
+            for tile_log in K.WALK_TILE_LOGS]
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("nwaves", K.WALK_FEW_WAVES)
+def test_walk_lines_more_tiles_than_waves(ctx, nwaves):
+    """A wave's share of several consecutive tiles (test_walk_cases_are_where_they_claim: whole shares, a shorter
+    last one, and waves without a share)."""
+    for case in walk_share_cases(nwaves):
+        check_walk(ctx, case)
 
 
 # ---- GPU: the device helpers -----------------------------------------------------------------
